@@ -8,10 +8,15 @@ A "step" = one pass of the hot path over one per-GPU batch of 64 synthetic CCV s
 Inputs (epoch pose cache, assets, weights) are resident in HBM when the timed region starts; the per-step host work
 (loss RNG draws, Adam bias corrections, batch gather) is inside it.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel family (implicit-GEMM conv on MFMA): algorithmic
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the `--steps` steps and prints the headline
+(`value`, `ms_per_step`); everything else is measured only under `--full`:
+`roofline` is for the dominant kernel family (implicit-GEMM conv on MFMA): algorithmic
 FLOPs of the conv stack per step / summed conv-kernel time measured with HIP events on the compute stream.
 `cpu_baseline` times the CPU oracle of the same step (oracle/: C rasteriser + torch-CPU fp32 learner) on a bounded
-sample on this box's host cores."""
+sample on this box's host cores.  The sustained block, the HBM rooflines and the side legs (eval forward, DexYCB, one-pass
+weight-gradient study, JPEG decode, mixed real + synthetic step, drop-in loop, one-rank RCCL schedule) are `--full` too.
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32 / float64): see dump_outputs()."""
 import argparse
 import json
 import os
@@ -741,6 +746,66 @@ def cpu_baseline(args, cfg):
             "render_samples_per_s": round(n * iters / t_render, 2), "learner_samples_per_s": round(n * iters / t_learn, 3)}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20             # elements of a seeded sample of each large array (weights, gradient, rendered image)
+DUMP_SEED = 1234
+
+
+def _dump_array(t, sample=None, seed=DUMP_SEED):
+    """A device / host tensor -> float32 numpy (float64 stays float64); `sample`: a fixed, seeded, sorted sample of that many
+    elements of its flat view when it holds more (the whole flat view otherwise)."""
+    import numpy as np
+    import torch
+    t = t.detach()
+    if sample is not None:
+        t = t.reshape(-1)
+        if t.numel() > sample:
+            idx = np.sort(np.random.default_rng(seed).choice(t.numel(), sample, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+    a = t.cpu()
+    return a.numpy() if a.dtype == torch.float64 else a.float().numpy()
+
+
+def dump_outputs(ts, static, out_dir):
+    """What the timed step computed in its last step, as a caller of TrainStep receives it: the predictions, the loss terms, the
+    updated weights and BatchNorm statistics (seeded sample of the flat weights), the gradient of the step (seeded sample) and a
+    seeded sample of the rendered image the step learned from.  Called right after the timed block, before anything else runs."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    preds = ts.predictions()
+    for k in sorted(preds):
+        if torch.is_tensor(preds[k]):
+            arrays["pred_" + k] = _dump_array(preds[k])
+    losses = ts.out[1]
+    if torch.is_tensor(losses):
+        arrays["losses"] = _dump_array(losses)
+    if ts.fused is None and isinstance(ts.out[2], dict):          # (unfused criterion: out = (preds, total, loss dict))
+        for k in sorted(ts.out[2]):
+            v = ts.out[2][k]
+            if torch.is_tensor(v) and v.numel() <= DUMP_SAMPLE:
+                arrays["loss_" + k] = _dump_array(v)
+            elif isinstance(v, float):
+                arrays["loss_" + k] = np.array([v], dtype=np.float64)
+    store = ts.hb.store
+    arrays["weights_sample"] = _dump_array(store.flat, DUMP_SAMPLE, DUMP_SEED)
+    if store.grad is not None:
+        arrays["grad_sample"] = _dump_array(store.grad, DUMP_SAMPLE, DUMP_SEED + 1)
+    arrays["bn_stats"] = _dump_array(store.stats, DUMP_SAMPLE, DUMP_SEED + 2)
+    img = static.get("image_nhwc4_padded")
+    if not torch.is_tensor(img):
+        img = static.get("image")
+    if torch.is_tensor(img):
+        arrays["image_sample"] = _dump_array(img, DUMP_SAMPLE, DUMP_SEED + 3)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET_BYTES}-byte budget")
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -777,22 +842,32 @@ def main():
     ap.add_argument("--eval", action="store_true",
                     help="BASELINE configs[1] instead of the training step: eval-mode forward only (bs 64, conv + soft-argmax integral kernels), "
                          "with its own roofline object")
-    ap.add_argument("--sustain", type=float, default=3.0,
-                    help="seconds of the sustained block run after the timed steps (extra keys of the line; 0 = off)")
-    ap.add_argument("--no-eval-leg", action="store_true", help="skip the configs[1] eval-forward sub-object of the default line")
-    ap.add_argument("--no-dexycb-leg", action="store_true", help="skip the configs[4]-on-one-GPU sub-object of the default line")
+    ap.add_argument("--sustain", type=float, default=None,
+                    help="seconds of the sustained block run after the timed steps (extra keys of the line; 0 = off; default 3 with --full, "
+                         "else 0)")
+    ap.add_argument("--no-eval-leg", action="store_true", help="skip the configs[1] eval-forward sub-object of the --full line")
+    ap.add_argument("--no-dexycb-leg", action="store_true", help="skip the configs[4]-on-one-GPU sub-object of the --full line")
     ap.add_argument("--rccl-single-rank", action="store_true",
                     help="N = 1 only: run the multi-rank schedule (three backward graphs, SUM all-reduces + 1 / world on the comm stream, render "
                          "overlap) over a ONE-rank RCCL group -- the part of the RCCL path a 1-GPU box can execute; not the headline")
-    ap.add_argument("--no-rccl-leg", action="store_true", help="skip the one-rank RCCL schedule sub-object of the default line")
-    ap.add_argument("--no-dropin-leg", action="store_true", help="skip the reference-shaped epoch_pass loop sub-object of the default line")
-    ap.add_argument("--no-mixed-leg", action="store_true", help="skip the mixed real + synthetic training-step sub-object of the default line")
-    ap.add_argument("--no-jpeg-leg", action="store_true", help="skip the real-frame JPEG decode sub-object of the default line")
-    ap.add_argument("--no-study-leg", action="store_true", help="skip the one-pass weight-gradient study sub-object of the default line")
+    ap.add_argument("--no-rccl-leg", action="store_true", help="skip the one-rank RCCL schedule sub-object of the --full line")
+    ap.add_argument("--no-dropin-leg", action="store_true", help="skip the reference-shaped epoch_pass loop sub-object of the --full line")
+    ap.add_argument("--no-mixed-leg", action="store_true", help="skip the mixed real + synthetic training-step sub-object of the --full line")
+    ap.add_argument("--no-jpeg-leg", action="store_true", help="skip the real-frame JPEG decode sub-object of the --full line")
+    ap.add_argument("--no-study-leg", action="store_true", help="skip the one-pass weight-gradient study sub-object of the --full line")
     ap.add_argument("--wgrad-1pass", action="store_true",
                     help="PRECISION STUDY, not a parity configuration (DESIGN 12.1): weight gradients from the hi planes only (one bf16 MFMA "
                          "pass instead of three); the line's dtype says so")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline, HBM rooflines, sustained block, side legs, CPU baseline "
+                         "(a plain run only sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     args = ap.parse_args()
+    if args.sustain is None:
+        args.sustain = 3.0 if args.full else 0.0
+    if args.dump_outputs and args.eval:
+        raise SystemExit("bench.py: --dump-outputs writes the training step's results; it does not apply to --eval")
 
     # `python bench.py --gpus N` is the whole multi-GPU command (the reference's is `train_artiboost.py --gpu_id 0,1,..`,
     # train/train_artiboost.py:131,249-257): without a launcher around it, start one rank per GPU under torch.distributed.run
@@ -864,6 +939,12 @@ def main():
         torch.distributed.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1,
                                              device_id=torch.device(device))
         args.no_eval_leg = args.no_dexycb_leg = args.no_study_leg = args.no_jpeg_leg = args.no_mixed_leg = args.no_rccl_leg = args.no_dropin_leg = args.no_cpu_baseline = True
+    # the losses' per-step draws come from the host's global RNGs: seeded as train/train_artiboost.py seeds them, so that the same
+    # arguments give the same inputs from run to run
+    import random
+    import numpy as np
+    seed = ref_cfg(args.size, args.dataset)["TRAIN"]["MANUAL_SEED"]
+    random.seed(seed); np.random.seed(seed); torch.manual_seed(seed)
     cfg, model, crit, opt, loader, ts, static = build_everything(args, rank, world, device)
 
     def barrier():
@@ -906,6 +987,8 @@ def main():
     if world > 1:
         world = torch.distributed.get_world_size()
     value = args.bs * world * args.steps / dt
+    if rank == 0 and args.dump_outputs:       # the last timed step's results, before any further step or measurement changes them
+        dump_outputs(ts, ts.static, args.dump_outputs)
     sustained = None
     if args.sustain > 0:      # every rank runs it (the steps contain the gradient all-reduce)
         sustained = sustained_block(ts, loader, args, args.sustain, args.warmup + args.steps, barrier)
@@ -914,88 +997,80 @@ def main():
     out = None
     if rank == 0:
         losses = ts.out[1].float().cpu().tolist() if ts.fused is not None else []
-        roof = None
-        try:
-            conv_ms_eager, nlaunch = conv_kernel_time_ms(ts, loader, static)
-            conv_ms, graph_err, boundary_us = conv_ms_eager, None, None
-            if not args.eager and ts.use_graph and not ts.split:
-                try:          # the number the roofline is quoted on: the same launches timed inside the graph replay
-                    conv_ms, nlaunch, boundary_us = conv_kernel_time_graph_ms(ts, loader)
+        roof = base = ev = hbm = dex = study = jpg = mixed = dropin = rccl1 = None
+        if args.full:           # everything beside the headline figure
+            try:
+                conv_ms_eager, nlaunch = conv_kernel_time_ms(ts, loader, static)
+                conv_ms, graph_err, boundary_us = conv_ms_eager, None, None
+                if not args.eager and ts.use_graph and not ts.split:
+                    try:          # the number the roofline is quoted on: the same launches timed inside the graph replay
+                        conv_ms, nlaunch, boundary_us = conv_kernel_time_graph_ms(ts, loader)
+                    except Exception as e:   # noqa: BLE001
+                        graph_err = repr(e)
+                flops = GFLOP_FWD_BWD_PER_SAMPLE.get(args.size, 31.785) * 1e9 * args.bs
+                ach = flops / (conv_ms * 1e-3) / 1e12
+                roof = {"bound": "mfma", "achieved": round(ach, 2), "peak": MFMA_PEAK_TFLOPS[args.dtype], "unit": "TFLOP/s",
+                        "frac": round(ach / MFMA_PEAK_TFLOPS[args.dtype], 4), "traffic": pmc_traffic(args),
+                        "traffic_unit": f"HBM bytes per step over the conv-stack launches (PMC passes of this precision: profiles/{PMC_FILE[args.dtype]}; "
+                                        "algorithmic bytes of the stack in the same file)",
+                        "kernel": "implicit-GEMM conv stack: conv3x3_kernel / conv3x3r_kernel / conv2x2_kernel / convp_kernel / conv_gemm2_kernel / gemm_rw_kernel / "
+                                  "stem_halo_x3_kernel (fwd, dgrad) + wgrad3x3_kernel / wgrad_gemm2_kernel / wgrad_reduce (weight grad)",
+                        "conv_ms_per_step": round(conv_ms, 3), "conv_launches_per_step": nlaunch,
+                        "conv_ms_source": ("graph replay: wall-clock stamps (ab_wall_stamp) captured around every conv-stack call, the leading stamp "
+                                           "launch of each bracket (= the difference of back-to-back stamps) removed" if boundary_us is not None else "eager HIP events"),
+                        "conv_ms_per_step_eager": round(conv_ms_eager, 3), "stamp_boundary_us": None if boundary_us is None else round(boundary_us, 2),
+                        "conv_ms_instrument_note": ("the stamped replay reads HIGH: the ~113 one-thread stamp launches break kernel-to-kernel chaining; against "
+                                                    "the rocprofv3 kernel trace of the same build it read +3.5 % in round 5 (6.749 vs 6.518 ms) and "
+                                                    "+3.4 % in round 6 (profiles/round6_*_step_trace.txt) -- `frac` is a lower bound by that much")}
+                if graph_err:
+                    roof["graph_stamp_error"] = graph_err
+            except Exception as e:   # noqa: BLE001
+                roof = {"bound": "mfma", "achieved": None, "peak": MFMA_PEAK_TFLOPS[args.dtype], "unit": "TFLOP/s", "frac": None,
+                        "traffic": None, "error": repr(e)}
+            if world == 1 and not args.no_eval_leg:
+                try:
+                    ev = eval_forward(args, model, static)
                 except Exception as e:   # noqa: BLE001
-                    graph_err = repr(e)
-            flops = GFLOP_FWD_BWD_PER_SAMPLE.get(args.size, 31.785) * 1e9 * args.bs
-            ach = flops / (conv_ms * 1e-3) / 1e12
-            roof = {"bound": "mfma", "achieved": round(ach, 2), "peak": MFMA_PEAK_TFLOPS[args.dtype], "unit": "TFLOP/s",
-                    "frac": round(ach / MFMA_PEAK_TFLOPS[args.dtype], 4), "traffic": pmc_traffic(args),
-                    "traffic_unit": f"HBM bytes per step over the conv-stack launches (PMC passes of this precision: profiles/{PMC_FILE[args.dtype]}; "
-                                    "algorithmic bytes of the stack in the same file)",
-                    "kernel": "implicit-GEMM conv stack: conv3x3_kernel / conv3x3r_kernel / conv2x2_kernel / convp_kernel / conv_gemm2_kernel / gemm_rw_kernel / "
-                              "stem_halo_x3_kernel (fwd, dgrad) + wgrad3x3_kernel / wgrad_gemm2_kernel / wgrad_reduce (weight grad)",
-                    "conv_ms_per_step": round(conv_ms, 3), "conv_launches_per_step": nlaunch,
-                    "conv_ms_source": ("graph replay: wall-clock stamps (ab_wall_stamp) captured around every conv-stack call, the leading stamp "
-                                       "launch of each bracket (= the difference of back-to-back stamps) removed" if boundary_us is not None else "eager HIP events"),
-                    "conv_ms_per_step_eager": round(conv_ms_eager, 3), "stamp_boundary_us": None if boundary_us is None else round(boundary_us, 2),
-                    "conv_ms_instrument_note": ("the stamped replay reads HIGH: the ~113 one-thread stamp launches break kernel-to-kernel chaining; against "
-                                                "the rocprofv3 kernel trace of the same build it read +3.5 % in round 5 (6.749 vs 6.518 ms) and "
-                                                "+3.4 % in round 6 (profiles/round6_*_step_trace.txt) -- `frac` is a lower bound by that much")}
-            if graph_err:
-                roof["graph_stamp_error"] = graph_err
-        except Exception as e:   # noqa: BLE001
-            roof = {"bound": "mfma", "achieved": None, "peak": MFMA_PEAK_TFLOPS[args.dtype], "unit": "TFLOP/s", "frac": None,
-                    "traffic": None, "error": repr(e)}
-        base = None
-        ev = None
-        if world == 1 and not args.no_eval_leg:
+                    ev = {"error": repr(e)}
             try:
-                ev = eval_forward(args, model, static)
+                hbm = hbm_rooflines(args, loader, static, model)
             except Exception as e:   # noqa: BLE001
-                ev = {"error": repr(e)}
-        hbm = None
-        try:
-            hbm = hbm_rooflines(args, loader, static, model)
-        except Exception as e:   # noqa: BLE001
-            hbm = {"error": repr(e)}
-        dex = None
-        if world == 1 and args.dataset == "HO3D" and not args.no_dexycb_leg and not args.eager:
-            try:
-                dex = dexycb_leg(args, device)
-            except Exception as e:   # noqa: BLE001
-                dex = {"error": repr(e)}
-        study = None
-        if world == 1 and args.dtype == "bf16x3" and not args.no_study_leg and not args.eager and not args.wgrad_1pass:
-            try:
-                study = wgrad_1pass_leg(args, device)
-            except Exception as e:   # noqa: BLE001
-                study = {"error": repr(e)}
-        jpg = None
-        if world == 1 and not args.no_jpeg_leg and not args.eager:
-            try:
-                jpg = jpeg_leg(device)
-            except Exception as e:   # noqa: BLE001
-                jpg = {"error": repr(e)}
-        mixed = None
-        if world == 1 and not args.no_mixed_leg and not args.eager and args.dtype == "bf16x3" and args.bs == 64:
-            try:
-                mixed = mixed_leg(args)
-            except Exception as e:   # noqa: BLE001
-                mixed = {"error": repr(e)}
-        dropin = None
-        if world == 1 and not args.no_dropin_leg and not args.eager and args.dtype == "bf16x3" and args.dataset == "HO3D":
-            try:
-                torch.cuda.synchronize()
-                dropin = dropin_leg(args, ms)
-            except Exception as e:   # noqa: BLE001
-                dropin = {"error": repr(e)}
-        rccl1 = None
-        if world == 1 and not args.no_rccl_leg and not args.eager and not args.rccl_single_rank:
-            try:
-                torch.cuda.synchronize()
-                rccl1 = rccl_leg(args, ms)
-            except Exception as e:   # noqa: BLE001
-                rccl1 = {"error": repr(e)}
-        roof["peak_note"] = ("dense bf16 MFMA peak / 3 passes" if args.dtype == "bf16x3" else "dense MFMA peak of the operand type")
-        if world == 1 and not args.no_cpu_baseline:
-            base = cpu_baseline(args, cfg)
+                hbm = {"error": repr(e)}
+            if world == 1 and args.dataset == "HO3D" and not args.no_dexycb_leg and not args.eager:
+                try:
+                    dex = dexycb_leg(args, device)
+                except Exception as e:   # noqa: BLE001
+                    dex = {"error": repr(e)}
+            if world == 1 and args.dtype == "bf16x3" and not args.no_study_leg and not args.eager and not args.wgrad_1pass:
+                try:
+                    study = wgrad_1pass_leg(args, device)
+                except Exception as e:   # noqa: BLE001
+                    study = {"error": repr(e)}
+            if world == 1 and not args.no_jpeg_leg and not args.eager:
+                try:
+                    jpg = jpeg_leg(device)
+                except Exception as e:   # noqa: BLE001
+                    jpg = {"error": repr(e)}
+            if world == 1 and not args.no_mixed_leg and not args.eager and args.dtype == "bf16x3" and args.bs == 64:
+                try:
+                    mixed = mixed_leg(args)
+                except Exception as e:   # noqa: BLE001
+                    mixed = {"error": repr(e)}
+            if world == 1 and not args.no_dropin_leg and not args.eager and args.dtype == "bf16x3" and args.dataset == "HO3D":
+                try:
+                    torch.cuda.synchronize()
+                    dropin = dropin_leg(args, ms)
+                except Exception as e:   # noqa: BLE001
+                    dropin = {"error": repr(e)}
+            if world == 1 and not args.no_rccl_leg and not args.eager and not args.rccl_single_rank:
+                try:
+                    torch.cuda.synchronize()
+                    rccl1 = rccl_leg(args, ms)
+                except Exception as e:   # noqa: BLE001
+                    rccl1 = {"error": repr(e)}
+            roof["peak_note"] = ("dense bf16 MFMA peak / 3 passes" if args.dtype == "bf16x3" else "dense MFMA peak of the operand type")
+            if world == 1 and not args.no_cpu_baseline:
+                base = cpu_baseline(args, cfg)
         out = {"metric": f"synth samples/sec (render+fwd+bwd) {args.size}x{args.size} bs={args.bs}", "value": round(value, 2), "unit": "samples/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None,

@@ -22,7 +22,7 @@ def _last_json(out):
 def test_bench_two_ranks_end_to_end():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--allow-shared-devices", "--steps", "3", "--warmup", "2",
-           "--sustain", "0.5"]
+           "--sustain", "0.5", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = _last_json(r.stdout)
@@ -33,6 +33,36 @@ def test_bench_two_ranks_end_to_end():
     roof = line["roofline"]
     assert roof["bound"] == "mfma" and roof["achieved"] and 0 < roof["frac"] < 1
     assert line["sustained"]["sustained_samples_per_s"] > 0
+
+
+def test_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) prints the headline alone: `steps` timed steps, `ms_per_step` and `value` of those steps, nothing measured
+    beside them.  --dump-outputs writes the last timed step's results (float32 / float64, <= 64 MB); the inputs are seeded, so a second
+    run renders the same images and draws the same losses."""
+    import numpy as np
+    runs = []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        line = _last_json(r.stdout)
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["dtype"] == "bf16x3"
+        assert line["unit"] == "samples/s" and line["higher_is_better"] is True
+        assert line["ms_per_step"] > 0 and abs(line["value"] - 64 * 1e3 / line["ms_per_step"]) < 1e-2 * line["value"]
+        assert line["roofline"] is None and line["cpu_baseline"] is None and line["sustained"] is None
+        assert 0 < line["final_loss"] < 1.0
+        out = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert {"losses", "pred_joints_3d_abs", "pred_kp3d", "weights_sample", "grad_sample", "bn_stats", "image_sample"} <= set(out), sorted(out)
+        assert sum(a.nbytes for a in out.values()) <= 64 << 20
+        for k, a in out.items():
+            assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), k
+        assert abs(float(out["losses"][5]) - line["final_loss"]) <= 1e-6 * abs(line["final_loss"])
+        runs.append(out)
+    a, b = runs
+    np.testing.assert_array_equal(a["image_sample"], b["image_sample"])
+    np.testing.assert_allclose(a["losses"], b["losses"], rtol=1e-3, atol=1e-6)
+    np.testing.assert_allclose(a["weights_sample"], b["weights_sample"], rtol=1e-3, atol=1e-5)
 
 
 def test_bench_eval_leg_configs1():
@@ -68,8 +98,8 @@ def test_dropin_loop_without_segment_graphs_stays_device_bound():
 def test_dropin_epoch_pass_leg_is_within_a_tenth_of_the_headline():
     """bench.py's `dropin_epoch_pass` leg: the reference's own epoch_pass loop through the anakin.* aliases (tools/bench_dropin.py) on the same
     box as the graph-replayed headline step -- the boundary the north star names.  Round-5 review: 1.28 x the headline; required <= 1.10."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--sustain", "0", "--no-eval-leg", "--no-dexycb-leg", "--no-study-leg",
-           "--no-jpeg-leg", "--no-mixed-leg", "--no-rccl-leg"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--sustain", "0", "--no-eval-leg", "--no-dexycb-leg",
+           "--no-study-leg", "--no-jpeg-leg", "--no-mixed-leg", "--no-rccl-leg"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = _last_json(r.stdout)
@@ -106,7 +136,8 @@ def test_rccl_single_rank_schedule():
 def test_bench_rccl_single_rank_mode():
     """`bench.py --rccl-single-rank`: init_process_group("nccl", device_id=...) exactly as the N > 1 launch does it, the multi-rank
     schedule with the real collective over one rank, one JSON line that says so."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rccl-single-rank", "--steps", "3", "--warmup", "2", "--sustain", "0"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rccl-single-rank", "--steps", "3", "--warmup", "2", "--sustain", "0",
+                        "--full"],
                        capture_output=True, text=True, timeout=600, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
@@ -119,8 +150,8 @@ def test_roofline_is_timed_inside_the_replayed_step():
     conv-stack call), the eager-event number is stated beside it, and the two describe the same launches: same count, and the replayed
     kernels are not slower than the eager ones by more than the instrument's boundary uncertainty (they run 3 - 5 % FASTER: no launch gaps,
     warmer clocks), never below 0.85 of them."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--sustain", "0", "--no-eval-leg",
-           "--no-dexycb-leg", "--no-study-leg", "--no-jpeg-leg", "--no-mixed-leg", "--no-rccl-leg", "--no-dropin-leg"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--sustain", "0",
+           "--no-eval-leg", "--no-dexycb-leg", "--no-study-leg", "--no-jpeg-leg", "--no-mixed-leg", "--no-rccl-leg", "--no-dropin-leg"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     roof = _last_json(r.stdout)["roofline"]

@@ -254,6 +254,33 @@ def test_assemble_gt_batch_equals_per_sample_assembly():
     assert nz > 0                                              # the all-zero visibility branches were exercised
 
 
+def test_bench_dump_outputs_writes_seeded_float_samples(tmp_path):
+    """bench.dump_outputs (`bench.py --dump-outputs DIR`): one float32 / float64 .npy per result of the step, large arrays as a fixed,
+    seeded sample (the same elements every run), within the 64 MB budget."""
+    from types import SimpleNamespace
+    import bench
+    g = torch.Generator().manual_seed(0)
+    n = 3 * bench.DUMP_SAMPLE
+    store = SimpleNamespace(flat=torch.randn(n, generator=g), grad=torch.randn(n, generator=g), stats=torch.randn(1000, generator=g))
+    preds = {"joints_3d_abs": torch.randn(4, 21, 3, generator=g), "kp3d": torch.randn(4, 22, 3, generator=g, dtype=torch.float64)}
+    ts = SimpleNamespace(hb=SimpleNamespace(store=store), out=(preds, torch.randn(8, generator=g), {"g_kp3d": preds["kp3d"]}), fused=object(),
+                         predictions=lambda: preds)
+    static = {"image_nhwc4_padded": torch.randn(4, 70, 72, 4, generator=g).to(torch.bfloat16)}
+    outs = []
+    for tag in ("a", "b"):
+        names = bench.dump_outputs(ts, static, str(tmp_path / tag))
+        outs.append({k: np.load(tmp_path / tag / (k + ".npy")) for k in names})
+    a, b = outs
+    assert sorted(a) == ["bn_stats", "grad_sample", "image_sample", "losses", "pred_joints_3d_abs", "pred_kp3d", "weights_sample"]
+    assert a["pred_kp3d"].dtype == np.float64 and all(v.dtype == np.float32 for k, v in a.items() if k != "pred_kp3d")
+    assert a["weights_sample"].shape == (bench.DUMP_SAMPLE,) and a["bn_stats"].shape == (1000,) and a["image_sample"].shape == (4 * 70 * 72 * 4,)
+    np.testing.assert_array_equal(a["pred_joints_3d_abs"], preds["joints_3d_abs"].numpy())
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k])
+    assert np.isin(a["weights_sample"], store.flat.numpy()).all()
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BUDGET_BYTES
+
+
 def test_bench_gpus_flag_launches_the_ranks():
     """`python bench.py --gpus 2` is the whole multi-GPU command: it starts 2 ranks itself (torch.distributed.run, gloo here)
     and the line reports the world size the ranks actually formed -- not the flag."""
@@ -344,35 +371,21 @@ def test_train_script_launches_one_rank_per_listed_gpu():
 
 def test_every_type_named_by_the_reference_yamls_is_registered():
     """Every TYPE the reference's shipped YAMLs name (config/*.yaml, config_eval/*.yaml: models, backbones / heads of the
-    regression model, losses, metrics, datasets) resolves in this build's registries.  Reads the reference checkout when it is
-    there (the build container); skipped elsewhere."""
-    import glob
-    import yaml
-    files = sorted(glob.glob("/root/reference/config/*.yaml") + glob.glob("/root/reference/config_eval/*.yaml"))
-    if not files:
-        pytest.skip("no reference checkout")
+    regression model, losses, metrics, datasets) resolves in this build's registries.  The names are read from
+    tests/golden/reference_yaml_types.json (oracle/gen_reference_types.py)."""
+    import json
     from artiboost_amd import registry as R
     import artiboost_amd.criterions, artiboost_amd.datasets, artiboost_amd.hpregnet, artiboost_amd.metrics, artiboost_amd.models  # noqa: F401,E401
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    files = json.load(open(os.path.join(root, "tests", "golden", "reference_yaml_types.json")))
+    assert len(files) >= 6 and any(f["BACKBONE"] for f in files)
+    regs = {"MODEL": R.MODEL, "BACKBONE": R.BACKBONE, "HEAD": R.HEAD, "CRITERION": R.LOSS, "EVALUATOR": R.METRIC, "DATASET": R.DATASET}
     missing = []
     for f in files:
-        c = yaml.safe_load(open(f))
-        archs = c["ARCH"] if isinstance(c["ARCH"], list) else [c["ARCH"]]
-        for a in archs:
-            if R.MODEL.get(a["TYPE"]) is None:
-                missing.append((os.path.basename(f), "MODEL", a["TYPE"]))
-            if a["TYPE"] == "HOPRegNet":            # its backbone / head are registry-built torch modules
-                if R.BACKBONE.get(a["BACKBONE"]["TYPE"]) is None:
-                    missing.append((os.path.basename(f), "BACKBONE", a["BACKBONE"]["TYPE"]))
-                if R.HEAD.get(a["HEAD"]["TYPE"]) is None:
-                    missing.append((os.path.basename(f), "HEAD", a["HEAD"]["TYPE"]))
-        for key, reg in (("CRITERION", R.LOSS), ("EVALUATOR", R.METRIC)):
-            for e in c.get(key) or []:
-                if reg.get(e["TYPE"]) is None:
-                    missing.append((os.path.basename(f), key, e["TYPE"]))
-        for split in ("TRAIN", "TEST"):
-            d = (c.get("DATASET") or {}).get(split)
-            if d and R.DATASET.get(d["TYPE"]) is None:
-                missing.append((os.path.basename(f), "DATASET", d["TYPE"]))
+        for key, reg in regs.items():
+            for ty in f[key]:
+                if reg.get(ty) is None:
+                    missing.append((os.path.basename(f["file"]), key, ty))
     assert not missing, missing
 
 
