@@ -6,6 +6,12 @@
 // kinematic chain -> skinning -> 21 joints (16 + 5 fingertip vertices, reordered).
 // The blend tables (posedirs 1.26 MB, shapedirs 93 KB, J_regressor 50 KB, weights 50 KB) are shared by the batch
 // and stay L2-resident; per hand the kernel reads 232 B and writes 9.6 KB.
+//
+// The regression model's MANO layer (anakin/models/mano.py:46-137 ManoBranch, hpregnet.py:75-104) with a gradient:
+// ab_mano_pca_fwd takes PCA coefficients (full pose = [root | hands_mean + pca . comps]) and centres on a joint;
+// ab_mano_pca_bwd recomputes the forward state in LDS (nothing is saved between the two launches) and runs the exact
+// reverse of every stage.  Every reduction (over the 778 vertices, over the 2334 posed coordinates) runs in a fixed order
+// through LDS -- no atomics -- so the gradient is bit-reproducible.  Exact fp32 throughout.
 #include "common.h"
 
 #define NV 778
@@ -15,43 +21,58 @@ __constant__ int c_mano_parents[16] = {-1, 0, 1, 2, 0, 4, 5, 0, 7, 8, 0, 10, 11,
 __constant__ int c_mano_tips[5] = {745, 317, 444, 556, 673};
 __constant__ int c_mano_reorder[21] = {0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20};
 
-__global__ __launch_bounds__(256) void mano_lbs_kernel(const float* __restrict__ pose, const float* __restrict__ betas,
-                                                       const float* __restrict__ v_template,   // [778,3]
-                                                       const float* __restrict__ shapedirs,    // [778,3,10]
-                                                       const float* __restrict__ posedirs,     // [778,3,135]
-                                                       const float* __restrict__ J_regressor,  // [16,778]
-                                                       const float* __restrict__ weights,      // [778,16]
-                                                       const float* __restrict__ hands_mean,   // [45]
-                                                       float* __restrict__ verts, float* __restrict__ joints,
-                                                       float* __restrict__ T_abs) {
-    const int b = blockIdx.x, tid = threadIdx.x;
-    __shared__ float R[NJ][9];
-    __shared__ float pmap[135];
-    __shared__ float beta[10];
-    __shared__ float vs[NV * 3];        // v_shaped, later v_posed
-    __shared__ float J[NJ][3];
-    __shared__ float G[NJ][12];         // 3x4 global transforms
-    __shared__ float G2[NJ][12];        // with rest-joint removed
-    __shared__ float part[256][3];
-    if (tid < 10) beta[tid] = betas[b * 10 + tid];
-    if (tid < NJ) {
-        // manolayer.py:162-172 (_batch_rodrigues through a quaternion, +1e-8 inside the norm) and :135-160 (_quat2mat)
-        float a[3];
-        for (int i = 0; i < 3; ++i) a[i] = pose[b * 48 + tid * 3 + i] + (tid > 0 ? hands_mean[(tid - 1) * 3 + i] : 0.f);
-        float e[3] = {a[0] + 1e-8f, a[1] + 1e-8f, a[2] + 1e-8f};
-        float n = sqrtf((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
-        float h = n * 0.5f, s = sinf(h), w = cosf(h);
-        float x = s * (a[0] / n), y = s * (a[1] / n), z = s * (a[2] / n);
-        float nq = sqrtf(((w * w + x * x) + y * y) + z * z);
-        w /= nq; x /= nq; y /= nq; z /= nq;
-        float w2 = w * w, x2 = x * x, y2 = y * y, z2 = z * z, wx = w * x, wy = w * y, wz = w * z, xy = x * y, xz = x * z, yz = y * z;
-        float* r = R[tid];
-        r[0] = w2 + x2 - y2 - z2; r[1] = 2 * xy - 2 * wz; r[2] = 2 * wy + 2 * xz;
-        r[3] = 2 * wz + 2 * xy; r[4] = w2 - x2 + y2 - z2; r[5] = 2 * yz - 2 * wx;
-        r[6] = 2 * xz - 2 * wy; r[7] = 2 * wx + 2 * yz; r[8] = w2 - x2 - y2 + z2;
+// manolayer.py:162-172 (_batch_rodrigues through a quaternion, +1e-8 inside the norm) and :135-160 (_quat2mat)
+__device__ __forceinline__ void mano_rodrigues(const float a[3], float* r) {
+    float e[3] = {a[0] + 1e-8f, a[1] + 1e-8f, a[2] + 1e-8f};
+    float n = sqrtf((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+    float h = n * 0.5f, s = sinf(h), w = cosf(h);
+    float x = s * (a[0] / n), y = s * (a[1] / n), z = s * (a[2] / n);
+    float nq = sqrtf(((w * w + x * x) + y * y) + z * z);
+    w /= nq; x /= nq; y /= nq; z /= nq;
+    float w2 = w * w, x2 = x * x, y2 = y * y, z2 = z * z, wx = w * x, wy = w * y, wz = w * z, xy = x * y, xz = x * z, yz = y * z;
+    r[0] = w2 + x2 - y2 - z2; r[1] = 2 * xy - 2 * wz; r[2] = 2 * wy + 2 * xz;
+    r[3] = 2 * wz + 2 * xy; r[4] = w2 - x2 + y2 - z2; r[5] = 2 * yz - 2 * wx;
+    r[6] = 2 * xz - 2 * wy; r[7] = 2 * wx + 2 * yz; r[8] = w2 - x2 - y2 + z2;
+}
+
+// reverse of mano_rodrigues: g (dL/dR, 9) -> ga (dL/da, 3), through the normalised quaternion and the +1e-8
+__device__ __forceinline__ void mano_rodrigues_bwd(const float a[3], const float* g, float ga[3]) {
+    float e[3] = {a[0] + 1e-8f, a[1] + 1e-8f, a[2] + 1e-8f};
+    float n = sqrtf((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+    float h = n * 0.5f, s = sinf(h), c = cosf(h);
+    float q0[4] = {c, s * (a[0] / n), s * (a[1] / n), s * (a[2] / n)};
+    float nq = sqrtf(((q0[0] * q0[0] + q0[1] * q0[1]) + q0[2] * q0[2]) + q0[3] * q0[3]);
+    float w = q0[0] / nq, x = q0[1] / nq, y = q0[2] / nq, z = q0[3] / nq;
+    float gq[4];
+    gq[0] = 2.f * (w * (g[0] + g[4] + g[8]) - z * g[1] + y * g[2] + z * g[3] - x * g[5] - y * g[6] + x * g[7]);
+    gq[1] = 2.f * (x * (g[0] - g[4] - g[8]) + y * g[1] + z * g[2] + y * g[3] - w * g[5] + z * g[6] + w * g[7]);
+    gq[2] = 2.f * (y * (-g[0] + g[4] - g[8]) + x * g[1] + w * g[2] + x * g[3] + z * g[5] - w * g[6] + z * g[7]);
+    gq[3] = 2.f * (z * (-g[0] - g[4] + g[8]) - w * g[1] + x * g[2] + w * g[3] + y * g[5] + x * g[6] + y * g[7]);
+    // q = q0 / |q0|
+    float dot = ((w * gq[0] + x * gq[1]) + y * gq[2]) + z * gq[3];
+    float g0[4] = {(gq[0] - w * dot) / nq, (gq[1] - x * dot) / nq, (gq[2] - y * dot) / nq, (gq[3] - z * dot) / nq};
+    // q0 = (cos h, s a / n), h = n / 2, n = |a + 1e-8|
+    float gs = 0.f, gn = 0.f;
+    for (int i = 0; i < 3; ++i) {
+        ga[i] = g0[1 + i] * (s / n);
+        gs += g0[1 + i] * (a[i] / n);
+        gn -= g0[1 + i] * (s * a[i] / (n * n));
     }
-    __syncthreads();
-    if (tid < 135) { int j = tid / 9 + 1, k = tid % 9; pmap[tid] = R[j][k] - ((k == 0 || k == 4 || k == 8) ? 1.f : 0.f); }
+    gn += 0.5f * (gs * c - g0[0] * s);
+    for (int i = 0; i < 3; ++i) ga[i] += gn * (e[i] / n);
+}
+
+// The pose-dependent state of one hand, shared by the three kernels.  In (LDS, visible to all threads): fp[48] the full
+// axis-angle pose, beta[10].  Out (LDS, visible to all threads on return): R, pmap, vs = v_posed, J, G (3x4 global
+// transforms), G2 (G with the rest joint removed).  part: 256 floats of scratch.
+__device__ __forceinline__ void mano_state(int tid, const float* fp, const float* beta, const float* __restrict__ v_template,
+                                           const float* __restrict__ shapedirs, const float* __restrict__ posedirs,
+                                           const float* __restrict__ J_regressor, float (*R)[9], float* pmap, float* vs,
+                                           float (*J)[3], float (*G)[12], float (*G2)[12], float* part) {
+    if (tid < NJ) {
+        float a[3] = {fp[tid * 3], fp[tid * 3 + 1], fp[tid * 3 + 2]};
+        mano_rodrigues(a, R[tid]);
+    }
     // v_shaped = v_template + shapedirs . beta
     for (int i = tid; i < NV * 3; i += 256) {
         float s = v_template[i];
@@ -60,6 +81,7 @@ __global__ __launch_bounds__(256) void mano_lbs_kernel(const float* __restrict__
         vs[i] = s;
     }
     __syncthreads();
+    if (tid < 135) { int j = tid / 9 + 1, k = tid % 9; pmap[tid] = R[j][k] - ((k == 0 || k == 4 || k == 8) ? 1.f : 0.f); }
     // J = J_regressor . v_shaped   (16 x 778 x 3): 48 outputs, each reduced by 5 threads
     {
         const int o = tid / 5, l = tid % 5;      // 240 active threads
@@ -68,10 +90,10 @@ __global__ __launch_bounds__(256) void mano_lbs_kernel(const float* __restrict__
             int j = o / 3, c = o % 3;
             for (int v = l; v < NV; v += 5) s += J_regressor[j * NV + v] * vs[v * 3 + c];
         }
-        part[tid][0] = s;
+        part[tid] = s;
     }
     __syncthreads();
-    if (tid < 48) { float s = 0.f; for (int l = 0; l < 5; ++l) s += part[tid * 5 + l][0]; J[tid / 3][tid % 3] = s; }
+    if (tid < 48) { float s = 0.f; for (int l = 0; l < 5; ++l) s += part[tid * 5 + l]; J[tid / 3][tid % 3] = s; }
     __syncthreads();
     // v_posed = v_shaped + posedirs . pose_map
     for (int i = tid; i < NV * 3; i += 256) {
@@ -110,6 +132,40 @@ __global__ __launch_bounds__(256) void mano_lbs_kernel(const float* __restrict__
             }
     }
     __syncthreads();
+}
+
+// skinning transform of vertex v: T = sum_j w_vj G2_j (3x4)
+__device__ __forceinline__ void mano_skin_T(const float* __restrict__ weights, const float (*G2)[12], int v, float T[12]) {
+    for (int k = 0; k < 12; ++k) T[k] = 0.f;
+    for (int j = 0; j < NJ; ++j) {
+        float w = weights[v * NJ + j];
+        if (w != 0.f) for (int k = 0; k < 12; ++k) T[k] += w * G2[j][k];
+    }
+}
+
+__global__ __launch_bounds__(256) void mano_lbs_kernel(const float* __restrict__ pose, const float* __restrict__ betas,
+                                                       const float* __restrict__ v_template,   // [778,3]
+                                                       const float* __restrict__ shapedirs,    // [778,3,10]
+                                                       const float* __restrict__ posedirs,     // [778,3,135]
+                                                       const float* __restrict__ J_regressor,  // [16,778]
+                                                       const float* __restrict__ weights,      // [778,16]
+                                                       const float* __restrict__ hands_mean,   // [45]
+                                                       float* __restrict__ verts, float* __restrict__ joints,
+                                                       float* __restrict__ T_abs) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    __shared__ float fp[48];
+    __shared__ float R[NJ][9];
+    __shared__ float pmap[135];
+    __shared__ float beta[10];
+    __shared__ float vs[NV * 3];        // v_shaped, later v_posed
+    __shared__ float J[NJ][3];
+    __shared__ float G[NJ][12];         // 3x4 global transforms
+    __shared__ float G2[NJ][12];        // with rest-joint removed
+    __shared__ float part[256];
+    if (tid < 10) beta[tid] = betas[b * 10 + tid];
+    if (tid < 48) fp[tid] = pose[b * 48 + tid] + (tid >= 3 ? hands_mean[tid - 3] : 0.f);
+    __syncthreads();
+    mano_state(tid, fp, beta, v_template, shapedirs, posedirs, J_regressor, R, pmap, vs, J, G, G2, part);
     if (T_abs && tid < NJ * 16) {
         int j = tid / 16, k = tid % 16, r = k / 4, c = k % 4;
         T_abs[((size_t)b * NJ + j) * 16 + k] = r < 3 ? G[j][r * 4 + c] : (c == 3 ? 1.f : 0.f);
@@ -118,11 +174,7 @@ __global__ __launch_bounds__(256) void mano_lbs_kernel(const float* __restrict__
     float* vo = verts + (size_t)b * NV * 3;
     for (int v = tid; v < NV; v += 256) {
         float T[12];
-        for (int k = 0; k < 12; ++k) T[k] = 0.f;
-        for (int j = 0; j < NJ; ++j) {
-            float w = weights[v * NJ + j];
-            if (w != 0.f) for (int k = 0; k < 12; ++k) T[k] += w * G2[j][k];
-        }
+        mano_skin_T(weights, G2, v, T);
         float x = vs[v * 3], y = vs[v * 3 + 1], z = vs[v * 3 + 2];
         for (int r = 0; r < 3; ++r) vo[v * 3 + r] = ((T[r * 4] * x + T[r * 4 + 1] * y) + T[r * 4 + 2] * z) + T[r * 4 + 3];
     }
@@ -142,6 +194,268 @@ extern "C" int ab_mano_lbs(const float* pose, const float* betas, const float* v
     if (B < 1) return AB_ESHAPE;
     mano_lbs_kernel<<<B, 256, 0, as_stream(stream)>>>(pose, betas, v_template, shapedirs, posedirs, J_regressor, weights,
                                                       hands_mean, verts, joints, T_abs);
+    AB_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- PCA pose + gradient
+// full[0:3] = pc[0:3];  full[3+i] = (sum_c pc[3+c] comps[c][i]) + hands_mean[i]      (ManoLayer use_pca, mano.py:96-104)
+__device__ __forceinline__ void mano_full_pose(int tid, const float* __restrict__ pc, const float* __restrict__ comps,
+                                               const float* __restrict__ hands_mean, int ncomps, float* fp) {
+    if (tid < 3) fp[tid] = pc[tid];
+    else if (tid < 48) {
+        const int i = tid - 3;
+        float s = 0.f;
+        for (int c = 0; c < ncomps; ++c) s += pc[3 + c] * comps[c * 45 + i];
+        fp[tid] = s + hands_mean[i];
+    }
+}
+
+__global__ __launch_bounds__(256) void mano_pca_fwd_kernel(const float* __restrict__ pose_coeffs, const float* __restrict__ betas,
+                                                           const float* __restrict__ comps, const float* __restrict__ hands_mean,
+                                                           const float* __restrict__ v_template, const float* __restrict__ shapedirs,
+                                                           const float* __restrict__ posedirs, const float* __restrict__ J_regressor,
+                                                           const float* __restrict__ weights, int ncomps, int center_idx,
+                                                           float* __restrict__ verts, float* __restrict__ joints,
+                                                           float* __restrict__ full_pose) {
+    const int b = blockIdx.x, tid = threadIdx.x, P = 3 + ncomps;
+    __shared__ float fp[48];
+    __shared__ float R[NJ][9];
+    __shared__ float pmap[135];
+    __shared__ float beta[10];
+    __shared__ float vs[NV * 3];
+    __shared__ float vo[NV * 3];        // skinned vertices before centring
+    __shared__ float J[NJ][3];
+    __shared__ float G[NJ][12];
+    __shared__ float G2[NJ][12];
+    __shared__ float part[256];
+    __shared__ float jr[63];
+    if (tid < 10) beta[tid] = betas[b * 10 + tid];
+    mano_full_pose(tid, pose_coeffs + (size_t)b * P, comps, hands_mean, ncomps, fp);
+    __syncthreads();
+    if (full_pose && tid < 48) full_pose[(size_t)b * 48 + tid] = fp[tid];
+    mano_state(tid, fp, beta, v_template, shapedirs, posedirs, J_regressor, R, pmap, vs, J, G, G2, part);
+    for (int v = tid; v < NV; v += 256) {
+        float T[12];
+        mano_skin_T(weights, G2, v, T);
+        float x = vs[v * 3], y = vs[v * 3 + 1], z = vs[v * 3 + 2];
+        for (int r = 0; r < 3; ++r) vo[v * 3 + r] = ((T[r * 4] * x + T[r * 4 + 1] * y) + T[r * 4 + 2] * z) + T[r * 4 + 3];
+    }
+    __syncthreads();
+    if (tid < 63) {
+        int k = tid / 3, c = tid % 3, src = c_mano_reorder[k];
+        jr[tid] = src < 16 ? G[src][c * 4 + 3] : vo[c_mano_tips[src - 16] * 3 + c];
+    }
+    __syncthreads();
+    float* vg = verts + (size_t)b * NV * 3;
+    for (int i = tid; i < NV * 3; i += 256) vg[i] = center_idx >= 0 ? vo[i] - jr[center_idx * 3 + i % 3] : vo[i];
+    if (tid < 63) joints[(size_t)b * 63 + tid] = center_idx >= 0 ? jr[tid] - jr[center_idx * 3 + tid % 3] : jr[tid];
+}
+
+__global__ __launch_bounds__(256) void mano_pca_bwd_kernel(const float* __restrict__ pose_coeffs, const float* __restrict__ betas,
+                                                           const float* __restrict__ comps, const float* __restrict__ hands_mean,
+                                                           const float* __restrict__ v_template, const float* __restrict__ shapedirs,
+                                                           const float* __restrict__ posedirs, const float* __restrict__ J_regressor,
+                                                           const float* __restrict__ weights, int ncomps, int center_idx,
+                                                           const float* __restrict__ g_verts, const float* __restrict__ g_joints,
+                                                           const float* __restrict__ g_full_pose, float* __restrict__ g_pose_coeffs,
+                                                           float* __restrict__ g_betas) {
+    const int b = blockIdx.x, tid = threadIdx.x, P = 3 + ncomps;
+    __shared__ float fp[48];
+    __shared__ float R[NJ][9];
+    __shared__ float pmap[135];
+    __shared__ float beta[10];
+    __shared__ float vs[NV * 3];        // v_posed (recomputed)
+    __shared__ float gv[NV * 3];        // dL/d verts (uncentred, tips added)
+    __shared__ float gvp[NV * 3];       // dL/d v_posed, then dL/d v_shaped
+    __shared__ float J[NJ][3];
+    __shared__ float G[NJ][12];
+    __shared__ float G2[NJ][12];
+    __shared__ float part[256];
+    __shared__ float red[256][10];      // fixed-order partial sums (centring: 3, shape blend: 10)
+    __shared__ float gj[63];
+    __shared__ float gGt[NJ][3];        // dL/d G[:, 3] from the joint outputs
+    __shared__ float gG2[NJ][12];       // dL/d G2, then dL/d G
+    __shared__ float gpmap[135];
+    __shared__ float gR[NJ][9];
+    __shared__ float gJ[NJ][3];
+    __shared__ float gfull[48];
+    const float* pc = pose_coeffs + (size_t)b * P;
+    if (tid < 10) beta[tid] = betas[b * 10 + tid];
+    mano_full_pose(tid, pc, comps, hands_mean, ncomps, fp);
+    __syncthreads();
+    mano_state(tid, fp, beta, v_template, shapedirs, posedirs, J_regressor, R, pmap, vs, J, G, G2, part);
+
+    // ---- centring: verts' = verts - c, joints' = joints - c, c = joints[center_idx]
+    {
+        const float* gvb = g_verts + (size_t)b * NV * 3;
+        float s[3] = {0.f, 0.f, 0.f};
+        for (int v = tid; v < NV; v += 256)
+            for (int c = 0; c < 3; ++c) { float g = gvb[v * 3 + c]; gv[v * 3 + c] = g; s[c] += g; }
+        for (int c = 0; c < 3; ++c) red[tid][c] = s[c];
+        if (tid < 63) gj[tid] = g_joints[(size_t)b * 63 + tid];
+    }
+    __syncthreads();
+    if (center_idx >= 0 && tid < 3) {
+        float s = 0.f;
+        for (int t = 0; t < 256; ++t) s += red[t][tid];
+        for (int k = 0; k < 21; ++k) s += gj[k * 3 + tid];
+        gj[center_idx * 3 + tid] -= s;
+    }
+    __syncthreads();
+    // ---- joint reordering: 16 transform translations + 5 fingertip vertices (a permutation: every target written once)
+    if (tid < 63) {
+        int k = tid / 3, c = tid % 3, src = c_mano_reorder[k];
+        if (src < 16) gGt[src][c] = gj[tid];
+        else gv[c_mano_tips[src - 16] * 3 + c] += gj[tid];
+    }
+    __syncthreads();
+    // ---- skinning: verts_v = T_v [v_posed_v, 1]
+    //   dL/dG2_j = sum_v w_vj g_v (x) [v_posed_v, 1]   (192 outputs, each a fixed-order sum over the vertices)
+    //   dL/dv_posed_v = T_v[:, :3]^T g_v
+    for (int v = tid; v < NV; v += 256) {
+        float T[12];
+        mano_skin_T(weights, G2, v, T);
+        float g0 = gv[v * 3], g1 = gv[v * 3 + 1], g2 = gv[v * 3 + 2];
+        for (int c = 0; c < 3; ++c) gvp[v * 3 + c] = (T[c] * g0 + T[4 + c] * g1) + T[8 + c] * g2;
+    }
+    if (tid < NJ * 12) {
+        const int j = tid / 12, r = (tid % 12) / 4, c = tid % 4;
+        float s = 0.f;
+        for (int v = 0; v < NV; ++v) {
+            float w = weights[v * NJ + j];
+            if (w != 0.f) s += w * gv[v * 3 + r] * (c < 3 ? vs[v * 3 + c] : 1.f);
+        }
+        gG2[j][r * 4 + c] = s;
+    }
+    __syncthreads();
+    // ---- pose blend: dL/dpmap = posedirs^T dL/dv_posed (135 outputs over 2334 rows, four interleaved partial sums)
+    if (tid < 135) {
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        const float* pd = posedirs + tid;
+        int i = 0;
+        for (; i + 4 <= NV * 3; i += 4) {
+            s0 += pd[(size_t)i * 135] * gvp[i];
+            s1 += pd[(size_t)(i + 1) * 135] * gvp[i + 1];
+            s2 += pd[(size_t)(i + 2) * 135] * gvp[i + 2];
+            s3 += pd[(size_t)(i + 3) * 135] * gvp[i + 3];
+        }
+        for (; i < NV * 3; ++i) s0 += pd[(size_t)i * 135] * gvp[i];
+        gpmap[tid] = (s0 + s1) + (s2 + s3);
+    }
+    // ---- rest-joint correction and kinematic chain in reverse (one thread; children have larger indices than parents)
+    if (tid == 255) {
+        for (int j = 0; j < NJ; ++j) {
+            for (int c = 0; c < 3; ++c) gJ[j][c] = 0.f;
+            for (int r = 0; r < 3; ++r) {
+                // G2[:, 3] = G[:, 3] - G[:, :3] J_j
+                const float gt = gG2[j][r * 4 + 3];
+                for (int c = 0; c < 3; ++c) {
+                    gJ[j][c] -= G[j][r * 4 + c] * gt;
+                    gG2[j][r * 4 + c] -= gt * J[j][c];
+                }
+                gG2[j][r * 4 + 3] = gt + gGt[j][r];
+            }
+        }
+        for (int j = NJ - 1; j >= 0; --j) {
+            const int par = c_mano_parents[j];
+            const float* gG = gG2[j];
+            float gL[12];
+            if (par < 0) { for (int k = 0; k < 12; ++k) gL[k] = gG[k]; }
+            else {
+                // G_j = G_par L_j (3x4 affine): dL/dL_j = G_par[:, :3]^T dL/dG_j;  dL/dG_par += dL/dG_j L_j^T (+ the translation)
+                const float* Pm = G[par];
+                float L[12];
+                for (int r = 0; r < 3; ++r) {
+                    for (int c = 0; c < 3; ++c) L[r * 4 + c] = R[j][r * 3 + c];
+                    L[r * 4 + 3] = J[j][r] - J[par][r];
+                }
+                for (int k = 0; k < 3; ++k)
+                    for (int c = 0; c < 4; ++c) gL[k * 4 + c] = (Pm[k] * gG[c] + Pm[4 + k] * gG[4 + c]) + Pm[8 + k] * gG[8 + c];
+                for (int r = 0; r < 3; ++r) {
+                    for (int k = 0; k < 3; ++k)
+                        gG2[par][r * 4 + k] += ((gG[r * 4] * L[k * 4] + gG[r * 4 + 1] * L[k * 4 + 1]) + gG[r * 4 + 2] * L[k * 4 + 2]) +
+                                               gG[r * 4 + 3] * L[k * 4 + 3];
+                    gG2[par][r * 4 + 3] += gG[r * 4 + 3];
+                }
+            }
+            for (int k = 0; k < 3; ++k) {
+                for (int c = 0; c < 3; ++c) gR[j][k * 3 + c] = gL[k * 4 + c];
+                gJ[j][k] += gL[k * 4 + 3];               // t_0 = J_0, t_j = J_j - J_par
+                if (par >= 0) gJ[par][k] -= gL[k * 4 + 3];
+            }
+        }
+    }
+    __syncthreads();
+    // ---- Rodrigues (+ the pose map R_j - I of joints 1..15) -> dL/d full pose
+    if (tid < NJ) {
+        float g[9];
+        for (int k = 0; k < 9; ++k) g[k] = gR[tid][k] + (tid > 0 ? gpmap[(tid - 1) * 9 + k] : 0.f);
+        float a[3] = {fp[tid * 3], fp[tid * 3 + 1], fp[tid * 3 + 2]}, ga[3];
+        mano_rodrigues_bwd(a, g, ga);
+        for (int i = 0; i < 3; ++i) gfull[tid * 3 + i] = ga[i] + (g_full_pose ? g_full_pose[(size_t)b * 48 + tid * 3 + i] : 0.f);
+    }
+    // ---- joint regression: dL/dv_shaped = dL/dv_posed + J_regressor^T dL/dJ
+    for (int i = tid; i < NV * 3; i += 256) {
+        const int v = i / 3, c = i % 3;
+        float s = 0.f;
+        for (int j = 0; j < NJ; ++j) s += J_regressor[j * NV + v] * gJ[j][c];
+        gvp[i] += s;
+    }
+    __syncthreads();
+    // ---- shape blend: dL/dbeta = shapedirs^T dL/dv_shaped;  PCA: dL/dpc[3+c] = sum_i dL/dfull[3+i] comps[c][i]
+    {
+        float s[10];
+        for (int l = 0; l < 10; ++l) s[l] = 0.f;
+        for (int i = tid; i < NV * 3; i += 256) {
+            const float* sd = shapedirs + (size_t)i * 10;
+            const float g = gvp[i];
+            for (int l = 0; l < 10; ++l) s[l] += sd[l] * g;
+        }
+        for (int l = 0; l < 10; ++l) red[tid][l] = s[l];
+    }
+    if (tid < P) {
+        float s;
+        if (tid < 3) s = gfull[tid];
+        else {
+            s = 0.f;
+            for (int i = 0; i < 45; ++i) s += gfull[3 + i] * comps[(tid - 3) * 45 + i];
+        }
+        g_pose_coeffs[(size_t)b * P + tid] = s;
+    }
+    __syncthreads();
+    if (tid < 10) {
+        float s = 0.f;
+        for (int t = 0; t < 256; ++t) s += red[t][tid];
+        g_betas[(size_t)b * 10 + tid] = s;
+    }
+}
+
+extern "C" int ab_mano_pca_fwd(const float* pose_coeffs, const float* betas, const float* comps, const float* hands_mean,
+                               const float* v_template, const float* shapedirs, const float* posedirs, const float* J_regressor,
+                               const float* weights, int ncomps, int center_idx, int B, float* verts, float* joints,
+                               float* full_pose, void* stream) {
+    if (!pose_coeffs || !betas || !comps || !hands_mean || !v_template || !shapedirs || !posedirs || !J_regressor || !weights ||
+        !verts || !joints)
+        return AB_EINVAL;
+    if (B < 1 || ncomps < 1 || ncomps > 45 || center_idx < -1 || center_idx > 20) return AB_ESHAPE;
+    mano_pca_fwd_kernel<<<B, 256, 0, as_stream(stream)>>>(pose_coeffs, betas, comps, hands_mean, v_template, shapedirs, posedirs,
+                                                          J_regressor, weights, ncomps, center_idx, verts, joints, full_pose);
+    AB_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ab_mano_pca_bwd(const float* pose_coeffs, const float* betas, const float* comps, const float* hands_mean,
+                               const float* v_template, const float* shapedirs, const float* posedirs, const float* J_regressor,
+                               const float* weights, int ncomps, int center_idx, int B, const float* g_verts, const float* g_joints,
+                               const float* g_full_pose, float* g_pose_coeffs, float* g_betas, void* stream) {
+    if (!pose_coeffs || !betas || !comps || !hands_mean || !v_template || !shapedirs || !posedirs || !J_regressor || !weights ||
+        !g_verts || !g_joints || !g_pose_coeffs || !g_betas)
+        return AB_EINVAL;
+    if (B < 1 || ncomps < 1 || ncomps > 45 || center_idx < -1 || center_idx > 20) return AB_ESHAPE;
+    mano_pca_bwd_kernel<<<B, 256, 0, as_stream(stream)>>>(pose_coeffs, betas, comps, hands_mean, v_template, shapedirs, posedirs,
+                                                          J_regressor, weights, ncomps, center_idx, g_verts, g_joints, g_full_pose,
+                                                          g_pose_coeffs, g_betas);
     AB_LAUNCH_CHECK();
     return 0;
 }

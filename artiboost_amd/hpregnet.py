@@ -5,8 +5,8 @@
   ManoBranch     anakin/models/mano.py:46-137       MLP -> PCA pose + shape -> MANO layer
   ResNet18       anakin/models/resnet.py:142-236    (the torchvision-keyed backbone, as a plain torch module)
 
-This is NOT the hot path: it is the small forward-only model the reference's own CPU configuration runs, kept as plain torch
-modules so that it runs wherever torch does (CPU here, as configs[0] says).  The MANO forward is the torch restatement of the
+These plain torch modules are the model the reference's own CPU configuration runs (CPU here, as configs[0] says); with cfg["DEVICE"]
+naming a HIP device, HOPRegNet builds regnet.HOPRegNetHIP instead -- the same model trained and evaluated on the HIP kernels.  The MANO forward is the torch restatement of the
 same arithmetic the HIP kernel `ab_mano_lbs` and `oracle/pose_oracle.mano_lbs` implement (pinned to the reference's in-tree
 MANO layer by tests/golden/mano.npz); MANO_RIGHT.pkl is licensed and absent, so the seeded stand-in hand model is used unless
 `MANO_ASSETS_ROOT/models/MANO_RIGHT.pkl` exists."""
@@ -243,6 +243,15 @@ class HOPRegNet(nn.Module):
         def forward(self, inp):
             return self.final_layer(self.decoder(inp))
 
+    def __new__(cls, *args, **cfg):
+        """cfg["DEVICE"] naming a HIP device (train_artiboost.py passes DEVICE to every arch; the GPU eval config sets ARCH.DEVICE) builds
+        the model on the HIP kernels (regnet.HOPRegNetHIP); without DEVICE, or with "cpu", this torch module."""
+        dev = cfg.get("DEVICE", cfg.get("device"))
+        if cls is HOPRegNet and dev is not None and torch.device(dev).type in ("cuda", "hip"):
+            from .regnet import HOPRegNetHIP
+            return HOPRegNetHIP(*args, **cfg)
+        return super().__new__(cls)
+
     @enable_lower_param
     def __init__(self, **cfg):
         super().__init__()
@@ -276,31 +285,40 @@ class HOPRegNet(nn.Module):
         return out
 
     def recover_mano(self, feature, samples):
-        from .models import ortho6d_to_rotmat  # noqa: F401  (same helper module; kept local to avoid an import cycle)
-        res = self.mano_branch(feature)
-        cam_intr, root = samples[Queries.CAM_INTR].to(feature.device), samples[Queries.ROOT_JOINT].to(feature.device)
-        res["joints_3d_abs"] = res["joints_3d"] + root.unsqueeze(1)
-        res["hand_verts_3d_abs"] = res["hand_verts_3d"] + root.unsqueeze(1)
-        res["joints_2d"] = batch_persp_proj2d(res["joints_3d_abs"], cam_intr)
-        res["hand_verts_2d"] = batch_persp_proj2d(res["hand_verts_3d_abs"], cam_intr)
-        res["root_joint"] = root
-        return res
+        return mano_outputs(self.mano_branch(feature), samples, feature.device)
 
     def recover_object(self, feature, samples):
-        from .models import ortho6d_to_rotmat
-        t = self.obj_transfhead(feature)
-        rotmat = ortho6d_to_rotmat(t[:, 3:]).view(t.shape[0], 3, 3)
-        root, cam_intr = samples[Queries.ROOT_JOINT].to(feature.device), samples[Queries.CAM_INTR].to(feature.device)
-        center = root + t[:, :3]
-        corners = rotmat.bmm(samples[Queries.CORNERS_CAN].to(feature.device).float().transpose(1, 2)).transpose(1, 2) + center.unsqueeze(1)
-        return {"obj_center": center, "corners_3d_abs": corners, "obj_pred_tsl": t[:, :3], "obj_pred_rot": rotmat,
-                "corners_2d": batch_persp_proj2d(corners, cam_intr), "box_rot_rotmat": rotmat, "boxroot_3d_abs": center}
+        return object_outputs(self.obj_transfhead(feature), samples, feature.device)
 
     def forward(self, samples):
         image = samples["image"]
         dev = next(self.parameters()).device
         feats = self.base_net(image=image.to(dev))
-        mano = self.recover_mano(feats["res_layer4_mean"], samples)
-        obj = self.recover_object(feats["res_layer4_mean"], samples)
-        obj["corners_3d"] = obj["corners_3d_abs"] - mano["root_joint"].unsqueeze(1)
-        return {**mano, **obj}
+        return combine_outputs(self.recover_mano(feats["res_layer4_mean"], samples), self.recover_object(feats["res_layer4_mean"], samples))
+
+
+# The camera-frame outputs of HOPRegNet (hpregnet.py:112-147) from the MANO branch's dict and the TransHead's 9 values: small torch ops,
+# shared by the torch module above and the HIP model (regnet.py), so both return the same 18 keys.
+def mano_outputs(res, samples, device):
+    cam_intr, root = samples[Queries.CAM_INTR].to(device), samples[Queries.ROOT_JOINT].to(device)
+    res["joints_3d_abs"] = res["joints_3d"] + root.unsqueeze(1)
+    res["hand_verts_3d_abs"] = res["hand_verts_3d"] + root.unsqueeze(1)
+    res["joints_2d"] = batch_persp_proj2d(res["joints_3d_abs"], cam_intr)
+    res["hand_verts_2d"] = batch_persp_proj2d(res["hand_verts_3d_abs"], cam_intr)
+    res["root_joint"] = root
+    return res
+
+
+def object_outputs(t, samples, device):
+    from .models import ortho6d_to_rotmat      # (kept local to avoid an import cycle)
+    rotmat = ortho6d_to_rotmat(t[:, 3:]).view(t.shape[0], 3, 3)
+    root, cam_intr = samples[Queries.ROOT_JOINT].to(device), samples[Queries.CAM_INTR].to(device)
+    center = root + t[:, :3]
+    corners = rotmat.bmm(samples[Queries.CORNERS_CAN].to(device).float().transpose(1, 2)).transpose(1, 2) + center.unsqueeze(1)
+    return {"obj_center": center, "corners_3d_abs": corners, "obj_pred_tsl": t[:, :3], "obj_pred_rot": rotmat,
+            "corners_2d": batch_persp_proj2d(corners, cam_intr), "box_rot_rotmat": rotmat, "boxroot_3d_abs": center}
+
+
+def combine_outputs(mano, obj):
+    obj["corners_3d"] = obj["corners_3d_abs"] - mano["root_joint"].unsqueeze(1)
+    return {**mano, **obj}

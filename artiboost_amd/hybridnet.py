@@ -51,12 +51,15 @@ class ParamStore:
     """Flat parameter / gradient / running-stat storage with reference <-> kernel layout conversion."""
 
     def __init__(self, nclasses=22, depth=28, device="cuda", layers=(3, 4, 6, 3), head_prefix="hybrid_head", box_head=True,
-                 block="basic", box_dims=(512, 256, 128)):
+                 block="basic", box_dims=(512, 256, 128), reg_heads=None):
         """layers: BasicBlock counts per stage ((3,4,6,3) = ResNet-34, (2,2,2,2) = ResNet-18: resnet.py:236-248); head_prefix: the
         IntegralDeconvHead's attribute name in the reference module ("hybrid_head" in HybridBaseline, "pose_head" in SimpleBaseline:
         hybridbaseline.py:31, simplebaseline.py:207); box_head: MLP_O present (HybridBaseline only).
         The final layer is laid out for `nclasses_pad` classes (even, so that its channel count is a multiple of 64 for the weight-gradient
-        kernels): a padding class has zero weights, zero bias and receives zero gradient."""
+        kernels): a padding class has zero weights, zero bias and receives zero gradient.
+        reg_heads=ncomps: the trunk-only layout of HOPRegNet (hpregnet.py:18-150) -- the backbone under the reference's `base_net.`
+        names, no IntegralDeconvHead and no MLP_O, and the regression heads of ManoBranch (mano.py:46-137: 512 -> 512 -> 512, pose
+        512 -> 3 + ncomps, shape 512 -> 10) and HOPRegNet.TransHead (512 -> 256 -> 9) as fp32 linear layers in the same flat buffer."""
         self.nclasses, self.depth = nclasses, depth
         self.nclasses_pad = nclasses + (nclasses & 1)
         self.layers, self.hp, self.box_head = tuple(layers), head_prefix, bool(box_head)
@@ -64,6 +67,13 @@ class ParamStore:
         self.block, self.expansion = block, (4 if block == "bottleneck" else 1)
         self.feat_ch = 512 * self.expansion                # res_layer4 channels = the head's INPUT_CHANNEL
         self.box_dims = tuple(box_dims)                    # MLP_O LAYERS_N (mlp.py:11-25)
+        self.reg_ncomps = None if reg_heads is None else int(reg_heads)
+        self.trunk_only = self.reg_ncomps is not None
+        if self.trunk_only:
+            self.box_head = False
+        # reference-side name of the trunk: "backbone" (HybridBaseline / SimpleBaseline) or "base_net" (HOPRegNet); entries are always
+        # named `backbone.*` inside (the executor addresses them so), the prefix is swapped at the state-dict boundary only
+        self.trunk_ref = "base_net" if self.trunk_only else "backbone"
         self.entries = OrderedDict()
         self.buffers = OrderedDict()   # running stats: name -> (offset, C)
         self._build_table()
@@ -125,6 +135,9 @@ class ParamStore:
         # backbone.fc exists in the reference state_dict (resnet.py:164) but never receives a gradient
         self._add("backbone.fc.weight", "frozen", (1000, self.feat_ch), (1000, self.feat_ch))
         self._add("backbone.fc.bias", "frozen", (1000,), (1000,))
+        if self.trunk_only:
+            self._build_reg_heads()
+            return
         self._add(hp + ".deconv_layers.0.weight", "deconv", (self.feat_ch, 256, 4, 4), (self.feat_ch, 4, 4, 256))
         self._add_bn(hp + ".deconv_layers.1", 256)
         self._add(hp + ".deconv_layers.3.weight", "deconv", (256, 256, 4, 4), (256, 4, 4, 256))
@@ -140,6 +153,29 @@ class ParamStore:
         self._add("box_head.layers.2.bias", "vec", (d2,), (d2,))
         self._add("box_head.layers.4.weight", "linear_pad", (6, d2), (BOX_OUT_PAD, 1, 1, d2))
         self._add("box_head.layers.4.bias", "vec_pad", (6,), (BOX_OUT_PAD,))
+
+    # output widths of the regression heads are padded with zero rows to a multiple of REG_PAD: linear.hip reduces the data
+    # gradient over them in float4 steps (multiples of 4), and the batched [out][in] -> [in][out] transpose takes multiples of 8
+    REG_PAD = 8
+
+    def _build_reg_heads(self):
+        F, P = self.feat_ch, 3 + self.reg_ncomps
+        for name, o, i in (("mano_branch.base_layer.0", 512, F), ("mano_branch.base_layer.2", 512, 512), ("mano_branch.pose_reg", P, 512),
+                           ("mano_branch.shape_reg.0", 10, 512), ("obj_transfhead.decoder.0", F // 2, F), ("obj_transfhead.final_layer", 9, F // 2)):
+            op = _round_up(o, self.REG_PAD)
+            self._add(name + ".weight", "linear" if op == o else "linear_pad", (o, i), (op, 1, 1, i))
+            self._add(name + ".bias", "vec" if op == o else "vec_pad", (o,), (op,))
+
+    def ref_name(self, name):
+        """internal entry / buffer name -> the reference's key"""
+        if self.trunk_ref != "backbone" and name.startswith("backbone."):
+            return self.trunk_ref + name[len("backbone"):]
+        return name
+
+    def internal_name(self, key):
+        if self.trunk_ref != "backbone" and key.startswith(self.trunk_ref + "."):
+            return "backbone" + key[len(self.trunk_ref):]
+        return key
 
     # ------------------------------------------------------------------ views
     def view(self, name, buf=None):
@@ -214,7 +250,7 @@ class ParamStore:
             for pre in ("module.", "_model_list.0."):
                 if k.startswith(pre):
                     k = k[len(pre):]
-            clean[k] = v
+            clean[self.internal_name(k)] = v
         missing = []
         for name, e in self.entries.items():
             if name not in clean:
@@ -241,14 +277,15 @@ class ParamStore:
         """Reference-layout tensors under the reference's keys, in the order of its module tree (a BatchNorm contributes weight,
         bias, running_mean, running_var, num_batches_tracked): what the reference's load_arch(strict=True) expects."""
         out = OrderedDict()
+        rn = self.ref_name
         for name, e in self.entries.items():
-            out[name] = self._to_reference(e, self.view(name, self.grad if grads else None))
+            out[rn(name)] = self._to_reference(e, self.view(name, self.grad if grads else None))
             pre = name[:-len(".bias")] if name.endswith(".bias") else None
             if not grads and pre is not None and pre + ".running_mean" in self.buffers:
-                out[pre + ".running_mean"] = self.stat(pre + ".running_mean").clone()
-                out[pre + ".running_var"] = self.stat(pre + ".running_var").clone()
+                out[rn(pre + ".running_mean")] = self.stat(pre + ".running_mean").clone()
+                out[rn(pre + ".running_var")] = self.stat(pre + ".running_var").clone()
                 if not (getattr(self, "frozen_bn", False) and pre.startswith("backbone.")):     # FrozenBatchNorm2d keeps no counter (resnet.py:45-55)
-                    out[pre + ".num_batches_tracked"] = torch.tensor(int(self.num_batches_tracked), dtype=torch.int64)
+                    out[rn(pre + ".num_batches_tracked")] = torch.tensor(int(self.num_batches_tracked), dtype=torch.int64)
         return out
 
     def init_reference_like(self, seed=1):
@@ -270,7 +307,7 @@ class ParamStore:
                 sd[name] = (torch.rand(shp, generator=g) * 2 - 1) * bound
             elif name.endswith(".weight") and e.kind == "vec":
                 sd[name] = torch.ones(shp)
-            elif "box_head" in name or "fc.bias" in name:
+            elif "box_head" in name or "fc.bias" in name or name.startswith(("mano_branch.", "obj_transfhead.")):
                 fan_in = self.entries[name.replace(".bias", ".weight")].ref_shape[1]
                 sd[name] = (torch.rand(shp, generator=g) * 2 - 1) / math.sqrt(fan_in)
             else:
@@ -345,9 +382,11 @@ class HybridNet:
                 pairs.append((p.view(name).reshape(O, kh * kw, I), dst))
             self._tr_pairs = pairs                                   # the flat buffer and the copies are persistent
             self._tr_plan = K.transpose_plan(pairs) or False
-            # fp32 [in][out] copies of the box-head weights (its data gradients run as NT products too)
+            # fp32 [in][out] copies of the box-head (trunk-only layout: regression-head) weights: their data gradients run as NT products too
             self.box_t, bpairs = {}, []
-            for name in (("box_head.layers.0.weight", "box_head.layers.2.weight", "box_head.layers.4.weight") if p.box_head else ()):
+            lin = (("box_head.layers.0.weight", "box_head.layers.2.weight", "box_head.layers.4.weight") if p.box_head else
+                   tuple(n for n, e in p.entries.items() if e.kind in ("linear", "linear_pad")) if p.trunk_only else ())
+            for name in lin:
                 O, _, _, I = p.entries[name].kshape
                 dst = self.box_t[name] = torch.empty((I, O), dtype=torch.float32, device=p.device)
                 bpairs.append((p.view(name).reshape(O, 1, I), dst.view(I, 1, O)))
@@ -571,6 +610,11 @@ class HybridNet:
                 inpl = planes
         feat = x                                         # res_layer4 [N,h,w,512]
         fmean = K.avgpool_fwd(feat)                      # res_layer4_mean [N,512] f32 (resnet.py:219)
+        if p.trunk_only:                                 # HOPRegNet: the heads take res_layer4_mean (hpregnet.py:112-147)
+            S.update(feat=feat)
+            self.saved = S if tr else None
+            self.last = dict(feat=feat, fmean=fmean)
+            return fmean
         h4, w4 = feat.shape[-3], feat.shape[-2]
         # ---- IntegralDeconvHead: ConvT == data-gradient of the mirrored stride-2 conv
         # transposed convs: the data-gradient kernel of the mirrored conv, BatchNorm partials from its epilogue
@@ -830,8 +874,9 @@ class HybridNet:
         o3 = self.p.entries["backbone.layer3.0.conv1.weight"].offset
         return [(o4, self.p.total), (o3, o4), (0, o3)]
 
-    def backward(self, dlogits=None, g_box6d=None, stage=None):
+    def backward(self, dlogits=None, g_box6d=None, stage=None, g_mean=None):
         """dlogits: gradient wrt the logits [N,h,w,22*32] (compute dtype); g_box6d [N,6] f32.
+        Trunk-only layout (ParamStore(reg_heads=...)): g_mean [N,512] f32, the gradient wrt res_layer4_mean (stage must be None).
         Fills self.p.grad (overwrites).  Returns nothing (no gradient to the image).
         stage=None runs the whole backward; stage=0 runs box head, heat-map head and layer4 and parks the activation
         gradient, stage=1 continues with layer3, stage=2 with layer2 .. stem (see grad_stage_ranges)."""
@@ -840,6 +885,14 @@ class HybridNet:
             raise RuntimeError("backward() without a training-mode forward()")
         N = S["N"]
         gv = p.gview
+        if p.trunk_only:
+            if stage is not None or g_mean is None:
+                raise ValueError("trunk-only backward: backward(g_mean=[N, 512]) in one piece")
+            feat = S["feat"]
+            # the layer-4 gradient starts as the average pool's backward (it writes every element: dout = g_mean / HW)
+            dout = K.avgpool_bwd(g_mean.contiguous().float(), torch.empty(feat.shape, dtype=feat.dtype, device=feat.device), accumulate=False)
+            self._backward_trunk(S, dout, list(reversed(S["blocks"])))
+            return
         if stage == 1:
             dout, blocks, part = S.pop("_dout"), S.pop("_blocks_left"), S.pop("_dout_part")
             n3 = sum(1 for r in blocks if r["pre"].startswith("backbone.layer3."))

@@ -841,3 +841,36 @@ def pose_assemble(kp3d, box6d, root_joint, cam_intr, corners_can, center_idx, in
                                      L.ptr(o["corners_3d_abs"]), L.ptr(o["box_rot_rotmat"]), L.ptr(o["uvd2d"]), L.ptr(o["joints_3d"]),
                                      L.ptr(o["corners_3d"]), L.ptr(o["boxroot_3d_abs"]), L.stream()), "ab_pose_assemble")
     return o
+
+
+def _mano_tables(t):
+    """t: dict of the MANO tables on the device (fp32, contiguous) -> the pointer arguments shared by the ab_mano_pca_* launches."""
+    return (L.ptr(t["comps"]), L.ptr(t["hands_mean"]), L.ptr(t["v_template"]), L.ptr(t["shapedirs"]), L.ptr(t["posedirs"]),
+            L.ptr(t["J_regressor"]), L.ptr(t["weights"]))
+
+
+def mano_pca_fwd(pose_coeffs, betas, tables, center_idx=None):
+    """MANO from PCA coefficients (ab_mano_pca_fwd): pose_coeffs [B,3+ncomps], betas [B,10] fp32; tables: comps [ncomps,45],
+    hands_mean [45], v_template, shapedirs, posedirs, J_regressor, weights -> verts [B,778,3], joints [B,21,3] (minus joint
+    center_idx unless None), full_pose [B,48]."""
+    B, P = pose_coeffs.shape
+    dev = pose_coeffs.device
+    verts = torch.empty((B, 778, 3), dtype=torch.float32, device=dev)
+    joints = torch.empty((B, 21, 3), dtype=torch.float32, device=dev)
+    full = torch.empty((B, 48), dtype=torch.float32, device=dev)
+    L.check(L.lib().ab_mano_pca_fwd(L.ptr(pose_coeffs), L.ptr(betas), *_mano_tables(tables), L.i(P - 3),
+                                    L.i(-1 if center_idx is None else center_idx), L.i(B), L.ptr(verts), L.ptr(joints), L.ptr(full),
+                                    L.stream()), "ab_mano_pca_fwd")
+    return verts, joints, full
+
+
+def mano_pca_bwd(pose_coeffs, betas, tables, g_verts, g_joints, g_full_pose=None, center_idx=None):
+    """Reverse of mano_pca_fwd (ab_mano_pca_bwd): -> g_pose_coeffs [B,3+ncomps], g_betas [B,10] (fixed-order reductions: bit-reproducible)."""
+    B, P = pose_coeffs.shape
+    dev = pose_coeffs.device
+    g_pc = torch.empty((B, P), dtype=torch.float32, device=dev)
+    g_b = torch.empty((B, 10), dtype=torch.float32, device=dev)
+    L.check(L.lib().ab_mano_pca_bwd(L.ptr(pose_coeffs), L.ptr(betas), *_mano_tables(tables), L.i(P - 3),
+                                    L.i(-1 if center_idx is None else center_idx), L.i(B), L.ptr(g_verts), L.ptr(g_joints),
+                                    L.ptr(g_full_pose), L.ptr(g_pc), L.ptr(g_b), L.stream()), "ab_mano_pca_bwd")
+    return g_pc, g_b

@@ -39,6 +39,11 @@ def _models(model):
     return model.module.model_list if hasattr(model, "module") else model.model_list
 
 
+def _ckpt_name(m):
+    """<ModelType>.pth.tar: the class name, or the one a model shares with another implementation (HOPRegNet on the HIP kernels)."""
+    return getattr(m, "CHECKPOINT_NAME", type(m).__name__)
+
+
 class Recorder:
     def __init__(self, exp_id, cfg, root_path="./exp", rank=None, time_f=None, eval_only=False):
         self.timestamp = time.strftime("%Y_%m%d_%H%M_%S", time.localtime(time_f if time_f else time.time()))
@@ -59,7 +64,7 @@ class Recorder:
         fold = os.path.join(root, "checkpoint")
         os.makedirs(fold, exist_ok=True)
         for m in _models(model):
-            torch.save(m.state_dict(), os.path.join(fold, f"{type(m).__name__}.pth.tar"))
+            torch.save(m.state_dict(), os.path.join(fold, f"{_ckpt_name(m)}.pth.tar"))
         cuda = torch.cuda.is_available()
         rs = RandomState(torch_rng_state=torch.get_rng_state(),
                          torch_cuda_rng_state=torch.cuda.get_rng_state() if cuda else None,
@@ -89,7 +94,7 @@ class Recorder:
             if torch.cuda.is_available() and rs.torch_cuda_rng_state is not None:
                 torch.cuda.set_rng_state(rs.torch_cuda_rng_state)
         for m in _models(model):
-            sd = torch.load(os.path.join(fold, f"{type(m).__name__}.pth.tar"), map_location="cpu", weights_only=False)
+            sd = torch.load(os.path.join(fold, f"{_ckpt_name(m)}.pth.tar"), map_location="cpu", weights_only=False)
             if sd and next(iter(sd)).startswith("module."):
                 sd = {k.split(".", 1)[1]: v for k, v in sd.items()}
             m.load_state_dict(sd)

@@ -109,7 +109,8 @@ class TrainStep:
             self.rstatic["image_nhwc4_padded"] = torch.zeros_like(self.static["image_nhwc4_padded"])
             self.render_stream = torch.cuda.Stream(device=self.dev)
         self.fused = None
-        self.model_key = type(self.hb).__name__                      # the key of this model's outputs in Arch's result dict
+        # the key of this model's outputs in Arch's result dict: its config TYPE (the class name can differ: HOPRegNet on the HIP kernels)
+        self.model_key = next((t for t, v in getattr(arch_model, "models", {}).items() if v["id"] == 0), type(self.hb).__name__)
         if not getattr(self.hb, "HAS_BOX_HEAD", True):               # SimpleBaseline: the fused pose/loss kernel is HybridBaseline's assembly
             fused_criterion = False
             self.split = False

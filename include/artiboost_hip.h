@@ -533,6 +533,25 @@ int ab_mano_lbs(const float* pose, const float* betas, const float* v_template, 
                 const float* posedirs, const float* J_regressor, const float* weights, const float* hands_mean,
                 int B, float* verts, float* joints, float* T_abs, void* stream);
 
+/* ---- MANO from PCA coefficients, forward and backward (the regression model's hand layer) ---------------------------
+ * anakin/models/mano.py:46-137 (ManoBranch: ManoLayer(use_pca=True, ncomps, center_idx, flat_hand_mean=False)) and
+ * anakin/models/hpregnet.py:75-104 (its call on the pose / shape regressions).  pose_coeffs [B,3+ncomps] (root axis-angle +
+ * PCA coefficients), betas [B,10], comps [ncomps,45] (the first ncomps rows of hands_components), hands_mean [45], and the
+ * tables of ab_mano_lbs.  full = [root | hands_mean + pca . comps] -> the maths of ab_mano_lbs (same Rodrigues, chain and
+ * skinning code) -> verts [B,778,3], joints [B,21,3], both minus joint center_idx (-1: no centring); full_pose [B,48]
+ * (optional).  1 <= ncomps <= 45.
+ * ab_mano_pca_bwd: the exact reverse, from g_verts [B,778,3], g_joints [B,21,3] and g_full_pose [B,48] (optional) to
+ * g_pose_coeffs [B,3+ncomps] and g_betas [B,10] (overwritten).  It recomputes the forward state itself; every reduction
+ * runs in a fixed order (no atomics): the gradient is bit-reproducible.                                              */
+int ab_mano_pca_fwd(const float* pose_coeffs, const float* betas, const float* comps, const float* hands_mean,
+                    const float* v_template, const float* shapedirs, const float* posedirs, const float* J_regressor,
+                    const float* weights, int ncomps, int center_idx, int B, float* verts, float* joints, float* full_pose,
+                    void* stream);
+int ab_mano_pca_bwd(const float* pose_coeffs, const float* betas, const float* comps, const float* hands_mean,
+                    const float* v_template, const float* shapedirs, const float* posedirs, const float* J_regressor,
+                    const float* weights, int ncomps, int center_idx, int B, const float* g_verts, const float* g_joints,
+                    const float* g_full_pose, float* g_pose_coeffs, float* g_betas, void* stream);
+
 /* ---- Argument contracts of the dispatcher ops (torch.ops.artiboost_hip.*, libartiboost_torch.so) ------------------------------------------
  * The C entry points above take raw pointers and trust their caller.  Their PyTorch-dispatcher form (ops that "validate
  * with TORCH_CHECK") is generated from this header by artiboost_amd/gen_torch_ops.py and checks, before the C call, for EVERY op:
@@ -595,6 +614,8 @@ int ab_mano_lbs(const float* pose, const float* betas, const float* v_template, 
  * @check ab_pose_loss_sym: strided: box6d g_box6d; kp3d g_kp3d >= B*22*3; root_joint >= B*3; cam_intr >= B*9
  * @check ab_linear_fused: strided: residual y; x >= M*K; w >= N*K; bias scale shift >= N
  * @check ab_mano_lbs: pose >= B*48; betas >= B*10; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; hands_mean >= 45; verts >= B*778*3; joints >= B*21*3; T_abs >= B*16*16
+ * @check ab_mano_pca_fwd: pose_coeffs >= B*(3+ncomps); betas >= B*10; comps >= ncomps*45; hands_mean >= 45; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; verts >= B*778*3; joints >= B*21*3; full_pose >= B*48
+ * @check ab_mano_pca_bwd: pose_coeffs g_pose_coeffs >= B*(3+ncomps); betas g_betas >= B*10; comps >= ncomps*45; hands_mean >= 45; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; g_verts >= B*778*3; g_joints >= B*21*3; g_full_pose >= B*48
  */
 
 #ifdef __cplusplus

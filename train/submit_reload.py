@@ -85,7 +85,7 @@ def main():
     model = Arch(cfg, model_list=builder.build_arch_model_list(cfg["ARCH"], preset_cfg=cfg["DATA_PRESET"]))
     if arg.resume:        # <exp>/checkpoints/checkpoint/<ModelType>.pth.tar (utils/io_utils.py:46-70)
         for m in model.model_list:
-            path = os.path.join(arg.resume, "checkpoints", "checkpoint", f"{type(m).__name__}.pth.tar")
+            path = os.path.join(arg.resume, "checkpoints", "checkpoint", f"{getattr(m, 'CHECKPOINT_NAME', type(m).__name__)}.pth.tar")
             m.load_state_dict(torch.load(path, map_location="cpu"))
     criterion = Criterion(cfg, loss_list=builder.build_criterion_loss_list(cfg.get("CRITERION", []), cfg["DATA_PRESET"], LAMBDAS=cfg.get("LAMBDAS", [])))
     evaluator = Evaluator(cfg, metrics_list=builder.build_evaluator_metric_list(cfg["EVALUATOR"], cfg["DATA_PRESET"], arg=arg))

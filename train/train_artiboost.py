@@ -259,8 +259,8 @@ def main():
                     if rec is not None:
                         rec.collect()
                     else:
-                        evaluator.feed_all(ts.predictions(), ts.static, losses)
-                        summarizer.summarize_losses(ts.fused.losses_dict() if ts.fused is not None else losses)
+                        evaluator.feed_all(ts.predictions(), ts.static, ts.out[2])       # (the autograd criterion's loss dict)
+                        summarizer.summarize_losses(ts.out[2])
                 if rec is not None:
                     rec.flush(evaluator, summarizer=summarizer)
                 torch.cuda.synchronize()
@@ -292,8 +292,8 @@ def main():
                 if rec is not None:
                     rec.collect()
                 else:
-                    evaluator.feed_all(ts.predictions(), ts.static, losses)
-                    summarizer.summarize_losses(ts.fused.losses_dict() if ts.fused is not None else losses)
+                    evaluator.feed_all(ts.predictions(), ts.static, ts.out[2])           # (the autograd criterion's loss dict)
+                    summarizer.summarize_losses(ts.out[2])
             if rec is not None:
                 rec.flush(evaluator, summarizer=summarizer)      # per-step loss scalars (epoch_pass: summarizer.summarize_losses) from the records
             torch.cuda.synchronize()
