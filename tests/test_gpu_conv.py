@@ -421,3 +421,86 @@ def test_transposed_conv_forward_with_fused_bn_partials(shape):
     yy = ref.double().reshape(-1, Co)
     np.testing.assert_allclose(have[:, 0].numpy(), want[:, 0].numpy(), rtol=2e-3, atol=2e-3 * float(yy.abs().sum(0).max()))
     np.testing.assert_allclose(have[:, 1].numpy(), want[:, 1].numpy(), rtol=2e-2)
+
+
+# ------------------------------------------------------------------ the kernels of HOPRegNet's heads and pooling, vs float64
+U32 = 2.0 ** -24        # fp32 unit roundoff
+
+
+@pytest.mark.parametrize("dtype", DT)
+@pytest.mark.parametrize("accumulate", [False, True])
+@pytest.mark.parametrize("shape", [(1, 7, 7, 512), (8, 4, 4, 512), (3, 5, 7, 8), (64, 8, 8, 512), (2, 1, 1, 16)])
+def test_avgpool_bwd_against_float64(shape, accumulate, dtype):
+    """dx[n,h,w,c] (+)= g[n,c] / HW.  accumulate=False starts from a NaN-filled buffer: every element must be written.  Bound: the
+    fp32 quotient (and sum) are correctly rounded, then the store rounds to the buffer's type (2^-8 relative for bf16)."""
+    from artiboost_amd import kernels as K
+    N, H, W, C = shape
+    gen = torch.Generator().manual_seed(N * 1000 + H * W + C)
+    g = torch.randn((N, C), generator=gen)
+    g[:, ::5] = 0.0
+    x0 = rnd((N, H, W, C), gen, dtype)
+    t = (g.double() / (H * W))[:, None, None, :].expand(N, H, W, C)
+    if accumulate:
+        dx = x0.to(dtype).cuda()
+        ref = x0.double() + t
+        err = 2 * U32 * (x0.double().abs() + t.abs())
+    else:
+        dx = torch.full((N, H, W, C), float("nan"), dtype=dtype, device="cuda")
+        ref = t
+        err = 2 * U32 * t.abs()
+    out = K.avgpool_bwd(g.cuda(), dx, accumulate=accumulate)
+    assert out is dx
+    got = dx.float().cpu().double()
+    assert torch.isfinite(got).all()
+    if dtype == torch.bfloat16:
+        err = err + 2.0 ** -8 * ref.abs()
+    bad = (got - ref).abs() > err
+    assert not bad.any(), (int(bad.sum()), float((got - ref).abs().max()))
+
+
+def _lin_abi(fn, *args):
+    from artiboost_amd import _lib as L
+    L.check(getattr(L.lib(), fn)(*args, L.stream()), fn)
+
+
+@pytest.mark.parametrize("M", [1, 5, 37, 64])
+@pytest.mark.parametrize("N,K", [(512, 512), (24, 512), (16, 512), (48, 512), (256, 512), (16, 256)])
+def test_linear_kernels_at_the_head_shapes(M, N, K):
+    """ab_linear_fwd / _dgrad / _wgrad at the shapes of HOPRegNet's heads (batch rows 1 .. 64, padded output widths), vs float64.  The
+    input is post-ReLU (exact zeros, one all-zero row), the data gradient is masked by an activation with exact zeros, and every
+    output buffer starts as NaN, so an element that is not written (or is accumulated into) fails.  Bound: an fp32 sum of R
+    products, in any order, is within (R + 2) 2^-24 sum |a b| of the exact one."""
+    from artiboost_amd import _lib as L
+    gen = torch.Generator().manual_seed(M * 7 + N + K)
+    x = torch.relu(torch.randn((M, K), generator=gen))
+    if M > 1:
+        x[M // 2] = 0.0
+    w = torch.randn((N, K), generator=gen) / K ** 0.5
+    b = torch.randn(N, generator=gen)
+    gy = torch.randn((M, N), generator=gen)
+    act = torch.relu(torch.randn((M, K), generator=gen))
+    x64, w64, b64, g64, m64 = x.double(), w.double(), b.double(), gy.double(), (act > 0).double()
+    nan = lambda *s: torch.full(s, float("nan"), device="cuda")      # noqa: E731
+    xd, wd, bd, gd, ad = x.cuda(), w.cuda(), b.cuda(), gy.cuda(), act.cuda()
+
+    def check(got, ref, err, what):
+        got = got.cpu().double()
+        assert torch.isfinite(got).all(), what
+        bad = (got - ref).abs() > err
+        assert not bad.any(), (what, int(bad.sum()), float((got - ref).abs().max()), float(err.max()))
+
+    for relu in (0, 1):
+        y = nan(M, N)
+        _lin_abi("ab_linear_fwd", L.ptr(xd), L.ptr(wd), L.ptr(bd), L.i(M), L.i(N), L.i(K), L.i(relu), L.ptr(y))
+        ref = x64 @ w64.T + b64
+        check(y, torch.relu(ref) if relu else ref, (K + 2) * U32 * (x64.abs() @ w64.abs().T + b64.abs()), f"fwd relu={relu}")
+    wt = w.t().contiguous().cuda()
+    for masked in (False, True):
+        gx = nan(M, K)
+        _lin_abi("ab_linear_dgrad", L.ptr(gd), L.ptr(wt), L.ptr(ad) if masked else None, L.i(M), L.i(N), L.i(K), L.ptr(gx))
+        mk = m64 if masked else 1.0
+        check(gx, (g64 @ w64) * mk, (N + 2) * U32 * (g64.abs() @ w64.abs()) * mk, f"dgrad masked={masked}")
+    dw, db = nan(N, K), nan(N)
+    _lin_abi("ab_linear_wgrad", L.ptr(gd), L.ptr(xd), L.i(M), L.i(N), L.i(K), L.ptr(dw), L.ptr(db))
+    check(dw, g64.T @ x64, (M + 2) * U32 * (g64.abs().T @ x64.abs()), "wgrad dW")
+    check(db, g64.sum(0), (M + 2) * U32 * g64.abs().sum(0), "wgrad db")
