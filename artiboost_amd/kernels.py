@@ -874,3 +874,28 @@ def mano_pca_bwd(pose_coeffs, betas, tables, g_verts, g_joints, g_full_pose=None
                                     L.i(-1 if center_idx is None else center_idx), L.i(B), L.ptr(g_verts), L.ptr(g_joints),
                                     L.ptr(g_full_pose), L.ptr(g_pc), L.ptr(g_b), L.stream()), "ab_mano_pca_bwd")
     return g_pc, g_b
+
+
+FIT_NP = 59             # parameters per hand of ab_mano_fit: so3 48 | beta 10 | bone 1
+
+
+def mano_fit(quat, pred_joints, tables, n_iter=20, step0=1, state=None, want_mesh=True, want_loss=False, want_grad=False):
+    """ab_mano_fit: B hands through n_iter Adam steps of the submission's MANO fit in one launch.  quat [B,64] raw IKNet output,
+    pred_joints [B,21,3]; tables: v_template, shapedirs, posedirs, J_regressor, weights, J_template [16,3], J_shapedirs [16,3,10]
+    (fitting.mano_fit_tables).  state None: start as the submit pass does (initialised inside the kernel); else (params, m, v), each
+    [B,59], copied first.  -> dict params / m / v [B,59], verts [B,778,3] / joints [B,21,3] (want_mesh), loss [B,n_iter]
+    (want_loss), grad [B,59] of the last step (want_grad)."""
+    B, dev = quat.shape[0], quat.device
+    z = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)      # noqa: E731
+    if state is None:
+        params, m, v = z(B, FIT_NP), z(B, FIT_NP), z(B, FIT_NP)
+    else:
+        params, m, v = (t.to(dev, torch.float32).clone().contiguous() for t in state)
+    o = dict(params=params, m=m, v=v, verts=z(B, 778, 3) if want_mesh else None, joints=z(B, 21, 3) if want_mesh else None,
+             loss=z(B, n_iter) if want_loss else None, grad=z(B, FIT_NP) if want_grad else None)
+    L.check(L.lib().ab_mano_fit(L.ptr(quat), L.ptr(pred_joints), L.ptr(tables["v_template"]), L.ptr(tables["shapedirs"]),
+                                L.ptr(tables["posedirs"]), L.ptr(tables["J_regressor"]), L.ptr(tables["weights"]),
+                                L.ptr(tables["J_template"]), L.ptr(tables["J_shapedirs"]), L.i(B), L.i(n_iter), L.i(step0),
+                                L.i(1 if state is None else 0), L.ptr(params), L.ptr(m), L.ptr(v), L.ptr(o["verts"]), L.ptr(o["joints"]),
+                                L.ptr(o["loss"]), L.ptr(o["grad"]), L.stream()), "ab_mano_fit")
+    return o

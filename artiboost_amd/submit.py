@@ -1,10 +1,14 @@
 """Evaluation / submission pass: anakin/submit/hodata_submit_epoch_pass.py:21-156 and
 submit_epoch_pass.py -- eval-mode forward over a loader, metrics, and the HO3D-v2 CodaLab prediction file.
 
-The hand-mesh fitting (`fit_mesh`: an IK network + licensed MANO assets) and the matplotlib drawings of the reference
-are not part of this build; without fitting the reference writes zero vertices, as here."""
+Without mesh fitting the vertex half of the file is zeros, as in the reference.  With FIT_MESH (`--postprocess_fit_mesh`) the
+vertices come from `fitting.FittingUnit` (IKNet + 20 Adam steps of a MANO fit per hand, one `ab_mano_fit` launch per batch on a
+HIP device) and are written as they are, in the predicted camera frame -- unlike the joints, they get no OpenGL flip (the
+reference's own convention, hodata_submit_epoch_pass.py:148-149).  FIT_MESH_USE_FITTED_JOINTS writes the fitted joints instead of
+the predicted ones, with the joint reorder undone and y and z negated (:129-140).  The matplotlib / OpenDR drawings are not built."""
 import json
 import os
+import warnings
 import zipfile
 
 import numpy as np
@@ -12,12 +16,26 @@ import torch
 
 
 class HOSubmitEpochPass:
-    """SubmitEpochPass.reg("hodata").  cfg: {"DUMP": bool, "TRUE_ROOT": bool} (arg.true_root in the reference)."""
+    """SubmitEpochPass.reg("hodata").  cfg: {"DUMP": bool, "TRUE_ROOT": bool (arg.true_root), "FIT_MESH": bool,
+    "FIT_MESH_USE_FITTED_JOINTS": bool, "FIT_MESH_IK": "iknet" | "iksolver", "DRAW": bool (arg.postprocess_draw),
+    "FITTING_UNIT": a FittingUnit-like callable to use instead of building one}."""
 
     def __init__(self, cfg=None):
         cfg = cfg or {}
         self.dump = cfg.get("DUMP", True)
         self.true_root = cfg.get("TRUE_ROOT", False)
+        self.fit_mesh = bool(cfg.get("FIT_MESH", False))
+        self.fit_mesh_use_fitted_joints = bool(cfg.get("FIT_MESH_USE_FITTED_JOINTS", False))
+        # "iksolver" is accepted and ignored, as in the reference: its FittingUnit always initialises with IKNet
+        self.fit_mesh_ik = cfg.get("FIT_MESH_IK", "iknet")
+        self.fitting_unit = None
+        if self.fit_mesh:
+            if cfg.get("DRAW"):
+                warnings.warn("--postprocess_draw (the OpenDR drawings of the fitted meshes) is not built; fitting goes on without it")
+            self.fitting_unit = cfg.get("FITTING_UNIT")
+            if self.fitting_unit is None:
+                from .fitting import FittingUnit
+                self.fitting_unit = FittingUnit()
 
     @staticmethod
     def get_order_idxs():
@@ -57,12 +75,25 @@ class HOSubmitEpochPass:
                     predicts["joints_3d_abs"][:, 0] = batch["root_joint"].to(predicts["joints_3d_abs"].device)
                 if evaluator:
                     evaluator.feed_all(predicts, batch, losses)
-                # HO3D submission convention (hodata_submit_epoch_pass.py:141-145): undo the joint reorder, OpenGL axes
-                pj = predicts["joints_3d_abs"].detach().cpu()[:, unorder].clone()
-                pj[:, :, 0] = -pj[:, :, 0]
-                joints = [-val.numpy()[0] for val in pj.split(1)]
-                res_joints.extend(joints)
-                res_verts.extend([np.zeros((778, 3))] * len(joints))
+                if self.fit_mesh:
+                    fitted_verts, fitted_joints = self.fitting_unit(batch, predicts["joints_3d_abs"].detach())
+                if self.fit_mesh and self.fit_mesh_use_fitted_joints:
+                    # hodata_submit_epoch_pass.py:129-140: reorder undone, y and z negated (no x flip, no overall sign)
+                    for fj in fitted_joints:
+                        item = np.array(fj[unorder, :])
+                        item[:, 1] = -item[:, 1]
+                        item[:, 2] = -item[:, 2]
+                        res_joints.append(item)
+                else:
+                    # HO3D submission convention (hodata_submit_epoch_pass.py:141-145): undo the joint reorder, OpenGL axes
+                    pj = predicts["joints_3d_abs"].detach().cpu()[:, unorder].clone()
+                    pj[:, :, 0] = -pj[:, :, 0]
+                    joints = [-val.numpy()[0] for val in pj.split(1)]
+                    res_joints.extend(joints)
+                if self.fit_mesh:
+                    res_verts.extend(fitted_verts)
+                else:
+                    res_verts.extend([np.zeros((778, 3))] * len(joints))
         if self.dump and dump_path:
             self.dump_json(dump_path, res_joints, res_verts, codalab=True)
         return res_joints

@@ -552,6 +552,23 @@ int ab_mano_pca_bwd(const float* pose_coeffs, const float* betas, const float* c
                     const float* weights, int ncomps, int center_idx, int B, const float* g_verts, const float* g_joints,
                     const float* g_full_pose, float* g_pose_coeffs, float* g_betas, void* stream);
 
+/* ---- Hand-mesh fitting of the submission pass (IKNet initialisation + 20 Adam steps of a MANO fit, all hands in one launch) -----
+ * anakin/postprocess/iknet/fittingunit.py:112-225 (FittingUnit.__call__: residuals :63-80, geo :43-60, mano_de :83-97) and
+ * utils.py:13-41 (quaternion -> axis-angle).  quat [B,64]: the raw IKNet output (16 quaternions, normalised here); pred_joints
+ * [B,21,3]: the predicted absolute joints (root = joint 9).  MANO tables as ab_mano_lbs (flat hand mean) plus J_template [16,3] =
+ * J_regressor . v_template and J_shapedirs [16,3,10] = J_regressor . shapedirs.  State in / out, [B,59] each (so3 48 | beta 10 |
+ * bone 1): params and the Adam moments adam_m / adam_v; init != 0 starts from so3 = the hand's own IKNet pose, beta = 0, bone = the
+ * predicted bone and zero moments (what the submit pass does), init == 0 reads them.  Runs n_iter Adam steps (lr 0.03, b1 = b2 =
+ * 0.5, eps 1e-8) with step indices n = step0 .. step0 + n_iter - 1 (bias correction 1 - 0.5^(n+1)); the pose regulariser pulls
+ * towards the mean of the WHOLE batch's IKNet poses, as in the reference.  Optional outputs: verts [B,778,3], joints [B,21,3] (the
+ * fitted mesh, scaled by the predicted bone and moved to the predicted root), loss [B,n_iter] (the objective before each step),
+ * grad [B,59] (the gradient of the last step).  0 <= n_iter, 0 <= step0, step0 + n_iter <= 120.  Fixed-order reductions only:
+ * bit-reproducible.                                                                                                                   */
+int ab_mano_fit(const float* quat, const float* pred_joints, const float* v_template, const float* shapedirs, const float* posedirs,
+                const float* J_regressor, const float* weights, const float* J_template, const float* J_shapedirs, int B, int n_iter,
+                int step0, int init, float* params, float* adam_m, float* adam_v, float* verts, float* joints, float* loss, float* grad,
+                void* stream);
+
 /* ---- Argument contracts of the dispatcher ops (torch.ops.artiboost_hip.*, libartiboost_torch.so) ------------------------------------------
  * The C entry points above take raw pointers and trust their caller.  Their PyTorch-dispatcher form (ops that "validate
  * with TORCH_CHECK") is generated from this header by artiboost_amd/gen_torch_ops.py and checks, before the C call, for EVERY op:
@@ -616,6 +633,7 @@ int ab_mano_pca_bwd(const float* pose_coeffs, const float* betas, const float* c
  * @check ab_mano_lbs: pose >= B*48; betas >= B*10; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; hands_mean >= 45; verts >= B*778*3; joints >= B*21*3; T_abs >= B*16*16
  * @check ab_mano_pca_fwd: pose_coeffs >= B*(3+ncomps); betas >= B*10; comps >= ncomps*45; hands_mean >= 45; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; verts >= B*778*3; joints >= B*21*3; full_pose >= B*48
  * @check ab_mano_pca_bwd: pose_coeffs g_pose_coeffs >= B*(3+ncomps); betas g_betas >= B*10; comps >= ncomps*45; hands_mean >= 45; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; g_verts >= B*778*3; g_joints >= B*21*3; g_full_pose >= B*48
+ * @check ab_mano_fit: quat >= B*64; pred_joints >= B*63; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; J_template >= 48; J_shapedirs >= 480; params adam_m adam_v grad >= B*59; verts >= B*778*3; joints >= B*63; loss >= B*n_iter
  */
 
 #ifdef __cplusplus

@@ -74,7 +74,10 @@ def main():
     random.seed(seed); np.random.seed(seed); torch.manual_seed(seed)
     cfg_name = os.path.basename(arg.cfg).split(".")[0]
     recorder = Recorder(f"submit_{cfg_name}", cfg, rank=0, time_f=time_f, eval_only=True)
-    submit_epoch_pass = SubmitEpochPass.build(arg.submit_dataset, cfg={"DUMP": bool(arg.submit_dump), "TRUE_ROOT": bool(arg.true_root)})
+    submit_epoch_pass = SubmitEpochPass.build(arg.submit_dataset, cfg={
+        "DUMP": bool(arg.submit_dump), "TRUE_ROOT": bool(arg.true_root), "FIT_MESH": bool(arg.postprocess_fit_mesh),
+        "FIT_MESH_USE_FITTED_JOINTS": bool(arg.postprocess_fit_mesh_use_fitted_joints), "FIT_MESH_IK": arg.postprocess_fit_mesh_ik,
+        "DRAW": bool(arg.postprocess_draw)})
     batch_size = arg.batch_size or cfg.get("TRAIN", {}).get("BATCH_SIZE", 8)
     if nrand:
         test_loader = _random_batches(nrand, batch_size, cfg["DATA_PRESET"]["IMAGE_SIZE"], seed)
