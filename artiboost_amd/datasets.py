@@ -65,6 +65,16 @@ def _obj_vertices(path):
     return np.asarray(out, np.float32)
 
 
+def _obj_faces(path):
+    """The `f a/.. b/.. c/..` lines of a Wavefront .obj as 0-based vertex indices (trimesh.load(path, process=False).faces)."""
+    out = []
+    with open(path) as f:
+        for line in f:
+            if line.startswith("f "):
+                out.append([int(t.split("/")[0]) - 1 for t in line.split()[1:4]])
+    return np.asarray(out, np.int32).reshape(-1, 3)
+
+
 @DATASET.register_module
 class HO3D(_DownloadedSet):
     """HO3D v2 from its download (anakin/datasets/ho3d.py:28-560, SPLIT_MODE "paper": train.txt / evaluation.txt): per frame the
@@ -130,7 +140,7 @@ class HO3D(_DownloadedSet):
             random.Random(1).shuffle(self.sample_idxs)
             self.sample_idxs = self.sample_idxs[:int(self.mini_factor * len(self.sample_idxs))]
         self.name2id = {v: k for k, v in CONST.YCB_IDX2CLASSES.items()}
-        self._can = {}
+        self._can, self._faces = {}, {}
 
     def _read_annotations(self, seq_frames):
         n = len(seq_frames)
@@ -176,6 +186,23 @@ class HO3D(_DownloadedSet):
             v = self.CAM_EXTR.dot(self.obj_verts[obj].transpose()).transpose()
             self._can[obj] = (v.min(0) + v.max(0)) / 2
         return self._can[obj]
+
+    def get_obj_idx(self, idx):
+        """ho3d.py:364-369: the YCB class id of the frame's object."""
+        return self.name2id[self.ann["obj_name"][self.sample_idxs[idx]]]
+
+    def get_obj_verts_can(self, idx):
+        """ho3d.py:376-385: the object's mesh in the OpenCV frame minus its bounding-box centre -> (verts_can float32, centre, None)."""
+        obj = self.ann["obj_name"][self.sample_idxs[idx]]
+        v = self.CAM_EXTR.dot(self.obj_verts[obj].transpose()).transpose()
+        return np.asarray(v - self._canonical(obj), np.float32), self._canonical(obj), None
+
+    def get_obj_faces(self, idx):
+        """ho3d.py:356-362: int32 faces of the object's mesh (YCB_models_supp/<obj>/textured_simple_ds.obj), read once per object."""
+        obj = self.ann["obj_name"][self.sample_idxs[idx]]
+        if obj not in self._faces:
+            self._faces[obj] = _obj_faces(os.path.join(self.data_root, "YCB_models_supp", obj, "textured_simple_ds.obj"))
+        return self._faces[obj]
 
     def get_annots(self, idx):
         i = self.sample_idxs[idx]

@@ -899,3 +899,44 @@ def mano_fit(quat, pred_joints, tables, n_iter=20, step0=1, state=None, want_mes
                                 L.i(1 if state is None else 0), L.ptr(params), L.ptr(m), L.ptr(v), L.ptr(o["verts"]), L.ptr(o["joints"]),
                                 L.ptr(o["loss"]), L.ptr(o["grad"]), L.stream()), "ab_mano_fit")
     return o
+
+
+DRAW_REC_WORDS = 12     # int32 words per vertex record of ab_draw_meshes
+
+
+def draw_meshes(hand_verts, tables, image, cam_intr, out, obj_id=None, obj_rot=None, obj_tsl=None, corners=None, debug=False):
+    """ab_draw_meshes: panels 2 (hand over the frame, the sample's camera) and 3 (hand + object on white, orbit camera) of the contact
+    sheet `out` uint8 [B,H,4W,3], in place; panels 1 and 4 are not touched.  hand_verts [B,778,3], image float [B,3,H,W] (frame - 0.5),
+    cam_intr [B,3,3].  tables (draw.MeshDrawer.tables): hand_faces [nhf,3] / adj_off [779] / adj_face int32 and, with an object
+    library, obj_verts / obj_normals / obj_faces / obj_vert_off / obj_face_off plus the ints n_obj, max_obj_verts, max_obj_faces.
+    obj_id int32 [B] (>= 0 library object, -1 none, -2 the box over corners[b]), obj_rot [B,3,3], obj_tsl [B,3], corners [B,8,3].
+    -> the orbit camera positions float [B,4] (xyz, pad), a view of the workspace; debug: -> (positions, vertex records int32
+    [B, 778 + max(max_obj_verts, 8), 12], keys int64 [B,2,H,W]), all views of the workspace."""
+    B, H, W = image.shape[0], image.shape[2], image.shape[3]
+    dev = hand_verts.device
+    if tuple(out.shape) != (B, H, 4 * W, 3) or out.dtype != torch.uint8:
+        raise ValueError(f"draw_meshes: out must be uint8 [{B},{H},{4 * W},3], got {out.dtype} {tuple(out.shape)}")
+    n_obj = int(tables.get("n_obj", 0))
+    mov, mof = int(tables.get("max_obj_verts", 0)), int(tables.get("max_obj_faces", 0))
+    if obj_id is None:
+        obj_id = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    if obj_rot is None:
+        obj_rot = torch.zeros((B, 3, 3), dtype=torch.float32, device=dev)
+    if obj_tsl is None:
+        obj_tsl = torch.zeros((B, 3), dtype=torch.float32, device=dev)
+    ws = torch.empty((L.lib().ab_draw_workspace_bytes(L.i(B), L.i(W), L.i(H), L.i(mov)),), dtype=torch.uint8, device=dev)
+    g = lambda k: L.ptr(tables[k]) if n_obj else None      # noqa: E731
+    L.check(L.lib().ab_draw_meshes(L.ptr(hand_verts), L.ptr(tables["hand_faces"]), L.i(tables["hand_faces"].shape[0]), L.ptr(tables["adj_off"]),
+                                   L.ptr(tables["adj_face"]), L.i(tables["adj_face"].numel()), g("obj_verts"), g("obj_normals"), g("obj_faces"),
+                                   g("obj_vert_off"), g("obj_face_off"), L.i(n_obj), L.i(tables["obj_verts"].shape[0] if n_obj else 0),
+                                   L.i(tables["obj_faces"].shape[0] if n_obj else 0), L.i(mov), L.i(mof), L.ptr(obj_id), L.ptr(obj_rot),
+                                   L.ptr(obj_tsl), L.ptr(corners), L.ptr(cam_intr), L.ptr(image), L.i(B), L.i(W), L.i(H), L.ptr(out), L.ptr(ws),
+                                   L.stream()), "ab_draw_meshes")
+    VP = 778 + max(mov, 8)
+    koff = L.lib().ab_draw_workspace_keys_offset(L.i(B), L.i(mov))
+    cam = ws[koff - (B * 16 + 255) // 256 * 256:][:B * 16].view(torch.float32).view(B, 4)
+    if not debug:
+        return cam
+    rec = ws[:B * VP * DRAW_REC_WORDS * 4].view(torch.int32).view(B, VP, DRAW_REC_WORDS)
+    keys = ws[koff:koff + B * 2 * H * W * 8].view(torch.int64).view(B, 2, H, W)
+    return cam, rec, keys

@@ -569,6 +569,34 @@ int ab_mano_fit(const float* quat, const float* pred_joints, const float* v_temp
                 int step0, int init, float* params, float* adam_m, float* adam_v, float* verts, float* joints, float* loss, float* grad,
                 void* stream);
 
+/* ---- Qualitative drawings of the submission pass (`--postprocess_draw`): two views of fitted hand + posed object per sample ----------
+ * anakin/viztools/draw.py:400-449 (save_a_image_with_mesh_joints_objects), opendr_renderer.py:137-170 (three Lambertian point lights),
+ * draw.py:236-276 (mayavi view azimuth -50, elevation 50, distance 0.6).  The reference draws with OpenDR / mayavi on the host, one
+ * sample at a time; their pixels are not reproduced -- DESIGN.md section 18 defines this build's, tests/draw_oracle.py restates them.
+ * out: uint8 [B, H, 4W, 3], the contact sheet; panels 2 (columns W .. 2W-1: the hand alone over the frame, the sample's cam_intr
+ * [B,3,3] with identity extrinsic) and 3 (columns 2W .. 3W-1: hand and object on white from the orbit camera) are written, every pixel
+ * of them; panels 1 and 4 are not touched.  image: the batch's float [B,3,H,W] tensor (frame - 0.5); an uncovered pixel of panel 2 is
+ * floor(255 (image + 0.5) + 0.5) clamped to a byte.
+ * hand_verts [B,778,3] (what ab_mano_fit returns), hand_faces [nhf,3], adj_off [779] / adj_face [nadj]: the faces around each hand
+ * vertex (CSR, ascending face index; vertex normals are gathered in that order, no atomics).  Object library in canonical coordinates:
+ * obj_verts / obj_normals [nov,3] and obj_faces [nof,3] (indices local to the object) packed, obj_vert_off / obj_face_off [n_obj+1];
+ * max_obj_verts / max_obj_faces >= the largest object's counts (they size the vertex records and the grid; an object larger than that is
+ * drawn without the faces that reach past it).  Per sample: obj_id [B] (>= 0 library object, -1 no object, -2 the 12-triangle box over
+ * corners[b], eight points indexed 4 ix + 2 iy + iz), obj_rot [B,3,3] and obj_tsl [B,3] (X = R v + t), corners [B,8,3] (may be NULL when no
+ * sample asks for the box).  The library pointers may be NULL with n_obj == 0.
+ * workspace: ab_draw_workspace_bytes(B, W, H, max_obj_verts) bytes.  After the call it holds, from byte 0, the vertex records
+ * [B, 778 + max(max_obj_verts, 8), 12] (int32 words: sx0 sy0 zq0 sx1 sy1 zq1 | float zv0 zv1 r g b | flags; view 0 = camera, 1 = orbit;
+ * screen positions in 1/256 px, zq the 24-bit inverse depth, flags bit v = usable in view v) and, from byte
+ * ab_draw_workspace_keys_offset(B, max_obj_verts), the depth keys uint64 [B, 2, H, W] (zq << 32 | face, hand faces first; all ones =
+ * uncovered) -- the stage outputs the tests compare.  W, H <= 4096.  Integer atomicMin only: bit-reproducible.                      */
+long ab_draw_workspace_bytes(int B, int W, int H, int max_obj_verts);
+long ab_draw_workspace_keys_offset(int B, int max_obj_verts);
+int ab_draw_meshes(const float* hand_verts, const int32_t* hand_faces, int nhf, const int32_t* adj_off, const int32_t* adj_face, int nadj,
+                   const float* obj_verts, const float* obj_normals, const int32_t* obj_faces, const int32_t* obj_vert_off,
+                   const int32_t* obj_face_off, int n_obj, int nov, int nof, int max_obj_verts, int max_obj_faces, const int32_t* obj_id,
+                   const float* obj_rot, const float* obj_tsl, const float* corners, const float* cam_intr, const float* image, int B, int W,
+                   int H, uint8_t* out, void* workspace, void* stream);
+
 /* ---- Argument contracts of the dispatcher ops (torch.ops.artiboost_hip.*, libartiboost_torch.so) ------------------------------------------
  * The C entry points above take raw pointers and trust their caller.  Their PyTorch-dispatcher form (ops that "validate
  * with TORCH_CHECK") is generated from this header by artiboost_amd/gen_torch_ops.py and checks, before the C call, for EVERY op:
@@ -634,6 +662,7 @@ int ab_mano_fit(const float* quat, const float* pred_joints, const float* v_temp
  * @check ab_mano_pca_fwd: pose_coeffs >= B*(3+ncomps); betas >= B*10; comps >= ncomps*45; hands_mean >= 45; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; verts >= B*778*3; joints >= B*21*3; full_pose >= B*48
  * @check ab_mano_pca_bwd: pose_coeffs g_pose_coeffs >= B*(3+ncomps); betas g_betas >= B*10; comps >= ncomps*45; hands_mean >= 45; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; g_verts >= B*778*3; g_joints >= B*21*3; g_full_pose >= B*48
  * @check ab_mano_fit: quat >= B*64; pred_joints >= B*63; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; J_template >= 48; J_shapedirs >= 480; params adam_m adam_v grad >= B*59; verts >= B*778*3; joints >= B*63; loss >= B*n_iter
+ * @check ab_draw_meshes: hand_verts >= B*778*3; hand_faces >= nhf*3; adj_off >= 779; adj_face >= nadj; obj_verts obj_normals >= nov*3; obj_faces >= nof*3; obj_vert_off obj_face_off >= n_obj+1; obj_id >= B; obj_rot >= B*9; obj_tsl >= B*3; corners >= B*24; cam_intr >= B*9; image >= B*3*H*W; out >= B*H*4*W*3; bytes workspace >= ab_draw_workspace_bytes(B,W,H,max_obj_verts)
  */
 
 #ifdef __cplusplus

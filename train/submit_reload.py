@@ -77,7 +77,7 @@ def main():
     submit_epoch_pass = SubmitEpochPass.build(arg.submit_dataset, cfg={
         "DUMP": bool(arg.submit_dump), "TRUE_ROOT": bool(arg.true_root), "FIT_MESH": bool(arg.postprocess_fit_mesh),
         "FIT_MESH_USE_FITTED_JOINTS": bool(arg.postprocess_fit_mesh_use_fitted_joints), "FIT_MESH_IK": arg.postprocess_fit_mesh_ik,
-        "DRAW": bool(arg.postprocess_draw)})
+        "DRAW": bool(arg.postprocess_draw), "DRAW_PATH": arg.postprocess_draw_path})
     batch_size = arg.batch_size or cfg.get("TRAIN", {}).get("BATCH_SIZE", 8)
     if nrand:
         test_loader = _random_batches(nrand, batch_size, cfg["DATA_PRESET"]["IMAGE_SIZE"], seed)
