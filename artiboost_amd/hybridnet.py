@@ -91,6 +91,7 @@ class ParamStore:
         self.grad = torch.zeros(self.total, dtype=torch.float32, device=self.device)
         self.stats = torch.zeros(boff, dtype=torch.float32, device=self.device)
         self.num_batches_tracked = 0
+        self.frozen_bn = False         # BACKBONE.FREEZE_BATCHNORM (set by the model wrappers): FrozenBatchNorm2d keeps no counter
 
     # ------------------------------------------------------------------ table
     def _add(self, name, kind, ref_shape, kshape):
@@ -284,7 +285,7 @@ class ParamStore:
             if not grads and pre is not None and pre + ".running_mean" in self.buffers:
                 out[rn(pre + ".running_mean")] = self.stat(pre + ".running_mean").clone()
                 out[rn(pre + ".running_var")] = self.stat(pre + ".running_var").clone()
-                if not (getattr(self, "frozen_bn", False) and pre.startswith("backbone.")):     # FrozenBatchNorm2d keeps no counter (resnet.py:45-55)
+                if not (self.frozen_bn and pre.startswith("backbone.")):     # FrozenBatchNorm2d keeps no counter (resnet.py:45-55)
                     out[rn(pre + ".num_batches_tracked")] = torch.tensor(int(self.num_batches_tracked), dtype=torch.int64)
         return out
 
@@ -332,7 +333,18 @@ class HybridNet:
         self.lp = None           # low-precision copy of the flat params (bf16 mode)
         self.tr = {}             # IHWO (data-gradient) copies of conv weights in the compute dtype
         self._packed = False
-        self.saved = None
+        self.saved = None        # the training forward's activations, consumed by backward()
+        self.last = None         # outputs of the latest forward (segment graphs swap `saved` / `last`, not other attributes)
+        self.eval_fold = True    # bf16x3 eval: BatchNorm folded into the conv epilogues (tests flip it: bit-identical to the unfolded forward)
+        self._tr_plan = None     # batched IHWO transpose of the data-gradient weight copies (pack_weights)
+        self._eval_desc = None   # descriptor table of the one-launch eval BatchNorm parameters (_eval_params_all)
+        self._eval_bnp = None    # ... and this eval forward's views into its output
+        self._zparts = {}        # C -> all-zero BatchNorm-backward partial sums (frozen BatchNorm)
+        self._g3 = None          # padded copy of the box head's incoming gradient
+        self._head_full = None   # head_fwd's outputs including the padding class (odd class counts)
+        self._wgrp = []          # open group of same-shape 3x3 weight gradients: [((x_hi, x_lo), (dy_hi, dy_lo), out)]
+        self._wgrp_key = None    # ... its (x, dy) plane shapes
+        self._wgrp_max = {}      # (x, dy) plane shapes -> largest group the kernel takes (0: none)
 
     # ------------------------------------------------------------------ weights in compute precision
     def _dgrad_names(self):
@@ -363,7 +375,7 @@ class HybridNet:
                 K.cast_bf16(p.flat, self.lp)
         else:
             self.lp = p.flat
-        if getattr(self, "_tr_plan", None) is None:
+        if self._tr_plan is None:
             pairs = []
             if self.x3:      # IHWO copies as split planes [2][tot]: written by the transpose launch itself
                 tot = sum(_round_up(p.entries[n].numel, 64) for n in self._dgrad_names())
@@ -435,12 +447,51 @@ class HybridNet:
     # (one MFMA pass, bf16 operands, fp32 accumulate).  Their rounding does not propagate (nothing consumes a weight gradient but Adam).
     wgrad_1pass = os.environ.get("AB_WGRAD_1PASS", "0") == "1"
 
-    def _conv_wgrad(self, x, dy, kh, kw, stride, pad, out=None, **kws):
+    # Weight-gradient queue.  Nothing consumes a weight gradient before the optimizer, so under bf16x3 up to K.WGRAD_GROUP_MAX consecutive
+    # SAME-SHAPE 3x3 / stride-1 weight gradients (a stage's blocks) wait for each other and run as one slab launch + one reduction
+    # (ab_conv2d_wgrad_x3_group; per shape the largest group the kernel takes in one round of workgroups).  The group is launched on a shape
+    # change, when it is full, or by _wgrad_join() at the end of a backward stage: gradients are complete only after that, and the queued
+    # layers' operand planes are kept until then.  Every other weight gradient is launched at once, in the same queue, each slab
+    # reduction right behind its slab kernel.  Measurements, and the schedules that lost (side stream, batched reductions): DESIGN 9, 15.5.
+    def _wgrad(self, x, dy, kh, kw, stride, pad, out):
+        """The weight gradient of one convolution into `out`: queued for the open group, or launched now."""
+        if self.x3 and not self.wgrad_1pass and (kh, kw, stride, pad) == (3, 3, 1, 1):
+            x, dy = K._planes(x), K._planes(dy)          # (split now: the planes, not the fp32 tensors, are what is kept)
+            key = (tuple(x[0].shape), tuple(dy[0].shape))
+            if key not in self._wgrp_max:
+                self._wgrp_max[key] = next((G for G in range(K.WGRAD_GROUP_MAX, 1, -1) if K.conv2d_wgrad_x3_group_ok(x, dy, G)), 0)
+            if self._wgrp_max[key]:
+                if self._wgrp and self._wgrp_key != key:
+                    self._wgrad_join()
+                self._wgrp.append((x, dy, out))
+                self._wgrp_key = key
+                if len(self._wgrp) >= self._wgrp_max[key]:
+                    self._wgrad_join()
+                return
         if self.x3 and self.wgrad_1pass:
-            return K.conv2d_wgrad(K._planes(x)[0], K._planes(dy)[0], kh, kw, stride, pad, out=out, **kws)
-        if self.x3:
-            return K.conv2d_wgrad_x3(x, dy, kh, kw, stride, pad, out=out, **kws)
-        return K.conv2d_wgrad(x, dy, kh, kw, stride, pad, out=out, **kws)
+            K.conv2d_wgrad(K._planes(x)[0], K._planes(dy)[0], kh, kw, stride, pad, out=out)
+        elif self.x3:
+            K.conv2d_wgrad_x3(x, dy, kh, kw, stride, pad, out=out)
+        else:
+            K.conv2d_wgrad(x, dy, kh, kw, stride, pad, out=out)
+
+    def _stem_wgrad(self, xpad, dy, H, W, out):
+        """The 7x7 stem's weight gradient (it never joins a group), launched now."""
+        if self.x3 and self.wgrad_1pass:
+            K.conv2d_stem_wgrad(K._planes(xpad)[0], K._planes(dy)[0], H, W, out=out)
+        elif self.x3:
+            K.conv2d_stem_wgrad_x3(xpad, dy, H, W, out=out)
+        else:
+            K.conv2d_stem_wgrad(xpad, dy, H, W, out=out)
+
+    def _wgrad_join(self):
+        """Launches the open group: after it every weight gradient issued so far is in the queue."""
+        items, self._wgrp = self._wgrp, []
+        if len(items) == 1:
+            x, dy, out = items[0]
+            K.conv2d_wgrad_x3(x, dy, 3, 3, 1, 1, out=out)
+        elif items:
+            K.conv2d_wgrad_x3_group(items)
 
     # ------------------------------------------------------------------ BN helper
     def _frozen(self, prefix):
@@ -449,12 +500,9 @@ class HybridNet:
     def _zero_part(self, C):
         """BatchNorm-backward partial sums of a FROZEN BatchNorm: zero, so that ab_bn_bwd* yields dy = scale * dz and zero parameter
         gradients (FrozenBatchNorm2d has no learnable state: its weight / bias are buffers)."""
-        z = getattr(self, "_zparts", None)
-        if z is None:
-            z = self._zparts = {}
-        if C not in z:
-            z[C] = torch.zeros((1, C, 2), dtype=torch.float32, device=self.p.device)
-        return z[C]
+        if C not in self._zparts:
+            self._zparts[C] = torch.zeros((1, C, 2), dtype=torch.float32, device=self.p.device)
+        return self._zparts[C]
 
     def _bn_params(self, prefix, stats_part, count):
         p = self.p
@@ -464,9 +512,8 @@ class HybridNet:
         if self.training:
             return K.bn_finalize(stats_part, count, p.view(prefix + ".weight"), p.view(prefix + ".bias"),
                                  p.stat(prefix + ".running_mean"), p.stat(prefix + ".running_var"))
-        ev = getattr(self, "_eval_bnp", None)
-        if ev is not None:
-            return ev[prefix]                      # this forward's batched launch (forward() -> _eval_params_all)
+        if self._eval_bnp is not None:
+            return self._eval_bnp[prefix]          # this forward's batched launch (forward() -> _eval_params_all)
         return K.bn_eval_params(p.view(prefix + ".weight"), p.view(prefix + ".bias"),
                                 p.stat(prefix + ".running_mean"), p.stat(prefix + ".running_var"))
 
@@ -474,7 +521,7 @@ class HybridNet:
         """Eval mode: (scale, shift, mean, invstd) of all 38 BatchNorms in ONE launch per forward (they are re-derived at every
         forward: weights and running statistics move between evaluations) instead of one tiny launch each."""
         p = self.p
-        if getattr(self, "_eval_desc", None) is None:
+        if self._eval_desc is None:
             import numpy as np
             rows, off, views = [], 0, {}
             prefixes = [k[:-len(".running_mean")] for k in p.buffers if k.endswith(".running_mean")]
@@ -552,20 +599,15 @@ class HybridNet:
             y0, st = K.conv2d_stem_fwd_x3(xpad, self.w("backbone.conv1.weight"), H, W, want_stats=True)
         else:
             y0, st = K.conv2d_stem_fwd(xpad, self.w("backbone.conv1.weight"), H, W, want_stats=True)
-        if self.fuse_stem:
-            bnp0 = self._bn_params("backbone.bn1", st, N * (H // 2) * (W // 2))
-            # BN + ReLU + 3x3/2 max-pool: the 128x128x64 activation is never stored (bf16x3: the pooled planes come from the same pass)
-            if self.x3:      # training: + the raw conv output at the winners, all the backward's reduction needs of y0
-                res = K.bn_relu_maxpool_fwd_x3(y0, bnp0, want_win=tr and self.pool_win, want_f32=not self.res_planes)
-                x, pool_idx = res[0], res[1]
-                S["pool_ywin"] = res[2] if len(res) > 2 else None
-            else:
-                x, pool_idx = K.bn_relu_maxpool_fwd(y0, bnp0)
+        bnp0 = self._bn_params("backbone.bn1", st, N * (H // 2) * (W // 2))
+        # BN + ReLU + 3x3/2 max-pool in one pass: the 128x128x64 activation is never stored.  bf16x3: the pooled tensor leaves it
+        # as planes only; training: + the raw conv output at the winners, all the backward's reduction needs of y0
+        if self.x3:
+            res = K.bn_relu_maxpool_fwd_x3(y0, bnp0, want_win=tr, want_f32=False)
+            x, pool_idx = res[0], res[1]
+            S["pool_ywin"] = res[2] if len(res) > 2 else None
         else:
-            a0, bnp0 = self._bn("backbone.bn1", y0, st, N * (H // 2) * (W // 2), feeds_conv=False)
-            x, pool_idx = K.maxpool_fwd(a0)
-        if self.x3 and x.dtype != torch.bfloat16 and getattr(x, "_ab_split", None) is None:
-            x._ab_split = K.split(x)      # layer1.0 reads the pooled tensor three times (conv1, residual, conv1's weight gradient)
+            x, pool_idx = K.bn_relu_maxpool_fwd(y0, bnp0)
         S.update(y0=y0, bnp0=bnp0, pool_idx=pool_idx)
         inpl = 64
         hp = p.hp
@@ -588,20 +630,11 @@ class HybridNet:
                 a1, bnp1 = self._bn(pre + ".bn1", y1, st1, cnt)
                 y2, st2 = self._conv_fwd(a1, pre + ".conv2.weight", 1, 1, want_stats=True)
                 rec = dict(pre=pre, stride=stride, x=x, y1=y1, a1=a1, bnp1=bnp1, y2=y2, ds=False)
-                if stride != 1 or inpl != planes:
-                    yd, std_ = self._conv_fwd(x, pre + ".downsample.0.weight", stride, 0, want_stats=True)
-                    if self.x3 and self.fuse_ds_bn:      # identity = bn_ds(yd) is applied inside bn2's pass, never stored
-                        r, bnpd = yd, self._bn_params(pre + ".downsample.1", std_, cnt)
-                    else:
-                        r, bnpd = self._bn(pre + ".downsample.1", yd, std_, cnt, relu=False, feeds_conv=False)
-                    rec.update(ds=True, yd=yd, bnpd=bnpd)
-                else:
-                    r, bnpd = x, None
-                # bf16x3 + AB_RES_PLANES=1: block outputs exist only as their planes (the next block adds hi + lo as its residual);
+                r, res_bnp = self._identity(x, pre, stride, cnt, stride != 1 or inpl != planes, rec)
+                # bf16x3: block outputs exist only as their planes (the next block adds hi + lo as its residual);
                 # the last block's output is also kept in fp32 (global average pool, transposed conv head)
                 last = li == 4 and b == nblk - 1
-                out, bnp2 = self._bn(pre + ".bn2", y2, st2, cnt, res=r, relu=True, keep_f32=(not self.res_planes) or last or not self.x3,
-                                     res_bnp=bnpd if (self.x3 and self.fuse_ds_bn) else None)
+                out, bnp2 = self._bn(pre + ".bn2", y2, st2, cnt, res=r, relu=True, keep_f32=last or not self.x3, res_bnp=res_bnp)
                 rec.update(bnp2=bnp2, out=out)
                 if not tr:
                     rec = dict(pre=pre)
@@ -617,15 +650,11 @@ class HybridNet:
             return fmean
         h4, w4 = feat.shape[-3], feat.shape[-2]
         # ---- IntegralDeconvHead: ConvT == data-gradient of the mirrored stride-2 conv
-        # transposed convs: the data-gradient kernel of the mirrored conv, BatchNorm partials from its epilogue
-        # (AB_DECONV_STATS=0: separate col_stats passes)
-        fused = os.environ.get("AB_DECONV_STATS", "1") != "0"
-
+        # transposed convs: the data-gradient kernel of the mirrored conv, in training with the BatchNorm partials from its epilogue
         def deconv(x, name, hw):
-            if tr and fused:
+            if tr:
                 return self._conv_dgrad(x, name, hw, 2, 1, want_stats=True)
-            d = self._conv_dgrad(x, name, hw, 2, 1)
-            return d, (K.col_stats(d) if tr else None)
+            return self._conv_dgrad(x, name, hw, 2, 1), None
 
         if not tr and self.x3 and self.eval_fold:      # eval: BatchNorm + ReLU of the two transposed convolutions in their epilogues
             d1 = d2 = bnpd1 = bnpd2 = None
@@ -642,8 +671,7 @@ class HybridNet:
         # (ab_conv1x1_sam_fwd_x3); head_fwd() then only merges the per-tile rows
         wf = self.w(hp + ".final_layer.weight") if self.x3 else None
         sam_part = None          # (travels in self.last with the logits it describes: segment graphs swap `last`, not attributes of the net)
-        if (self.x3 and self.fuse_sam and self.norm == 0
-                and K.conv1x1_sam_fwd_x3_ok(e2, wf, p.nclasses_pad, p.depth, DEPTH_PITCH)):
+        if self.x3 and self.norm == 0 and K.conv1x1_sam_fwd_x3_ok(e2, wf, p.nclasses_pad, p.depth, DEPTH_PITCH):
             logits, sam_part = K.conv1x1_sam_fwd_x3(e2, wf, p.view(hp + ".final_layer.bias"), p.nclasses_pad, p.depth)
         else:
             logits = self._conv_fwd(e2, hp + ".final_layer.weight", 1, 0, bias=p.view(hp + ".final_layer.bias"))
@@ -663,7 +691,18 @@ class HybridNet:
         self.last = dict(feat=feat, fmean=fmean, logits=logits, box_raw=b3.view(N, BOX_OUT_PAD), sam_part=sam_part)
         return logits, box6d
 
-    eval_fold = os.environ.get("AB_EVAL_FOLD", "1") != "0"       # bf16x3 eval: BatchNorm folded into the 3x3 conv epilogues
+    def _identity(self, x, pre, stride, cnt, has_ds, rec):
+        """The identity branch of a residual block -> (r, res_bnp) for the closing BatchNorm's apply pass, which adds r (bf16x3 with a
+        downsample: bn_ds(r), the downsample BatchNorm applied inside that pass and never stored).  Records the branch in `rec`."""
+        if not has_ds:
+            return x, None
+        yd, std_ = self._conv_fwd(x, pre + ".downsample.0.weight", stride, 0, want_stats=True)
+        if self.x3:
+            r, bnpd = yd, self._bn_params(pre + ".downsample.1", std_, cnt)
+        else:
+            r, bnpd = self._bn(pre + ".downsample.1", yd, std_, cnt, relu=False, feeds_conv=False)
+        rec.update(ds=True, yd=yd, bnpd=bnpd)
+        return r, (bnpd if self.x3 else None)
 
     def _bottleneck_fwd(self, x, pre, planes, stride, has_ds, last):
         """Bottleneck.forward (resnet.py:104-141): 1x1 -> bn -> relu -> 3x3 (stride) -> bn -> relu -> 1x1 (x4) -> bn, + identity /
@@ -675,17 +714,8 @@ class HybridNet:
         a2, bnp2 = self._bn(pre + ".bn2", y2, st2, cnt)
         y3, st3 = self._conv_fwd(a2, pre + ".conv3.weight", 1, 0, want_stats=True)
         rec = dict(kind="bottleneck", pre=pre, stride=stride, x=x, y1=y1, a1=a1, bnp1=bnp1, y2=y2, a2=a2, bnp2=bnp2, y3=y3, ds=False)
-        if has_ds:
-            yd, std_ = self._conv_fwd(x, pre + ".downsample.0.weight", stride, 0, want_stats=True)
-            if self.x3 and self.fuse_ds_bn:
-                r, bnpd = yd, self._bn_params(pre + ".downsample.1", std_, cnt)
-            else:
-                r, bnpd = self._bn(pre + ".downsample.1", yd, std_, cnt, relu=False, feeds_conv=False)
-            rec.update(ds=True, yd=yd, bnpd=bnpd)
-        else:
-            r, bnpd = x, None
-        out, bnp3 = self._bn(pre + ".bn3", y3, st3, cnt, res=r, relu=True, keep_f32=(not self.res_planes) or last or not self.x3,
-                             res_bnp=bnpd if (self.x3 and self.fuse_ds_bn and has_ds) else None)
+        r, res_bnp = self._identity(x, pre, stride, cnt, has_ds, rec)
+        out, bnp3 = self._bn(pre + ".bn3", y3, st3, cnt, res=r, relu=True, keep_f32=last or not self.x3, res_bnp=res_bnp)
         rec.update(bnp3=bnp3, out=out, y2_last=y3, bnp_last=bnp3)
         return out, rec
 
@@ -697,18 +727,18 @@ class HybridNet:
         dy3, dz = self._bn_bwd(dout, rec["out"], rec["y3"], rec["bnp3"], gv(pre + ".bn3.weight"), gv(pre + ".bn3.bias"),
                            relu=True, want_dz=True, part=dout_part, frozen=fz)
         a2, a1 = rec["a2"], rec["a1"]
-        self._wgrad_side(self._conv_wgrad, a2, dy3, 1, 1, 1, 0, out=gv(pre + ".conv3.weight"))
+        self._wgrad(a2, dy3, 1, 1, 1, 0, out=gv(pre + ".conv3.weight"))
         da2, part2 = self._conv_dgrad(dy3, pre + ".conv3.weight", (dy3.shape[-3], dy3.shape[-2]), 1, 0, bn=(rec["y2"], None, rec["bnp2"]))
         dy2 = self._bn_bwd(da2, a2, rec["y2"], rec["bnp2"], gv(pre + ".bn2.weight"), gv(pre + ".bn2.bias"), relu="recompute", part=part2, frozen=fz)
-        self._wgrad_side(self._conv_wgrad, a1, dy2, 3, 3, stride, 1, out=gv(pre + ".conv2.weight"))
+        self._wgrad(a1, dy2, 3, 3, stride, 1, out=gv(pre + ".conv2.weight"))
         h1, w1 = (a1.shape[-3], a1.shape[-2])
         da1, part1 = self._conv_dgrad(dy2, pre + ".conv2.weight", (h1, w1), stride, 1, bn=(rec["y1"], None, rec["bnp1"]))
         dy1 = self._bn_bwd(da1, a1, rec["y1"], rec["bnp1"], gv(pre + ".bn1.weight"), gv(pre + ".bn1.bias"), relu="recompute", part=part1, frozen=fz)
-        self._wgrad_side(self._conv_wgrad, x, dy1, 1, 1, 1, 0, out=gv(pre + ".conv1.weight"))
+        self._wgrad(x, dy1, 1, 1, 1, 0, out=gv(pre + ".conv1.weight"))
         hw = (x.shape[-3], x.shape[-2])
         if rec["ds"]:
             dyd = self._bn_bwd(dz, None, rec["yd"], rec["bnpd"], gv(pre + ".downsample.1.weight"), gv(pre + ".downsample.1.bias"), relu=False, frozen=fz)
-            self._wgrad_side(self._conv_wgrad, x, dyd, 1, 1, stride, 0, out=gv(pre + ".downsample.0.weight"))
+            self._wgrad(x, dyd, 1, 1, stride, 0, out=gv(pre + ".downsample.0.weight"))
             dx = self._conv_dgrad(dy1, pre + ".conv1.weight", hw, 1, 0)
             return self._conv_dgrad(dyd, pre + ".downsample.0.weight", hw, stride, 0, addend=dx), None
         return self._conv_dgrad(dy1, pre + ".conv1.weight", hw, 1, 0, addend=dz), None
@@ -716,7 +746,7 @@ class HybridNet:
     def _eval_block(self, x, pre, stride, has_ds, last):
         """One BasicBlock in eval mode (resnet.py:85-101 with running statistics): where the 3x3 kernel takes the shape the
         BatchNorm after a convolution (+ residual + ReLU) rides in its epilogue and the fp32 conv output is never stored;
-        bit-identical to conv + ab_bn_apply_x3 (AB_EVAL_FOLD=0)."""
+        bit-identical to conv + ab_bn_apply_x3 (eval_fold = False)."""
         def conv_bn(inp, cname, bname, s, res, relu, want_f32=False):
             w = self.w(cname)
             bnp = self._bn_params(bname, None, 0)
@@ -733,11 +763,11 @@ class HybridNet:
                                        relu=False, planes=False)
         else:
             r = x
-        return conv_bn(a1, pre + ".conv2.weight", pre + ".bn2", 1, r, True, want_f32=last or not self.res_planes)
+        return conv_bn(a1, pre + ".conv2.weight", pre + ".bn2", 1, r, True, want_f32=last)
 
     def head_fwd(self, logits):
         """-> kp3d [N,22,3], conf [N,22], stat (kept for head_bwd)."""
-        last = getattr(self, "last", None)
+        last = self.last
         part = last.get("sam_part") if last is not None and logits is last.get("logits") else None
         if part is not None and part.shape[0] == logits.shape[0]:      # statistics from the GEMM epilogue of THIS forward
             kp3d, conf, stat = softargmax3d_stage2(part, self.p.nclasses_pad)
@@ -762,108 +792,13 @@ class HybridNet:
                 g_conf = gc
         if self.x3:
             # (the final layer's bias gradient = column sums of dlogits comes out of the same pass; backward() sees the tag)
-            dbias = self.p.gview(hp + ".final_layer.bias") if (self.sam_bias and self.saved is not None) else None
+            dbias = self.p.gview(hp + ".final_layer.bias") if self.saved is not None else None
             return softargmax3d_bwd_x3(logits, CP, self.p.depth, DEPTH_PITCH, kp3d, conf, stat, g_kp3d, g_conf, dbias=dbias,
                                        norm=self.norm)
         return softargmax3d_bwd(logits, CP, self.p.depth, DEPTH_PITCH, kp3d, conf, stat, g_kp3d, g_conf,
                                 inplace=True, norm=self.norm)
 
     # ------------------------------------------------------------------ backward
-    # Weight gradients are off the critical path (nothing consumes them before the optimizer), so they CAN be issued on
-    # a side stream to co-run with the HBM-bound BatchNorm-backward passes of the layers below.  Measured on MI355X
-    # (B=64, 256x256, graph replay): 7366 samples/s with the side stream vs 7715 without -- co-scheduled workgroups evict
-    # each other's L2 / LDS residency and the single-queue order is faster.  Round 3, bf16x3 (tools/ab_env.sh AB_WGRAD_OVERLAP 0 1 2):
-    # 9.68 ms/step in one queue, 9.84 / 10.01 with the side stream.  Kept as an opt-in (AB_WGRAD_OVERLAP=1).
-    overlap_wgrad = os.environ.get("AB_WGRAD_OVERLAP", "0") == "1"
-    fuse_stem = os.environ.get("AB_STEM_FUSE", "1") != "0"       # stem BN+ReLU+max-pool as one pass (forward)
-    fuse_stem_bwd = os.environ.get("AB_STEM_FUSE_BWD", "0") == "1"   # ... and the gather-based fused backward
-    stem_pool_reduce = os.environ.get("AB_STEM_POOL_REDUCE", "1") != "0"   # bf16x3: see _backward_trunk
-    res_planes = os.environ.get("AB_RES_PLANES", "1") != "0"     # bf16x3: block outputs only as (hi, lo) planes, no fp32 copy
-    pool_win = os.environ.get("AB_POOL_WIN", "1") != "0"          # bf16x3: stem BatchNorm-backward reduction over the pooled elements
-    fuse_sam = os.environ.get("AB_FUSE_SAM", "1") != "0"          # bf16x3: soft-argmax stage 1 in the final layer's GEMM epilogue
-    sam_bias = os.environ.get("AB_SAM_BIAS", "1") != "0"          # bf16x3: final-layer bias gradient out of the soft-argmax backward
-    fuse_ds_bn = os.environ.get("AB_FUSE_DS_BN", "1") != "0"      # bf16x3: the downsample BatchNorm inside bn2's apply pass
-    pair_dgrad = os.environ.get("AB_PAIR_DGRAD", "1") != "0"      # bf16x3: conv1 + downsample data gradients of a block in one launch
-    pair_dgrad_bn = os.environ.get("AB_PAIR_DGRAD_BN", "1") != "0"      # ... with the BatchNorm-backward reduction of the stage below in its epilogue
-
-    # AB_WGRAD_BATCH=1: the fixed-order slab reductions of a backward stage's weight gradients run as ONE launch at the end
-    # of the stage instead of one per layer right behind its slab kernel.  Bit-identical, 38 graph nodes fewer -- and 2 %
-    # slower (6.65 vs 6.51 ms/step): a layer's slabs (<= 50 MB) are still in the 256 MB Infinity Cache when reduced at
-    # once, a stage's 0.3-0.7 GB are not.  Kept as an opt-in.
-    batch_wgrad_reduce = os.environ.get("AB_WGRAD_BATCH", "0") == "1"
-
-    # bf16x3, AB_WGRAD_GROUP=g > 1: the slab reductions of every g consecutive weight gradients run as ONE launch (bit-identical;
-    # each deferred gradient keeps its own slab workspace until then).  Measured at B = 64: 10.42 ms/step ungrouped, 10.43 / 10.45 /
-    # 10.46 / 10.50 for g = 2 / 3 / 6 / 10 -- the launches saved do not pay for the larger live slab footprint.  Default: off.
-    wgrad_group = int(os.environ.get("AB_WGRAD_GROUP", "1"))
-
-    # bf16x3, AB_WGRAD_FUSE=g (default 8, the kernel's maximum -- and never more problems than one round of workgroups holds: 4 on layer 4;
-    # 1: off): up to g consecutive SAME-SHAPE 3x3 / stride-1 weight gradients of the backward (a stage's
-    # blocks: layer 1 has 6 of one shape, layers 2 - 4 have 7 / 11 / 5) run as ONE slab launch + ONE reduction (ab_conv2d_wgrad_x3_group).
-    # At one workgroup per CU every launch writes 256 partial tiles of 147 KB (37.7 MB) and the reduction reads them back: per LAYER before,
-    # per GROUP now, and a workgroup's band pipeline ramps up once per group.  The deferred layers' operand planes are kept until the group
-    # is launched (a shape change, a full group, or the end of a backward stage: _wgrad_join); gradients are complete only after that.
-    # tools/bench_conv_x3.py "probe grp": 72 -> 56 -> 53 us per layer on layer 2 for groups of 1 / 2 / 4, 66 -> 53 -> 48 on layer 3.
-    # The step, same box, alternating processes: 8.68 ms ungrouped -> 8.47 (g = 2); 8.91 (2) -> 8.78 (4) on another; 8.69 (4) -> 8.63 (8).
-    wgrad_fuse = int(os.environ.get("AB_WGRAD_FUSE", "8"))
-
-    def _wgrad_group_flush(self):
-        items, self._wgrp = getattr(self, "_wgrp", None), None
-        if not items:
-            return
-        if len(items) == 1:
-            x, dy, out = items[0]
-            K.conv2d_wgrad_x3(x, dy, 3, 3, 1, 1, out=out)
-        else:
-            K.conv2d_wgrad_x3_group(items)
-
-    def _wgrad_side(self, fn, *args, **kw):
-        if (self.x3 and self.wgrad_fuse > 1 and not self.overlap_wgrad and not self.wgrad_1pass and fn == self._conv_wgrad
-                and len(args) == 6 and tuple(args[2:6]) == (3, 3, 1, 1) and set(kw) == {"out"} and kw["out"] is not None):
-            xp, dp = K._planes(args[0]), K._planes(args[1])          # (split now: the planes, not the fp32 tensors, are what is kept)
-            key = (tuple(xp[0].shape), tuple(dp[0].shape))
-            ok = self.__dict__.setdefault("_wgrp_ok", {})
-            if key not in ok:          # the largest group of this shape the kernel takes in one round of workgroups (0: none)
-                ok[key] = next((G for G in range(min(self.wgrad_fuse, K.WGRAD_GROUP_MAX), 1, -1) if K.conv2d_wgrad_x3_group_ok(xp, dp, G)), 0)
-            if ok[key]:
-                pend = getattr(self, "_wgrp", None)
-                if pend and (tuple(pend[0][0][0].shape), tuple(pend[0][1][0].shape)) != key:
-                    self._wgrad_group_flush()
-                    pend = None
-                if not pend:
-                    pend = self._wgrp = []
-                pend.append((xp, dp, kw["out"]))
-                if len(pend) >= ok[key]:
-                    self._wgrad_group_flush()
-                return kw["out"]
-        if not self.overlap_wgrad:
-            grouped = self.x3 and self.wgrad_group > 1
-            if (self.batch_wgrad_reduce and not self.x3) or grouped:
-                if getattr(self, "_pending", None) is None:
-                    self._pending = K.PendingReductions()
-                kw["defer"] = self._pending
-                r = fn(*args, **kw)
-                if grouped and len(self._pending.descs) >= self.wgrad_group:
-                    self._pending.flush()
-                return r
-            return fn(*args, **kw)
-        if getattr(self, "_wg_stream", None) is None:
-            self._wg_stream = torch.cuda.Stream(device=self.p.device)
-            self._wg_keep = []
-        main = torch.cuda.current_stream(self.p.device)
-        self._wg_stream.wait_stream(main)
-        with torch.cuda.stream(self._wg_stream):
-            fn(*args, **kw)
-        self._wg_keep.append(args)
-
-    def _wgrad_join(self):
-        self._wgrad_group_flush()
-        if getattr(self, "_pending", None) is not None:
-            self._pending.flush()
-        if getattr(self, "_wg_stream", None) is not None:
-            torch.cuda.current_stream(self.p.device).wait_stream(self._wg_stream)
-            self._wg_keep.clear()
-
     BWD_STAGES = 3
 
     def grad_stage_ranges(self):
@@ -907,7 +842,7 @@ class HybridNet:
         # ---- box head (f32)
         g_mean = None
         if p.box_head:
-            g3 = getattr(self, "_g3", None)      # padded copy of g_box6d: columns 6.. are zeroed once, only the six live ones are rewritten
+            g3 = self._g3      # padded copy of g_box6d: columns 6.. are zeroed once, only the six live ones are rewritten
             if g3 is None or g3.shape[0] != N or g3.device != p.device:
                 g3 = self._g3 = torch.zeros((N, BOX_OUT_PAD), dtype=torch.float32, device=p.device)
             g3[:, :6].copy_(g_box6d)
@@ -928,18 +863,18 @@ class HybridNet:
             K.col_sum(dlogits, gv(hp + ".final_layer.bias"))
             if self.x3:
                 dlogits = K.split(dlogits)        # one split serves the weight and the data gradient
-        self._wgrad_side(self._conv_wgrad, e2, dlogits, 1, 1, 1, 0, out=gv(hp + ".final_layer.weight"))
+        self._wgrad(e2, dlogits, 1, 1, 1, 0, out=gv(hp + ".final_layer.weight"))
         # (bf16x3: the ReLU mask + BatchNorm-backward reduction of the deconvolution below ride in the data gradient's epilogue)
         de2, part2 = self._conv_dgrad(dlogits, hp + ".final_layer.weight", (e2.shape[-3], e2.shape[-2]), 1, 0,
                                       bn=(S["d2"], None, S["bnpd2"])) if self.x3 else (
             self._conv_dgrad(dlogits, hp + ".final_layer.weight", (e2.shape[-3], e2.shape[-2]), 1, 0), None)
         dd2 = self._bn_bwd(de2, e2, S["d2"], S["bnpd2"], gv(hp + ".deconv_layers.4.weight"),
                        gv(hp + ".deconv_layers.4.bias"), relu="recompute", part=part2)
-        self._wgrad_side(self._conv_wgrad, dd2, e1, 4, 4, 2, 1, out=gv(hp + ".deconv_layers.3.weight"))
+        self._wgrad(dd2, e1, 4, 4, 2, 1, out=gv(hp + ".deconv_layers.3.weight"))
         de1 = self._conv_fwd(dd2, hp + ".deconv_layers.3.weight", 2, 1)
         dd1 = self._bn_bwd(de1, e1, S["d1"], S["bnpd1"], gv(hp + ".deconv_layers.1.weight"),
                        gv(hp + ".deconv_layers.1.bias"), relu="recompute")
-        self._wgrad_side(self._conv_wgrad, dd1, feat, 4, 4, 2, 1, out=gv(hp + ".deconv_layers.0.weight"))
+        self._wgrad(dd1, feat, 4, 4, 2, 1, out=gv(hp + ".deconv_layers.0.weight"))
         dout = self._conv_fwd(dd1, hp + ".deconv_layers.0.weight", 2, 1)
         if g_mean is not None:
             K.avgpool_bwd(g_mean, dout, accumulate=True)
@@ -968,22 +903,22 @@ class HybridNet:
             fz = self._frozen(pre)
             dy2, dz = self._bn_bwd(dout, rec["out"], rec["y2"], rec["bnp2"], gv(pre + ".bn2.weight"), gv(pre + ".bn2.bias"),
                                relu=True, want_dz=True, part=dout_part, frozen=fz)
-            self._wgrad_side(self._conv_wgrad, rec["a1"], dy2, 3, 3, 1, 1, out=gv(pre + ".conv2.weight"))
+            self._wgrad(rec["a1"], dy2, 3, 3, 1, 1, out=gv(pre + ".conv2.weight"))
             # the BN-backward reduction of bn1 rides in the epilogue of the data gradient that produces its input
             da1, part1 = self._conv_dgrad(dy2, pre + ".conv2.weight", (dy2.shape[-3], dy2.shape[-2]), 1, 1,
                                           bn=(rec["y1"], None, rec["bnp1"]))
             dy1 = self._bn_bwd(da1, rec["a1"], rec["y1"], rec["bnp1"], gv(pre + ".bn1.weight"), gv(pre + ".bn1.bias"),
                             relu="recompute", part=part1, frozen=fz)
-            self._wgrad_side(self._conv_wgrad, x, dy1, 3, 3, stride, 1, out=gv(pre + ".conv1.weight"))
+            self._wgrad(x, dy1, 3, 3, stride, 1, out=gv(pre + ".conv1.weight"))
             bn_below = (nxt["y2"], nxt["out"], nxt["bnp2"]) if nxt is not None else None
             if rec["ds"]:
                 dyd = self._bn_bwd(dz, None, rec["yd"], rec["bnpd"], gv(pre + ".downsample.1.weight"),
                                gv(pre + ".downsample.1.bias"), relu=False, frozen=fz)
-                self._wgrad_side(self._conv_wgrad, x, dyd, 1, 1, stride, 0, out=gv(pre + ".downsample.0.weight"))
-                if self.x3 and stride == 2 and self.pair_dgrad:      # both branches in one launch (the 1x1 as a tap of the 3x3/s2)
+                self._wgrad(x, dyd, 1, 1, stride, 0, out=gv(pre + ".downsample.0.weight"))
+                if self.x3 and stride == 2:      # both branches in one launch (the 1x1 as a tap of the 3x3/s2)
                     # ... and the BatchNorm-backward mask + reduction of the stage below in its epilogue (convp.hip)
                     dout = K.conv2d_dgrad_x3_pair(dy1, self.tr[pre + ".conv1.weight"], dyd, self.tr[pre + ".downsample.0.weight"],
-                                                  (x.shape[-3], x.shape[-2]), 1, bn=bn_below if self.pair_dgrad_bn else None)
+                                                  (x.shape[-3], x.shape[-2]), 1, bn=bn_below)
                     dout, dout_part = dout if isinstance(dout, tuple) else (dout, None)
                 else:
                     dx = self._conv_dgrad(dy1, pre + ".conv1.weight", (x.shape[-3], x.shape[-2]), stride, 1)
@@ -1001,27 +936,16 @@ class HybridNet:
         gv = self.p.gview
         dout, _ = self._backward_blocks(dout, blocks, dout_part)
         # ---- stem
-        dy0 = None
-        if self.frozen_bn:      # frozen stem BatchNorm: max-pool backward, then the apply pass with zero partial sums (no fused reduction)
-            y0 = S["y0"]
-            da0 = K.maxpool_bwd(S["pool_idx"], dout, (y0.shape[1], y0.shape[2]))
-            dy0 = self._bn_bwd(da0, None, y0, S["bnp0"], gv("backbone.bn1.weight"), gv("backbone.bn1.bias"), relu="recompute", frozen=True)
-        elif self.x3 and self.fuse_stem and self.stem_pool_reduce:
-            # the max-pool backward pass also masks and reduces for the stem BatchNorm (AB_STEM_POOL_REDUCE=0: separate passes)
-            dy0 = K.bn_relu_maxpool_bwd_x3(dout, S["pool_idx"], S["y0"], S["bnp0"], gv("backbone.bn1.weight"), gv("backbone.bn1.bias"),
+        y0, dy0 = S["y0"], None
+        if self.x3 and not self.frozen_bn:
+            # the max-pool backward pass also masks and reduces for the stem BatchNorm, over the pooled elements where the forward
+            # kept the winners; None: a shape the kernel does not take
+            dy0 = K.bn_relu_maxpool_bwd_x3(dout, S["pool_idx"], y0, S["bnp0"], gv("backbone.bn1.weight"), gv("backbone.bn1.bias"),
                                            ywin=S.get("pool_ywin"))
-        if dy0 is not None:
-            pass
-        elif self.fuse_stem_bwd:
-            dy0 = K.bn_relu_maxpool_bwd(dout, S["pool_idx"], S["y0"], S["bnp0"], gv("backbone.bn1.weight"), gv("backbone.bn1.bias"))
-        else:
-            y0 = S["y0"]
+        if dy0 is None:      # bf16 / f32, and the frozen stem BatchNorm (the apply pass with zero partial sums): separate passes
             da0 = K.maxpool_bwd(S["pool_idx"], dout, (y0.shape[1], y0.shape[2]))
-            dy0 = self._bn_bwd(da0, None, y0, S["bnp0"], gv("backbone.bn1.weight"), gv("backbone.bn1.bias"), relu="recompute")
-        H, W = S["HW"]
-        if self.x3 and self.wgrad_1pass:
-            self._wgrad_side(K.conv2d_stem_wgrad, K._planes(S["xpad"])[0], K._planes(dy0)[0], H, W, out=gv("backbone.conv1.weight"))
-        else:
-            self._wgrad_side(K.conv2d_stem_wgrad_x3 if self.x3 else K.conv2d_stem_wgrad, S["xpad"], dy0, H, W, out=gv("backbone.conv1.weight"))
+            dy0 = self._bn_bwd(da0, None, y0, S["bnp0"], gv("backbone.bn1.weight"), gv("backbone.bn1.bias"), relu="recompute",
+                               frozen=self.frozen_bn)
+        self._stem_wgrad(S["xpad"], dy0, *S["HW"], out=gv("backbone.conv1.weight"))
         self._wgrad_join()
         self.saved = None

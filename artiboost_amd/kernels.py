@@ -558,6 +558,16 @@ def conv2d_dgrad_x3_affine(dy, wt_split, in_hw, stride, pad, bnp, relu=True):
     return sp
 
 
+def _relu_mask(bn_out):
+    """The ReLU mask of the fused BatchNorm-backward epilogues: the hi plane of the stored activation `bn_out` (split planes, or an fp32
+    tensor that carries them as `_ab_split`) -> (mask, True); (None, True) when there is no activation to mask with (the epilogue
+    recomputes relu(bn(y))); (None, False) when the activation was kept without its planes and the epilogue cannot be used."""
+    if bn_out is None:
+        return None, True
+    sp = bn_out if bn_out.dtype == torch.bfloat16 else getattr(bn_out, "_ab_split", None)
+    return (None, False) if sp is None else (sp[0], True)
+
+
 def conv2d_dgrad_x3(dy, wt_split, in_hw, stride, pad, addend=None, want_stats=False, bn=None):
     """dy: fp32 / split [.., N,Ho,Wo,Cout]; wt_split [2,Cin,kh,kw,Cout] -> dx fp32 [N,H,W,Cin] (+ BN partials of dx).
 
@@ -574,14 +584,8 @@ def conv2d_dgrad_x3(dy, wt_split, in_hw, stride, pad, addend=None, want_stats=Fa
     if bn is not None:
         bn_y, bn_out, bnp = bn
         rows = lib.ab_conv2d_dgrad_x3_bn_rows(L.i(N), L.i(H), L.i(W), L.i(Cin), L.i(Cout), L.i(kh), L.i(kw), L.i(stride), L.i(pad))
-        mask = None
-        if bn_out is not None:
-            sp = bn_out if bn_out.dtype == torch.bfloat16 else getattr(bn_out, "_ab_split", None)
-            if sp is None:
-                rows = 0                   # the mask is read from the hi plane of the stored activation
-            else:
-                mask = sp[0]
-        if rows > 0:
+        mask, has_mask = _relu_mask(bn_out)
+        if rows > 0 and has_mask:
             part = torch.empty((rows, Cin, 2), dtype=torch.float32, device=dh.device)
             L.check(lib.ab_conv2d_dgrad_x3_bn(L.ptr(dh), L.ptr(dl), L.ptr(wt_split[0]), L.ptr(wt_split[1]), L.ptr(dx), L.i(N),
                                               L.i(H), L.i(W), L.i(Cin), L.i(Cout), L.i(kh), L.i(kw), L.i(stride), L.i(pad),
@@ -617,14 +621,8 @@ def conv2d_dgrad_x3_pair(dy, wt_split, dy2, wt2_split, in_hw, pad, addend=None, 
     if bn is not None and addend is None:
         bn_y, bn_out, bnp = bn
         rows = lib.ab_conv2d_dgrad_x3_pair_bn_rows(L.i(N), L.i(H), L.i(W), L.i(Cin), L.i(Cout), L.i(kh), L.i(kw), L.i(pad))
-        mask = None
-        if bn_out is not None:
-            sp = bn_out if bn_out.dtype == torch.bfloat16 else getattr(bn_out, "_ab_split", None)
-            if sp is None:
-                rows = 0                   # the mask is read from the hi plane of the stored activation
-            else:
-                mask = sp[0]
-        if rows > 0:
+        mask, has_mask = _relu_mask(bn_out)
+        if rows > 0 and has_mask:
             part = torch.empty((rows, Cin, 2), dtype=torch.float32, device=dh.device)
             L.check(lib.ab_conv2d_dgrad_x3_pair_bn(L.ptr(dh), L.ptr(dl), L.ptr(wt_split[0]), L.ptr(wt_split[1]), L.ptr(eh), L.ptr(el),
                                                    L.ptr(wt2_split[0]), L.ptr(wt2_split[1]), L.ptr(dx), L.i(N), L.i(H), L.i(W), L.i(Cin),
