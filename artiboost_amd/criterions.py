@@ -549,3 +549,106 @@ class FusedPoseCriterion:
         if self.sym is not None:
             d["sym_corners_3d_loss"] = self.out["sym_loss"].cpu()[0]
         return d
+
+
+class FusedRegCriterion:
+    """The regression-based model's criterion in ONE HIP kernel (ab_reg_pose_loss, csrc/pose_loss.hip): HOPRegNet's assembly
+    (hpregnet.mano_outputs / object_outputs: joints + the target's root, corners = R(transf[3:9]) can + root + transf[0:3]) +
+    ManoLoss + JointsLoss + HandOrdLoss + SceneOrdLoss + per-sample EPE + backward down to MANO's joints, the PCA pose, the shape
+    and the nine TransHead values.  Built from a `Criterion` whose list is any subset of those four containing ManoLoss; uses that
+    criterion's draw buffers, so the host RNG stream is the reference's.  The hand-vertex term needs a `hand_verts_3d` target:
+    a batch that carries one under a non-zero LAMBDA_HAND_VERTS_3D is refused (the registry losses then run instead)."""
+
+    LOSS_WIDTH = 16          # floats of the kernel's loss vector
+
+    def __init__(self, criterion: Criterion, ncomps, example_batch=None):
+        import ctypes
+        self.crit = criterion
+        self.ncomps = int(ncomps)
+        w = [0.0] * 12
+        self.mano = self.hand = self.scene = None
+        # key -> slot of the loss vector (None: the registry route reports None), in the registry's own update order
+        d = {}
+        for loss in criterion.loss_list:
+            lam = float(criterion.loss_lambdas[type(loss).__name__])
+            if isinstance(loss, ManoLoss):
+                if self.mano is not None:
+                    raise NotImplementedError("two ManoLoss entries")
+                self.mano = loss
+                w[8], w[9], w[10], w[11] = loss.lambda_shape_reg, loss.lambda_pose_reg, loss.lambda_joints_3d, lam
+                d.update(mano_shape=8 if loss.lambda_shape_reg else None, mano_pca_pose=9 if loss.lambda_pose_reg else None,
+                         joints_3d_loss=10 if loss.lambda_joints_3d else None, hand_verts_3d_loss=None)
+            elif isinstance(loss, JointsLoss):
+                w[0], w[1], w[5] = float(loss.lambda_joints_3d), float(loss.lambda_corners_3d), lam
+                d.update({"joints_3d_loss": 0 if loss.lambda_joints_3d else None, "corners_3d_loss": 1 if loss.lambda_corners_3d else None,
+                          loss.output_key: 11})
+            elif isinstance(loss, HandOrdLoss):
+                w[2], w[3], w[6] = loss.lambda_joint_lev, loss.lambda_part_lev, lam
+                self.hand = loss
+                d.update({"joint_ord_loss": 2, "part_ord_loss": 3, loss.output_key: 12})
+            elif isinstance(loss, SceneOrdLoss):
+                w[4], w[7] = loss.lambda_scene_lev, lam
+                self.scene = loss
+                d["scene_ord_loss"] = 4
+            else:
+                raise NotImplementedError(f"{type(loss).__name__} is not part of the fused regbased criterion")
+        if self.mano is None:
+            raise NotImplementedError("the fused regbased criterion needs ManoLoss in the list")
+        if self.mano.lambda_hand_verts_3d and example_batch is not None and "hand_verts_3d" in example_batch:
+            raise NotImplementedError("ManoLoss's hand-vertex term (a hand_verts_3d target with LAMBDA_HAND_VERTS_3D != 0)")
+        d["final_loss"] = 5
+        self.key_slots = d
+        # the vector's layout: the dict key each slot is reported under (None: not an entry of the loss dict)
+        keys = [None] * self.LOSS_WIDTH
+        for k, s in d.items():
+            if s is not None:
+                keys[s] = k
+        self.LOSS_KEYS = tuple(keys)
+        self.weights = (ctypes.c_float * 12)(*[float(x) for x in w])
+        self.out = None
+
+    def draw(self, dev):
+        self.crit.draw(dev)
+
+    def _alloc(self, B, dev):
+        z = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)   # noqa: E731
+        self.out = dict(joints_3d_abs=z(B, 21, 3), corners_3d_abs=z(B, 8, 3), box_rot_rotmat=z(B, 3, 3), sample_part=z(B, 8),
+                        losses=z(self.LOSS_WIDTH), g_joints=z(B, 21, 3), g_pose=z(B, 3 + self.ncomps), g_shape=z(B, 10), g_transf=z(B, 9))
+
+    def __call__(self, joints_3d, mano_pca_pose, mano_shape, transf, targs, backward=True, g_transf=None):
+        """joints_3d [B,21,3] (MANO's, root-relative), mano_pca_pose [B,3+ncomps], mano_shape [B,10] f32 contiguous; transf: f32 rows
+        whose first nine values are translation | 6-D rotation (any row pitch >= 9).  g_transf: a buffer of transf's pitch to receive
+        its gradient (default: the criterion's own [B,9] when transf is [B,9])."""
+        from . import _lib as L
+        if "hand_verts_3d" in targs and self.mano.lambda_hand_verts_3d:
+            raise NotImplementedError("ManoLoss's hand-vertex term (a hand_verts_3d target with LAMBDA_HAND_VERTS_3D != 0)")
+        B, dev = joints_3d.shape[0], joints_3d.device
+        if mano_pca_pose.shape[1] != 3 + self.ncomps:
+            raise ValueError(f"mano_pca_pose has {mano_pca_pose.shape[1]} columns, ncomps = {self.ncomps}")
+        if self.out is None or self.out["g_joints"].shape[0] != B or self.out["g_joints"].device != dev:
+            self._alloc(B, dev)
+        o = self.out
+        stride = transf.stride(0)
+        gt = g_transf if g_transf is not None else o["g_transf"]
+        if backward and (gt.stride(0) != stride or transf.stride(1) != 1 or gt.stride(1) != 1):
+            raise ValueError("g_transf must have transf's row pitch")
+        hb = self.hand.draws.bufs if self.hand is not None else {}
+        sb = self.scene.draws.bufs if self.scene is not None else {}
+        t = lambda k: targs[k]   # noqa: E731
+        L.check(L.lib().ab_reg_pose_loss(
+            L.ptr(joints_3d), L.ptr(mano_pca_pose), L.ptr(mano_shape), L.view_ptr(transf), L.i(stride),
+            L.ptr(t(Queries.ROOT_JOINT)), L.ptr(t(Queries.CAM_INTR)), L.ptr(t(Queries.CORNERS_CAN)), L.ptr(t(Queries.JOINTS_3D)),
+            L.ptr(t(Queries.CORNERS_3D)), L.ptr(t(Queries.JOINTS_VIS)), L.ptr(t(Queries.CORNERS_VIS)),
+            L.ptr(hb.get("views")), L.i(hb["views"].shape[0] if hb else 0), L.ptr(hb.get("j0")), L.ptr(hb.get("j1")),
+            L.i(hb["j0"].numel() if hb else 0), L.ptr(hb.get("p0")), L.ptr(hb.get("p1")), L.i(hb["p0"].numel() if hb else 0),
+            L.ptr(sb.get("views")), L.i(sb["views"].shape[0] if sb else 0), L.ptr(sb.get("i0")), L.ptr(sb.get("i1")),
+            L.i(sb["i0"].numel() if sb else 0), L.i(B), L.i(self.ncomps), self.weights,
+            L.ptr(o["joints_3d_abs"]), L.ptr(o["corners_3d_abs"]), L.ptr(o["box_rot_rotmat"]), L.ptr(o["sample_part"]), L.ptr(o["losses"]),
+            L.ptr(o["g_joints"] if backward else None), L.ptr(o["g_pose"] if backward else None), L.ptr(o["g_shape"] if backward else None),
+            L.view_ptr(gt if backward else None), L.stream()), "ab_reg_pose_loss")
+        return o
+
+    def losses_dict(self):
+        """Host view of the loss scalars of the last call under the keys of Criterion.compute_losses (synchronises)."""
+        v = self.out["losses"].cpu()
+        return {k: (None if s is None else v[s]) for k, s in self.key_slots.items()}

@@ -55,6 +55,14 @@ struct PoseLossArgs {
     float* sample_part;     // [B,8] per-sample loss partial sums + EPE: Lj, Lc, jo, po, so, epe_j_mm, epe_c_mm, -
     float* g_kp3d;          // [B,22,3]   (may be NULL: forward only)
     float* g_box6d;         // [B,6]
+    // regression-based assembly (pose_loss_kernel<1>, ab_reg_pose_loss): kp3d = MANO's root-relative joints [B,21,3], box6d = transf rows
+    // (translation 3 | 6-D rotation, pitch box_stride), g_kp3d = g_joints [B,21,3], g_box6d = g_transf (pitch box_stride)
+    const float* mano_pose;    // [B,3+ncomps]
+    const float* mano_shape;   // [B,10]
+    int ncomps;
+    float lam_shape_reg, lam_pose_reg, lam_mano_joints, w_mano;   // inside ManoLoss, and its Criterion LAMBDA
+    float* g_pose;             // [B,3+ncomps]
+    float* g_shape;            // [B,10]
 };
 
 __device__ __forceinline__ void cross3(const float* a, const float* b, float* o) {
@@ -70,7 +78,11 @@ __constant__ int c_parents[21] = {0, 0, 1, 2, 3, 0, 5, 6, 7, 0, 9, 10, 11, 0, 13
 // the views of a pair spread over 4 (hand) or 8 (scene) adjacent lanes, whose gradient partials are combined by a fixed
 // butterfly; the deterministic gradient gathers split each pair list in sixteen fixed ranges, summed in wave order.  As a
 // single wave the kernel was a 75 us chain of dependent LDS / transcendental latencies (~800 cycles per view).
+// REG = 1: the regression-based assembly of HOPRegNet (anakin/models/hpregnet.py:112-147) in front of the same losses -- joints = MANO's
+// joints + the TARGET's root, corners = R(transf[3:9]) * can + root + transf[0:3] -- plus ManoLoss (criterions/honetloss.py:12-73): the
+// unmasked joint MSE per sample in sample_part[:, 7] and the gradients of the two regularisers; their sums are pose_loss_finalize<1>'s.
 #define PL_WAVES 16
+template <int REG>
 __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a) {
     const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, l64 = tid & 63;
     const int lane = wave == 0 ? tid : 1 << 20;
@@ -94,6 +106,8 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
     // is one wave per sample, and as ~30 dependent load -> wait -> use rounds it was a 75 us latency chain.
     __shared__ uint8_t ij0[PL_MAXPAIR], ij1[PL_MAXPAIR], ip0[PL_MAXPAIR], ip1[PL_MAXPAIR], is0[PL_MAXPAIR], is1[PL_MAXPAIR];
     __shared__ float kp[66], Kc[9], CAN[8][3], J3[63], C3[24], RJ[3];
+    __shared__ float tvec[3];         // REG: the object's translation (transf[0:3])
+    float r_pose = 0.f, r_shape = 0.f;
     // unconditional loads (index clamped, absent tables redirected to a valid address), conditional LDS writes: branches
     // around the loads would put each one in its own basic block with its own s_waitcnt
     if (wave == 0) {
@@ -113,14 +127,20 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
         const int i = lane + it * 64;
         rhv[it] = ld(a.hand_views, i, a.nvh * 3); rsv[it] = ld(a.scene_views, i, a.nvs * 3);
     }
-    const float r_kp = a.kp3d[(long)b * 66 + lane], r_kp2 = a.kp3d[(long)b * 66 + 64 + (lane & 1)];
+    const float r_kp = REG ? a.kp3d[(long)b * 63 + (lane < 63 ? lane : 0)] : a.kp3d[(long)b * 66 + lane];
+    const float r_kp2 = REG ? 0.f : a.kp3d[(long)b * 66 + 64 + (lane & 1)];
     const float r_K = a.cam_intr[(long)b * 9 + (lane < 9 ? lane : 0)];
     const int l24 = lane < 24 ? lane : 0;
     const float r_can = a.corners_can[(long)b * 24 + l24], r_c3 = a.corners_3d[(long)b * 24 + l24];
     const float r_j3 = a.joints_3d[(long)b * 63 + (lane < 63 ? lane : 0)];
     const float r_rj = a.root_joint[b * 3 + (lane < 3 ? lane : 0)];
     const float r_vj = a.joints_vis[b * 21 + (lane < 21 ? lane : 0)], r_vc = a.corners_vis[b * 8 + (lane & 7)];
-    const float r_box = a.box6d[(long)b * a.box_stride + (lane < 6 ? lane : 0)];
+    const float r_box = a.box6d[(long)b * a.box_stride + (lane < (REG ? 9 : 6) ? lane : 0)];
+    if constexpr (REG) {
+        const int P_ = 3 + a.ncomps;
+        r_pose = a.mano_pose[(long)b * P_ + (lane < P_ ? lane : 0)];
+        r_shape = a.mano_shape[(long)b * 10 + (lane < 10 ? lane : 0)];
+    }
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
         const int i = lane + it * 64;
@@ -139,15 +159,24 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
     if (lane < 9) Kc[lane] = r_K;
     if (lane < 24) { (&CAN[0][0])[lane] = r_can; C3[lane] = r_c3; }
     if (lane < 63) J3[lane] = r_j3;
-    if (lane < 3) { RJ[lane] = r_rj; avec[lane] = r_box; }
-    else if (lane < 6) bvec[lane - 3] = r_box;
+    if constexpr (REG) {
+        if (lane < 3) { RJ[lane] = r_rj; tvec[lane] = r_box; }
+        else if (lane < 6) avec[lane - 3] = r_box;
+        else if (lane < 9) bvec[lane - 6] = r_box;
+    } else {
+        if (lane < 3) { RJ[lane] = r_rj; avec[lane] = r_box; }
+        else if (lane < 6) bvec[lane - 3] = r_box;
+    }
     if (lane < 21) vj[lane] = r_vj;
     if (lane < 8) vc[lane] = r_vc;
     }
     __syncthreads();
     const float fx = Kc[0], fy = Kc[4], cx = Kc[2], cy = Kc[5], rootz = RJ[2];
     // ---- uvd -> xyz (transform.py:512-546)
-    if (lane < 22) {
+    if constexpr (REG) {      // hpregnet.py:112-147: joints + the target's root; P[21] = the object's centre
+        if (lane < 63) P[lane / 3][lane % 3] = kp[lane] + RJ[lane % 3];
+        if (lane < 3) P[21][lane] = RJ[lane] + tvec[lane];
+    } else if (lane < 22) {
         float u = kp[lane * 3], v = kp[lane * 3 + 1], d = kp[lane * 3 + 2];
         float z = (d - 0.5f) * a.depth_range + rootz;
         P[lane][0] = (u * a.res_w - cx) / fx * z;
@@ -336,6 +365,15 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
         else { for (int k = 0; k < 8; ++k) { float d[3] = {C[k][0] - TC[k][0], C[k][1] - TC[k][1], C[k][2] - TC[k][2]}; s += sqrtf(dot3(d, d)); } s = s / 8.f * 1000.f; }
         a.sample_part[(long)b * 8 + lane] = s;
     }
+    if constexpr (REG) {      // ManoLoss's joint term: unmasked squared error of the sample (honetloss.py:49-53)
+        if (wave == 0) {
+            const float d = l64 < 63 ? P[l64 / 3][l64 % 3] - T[l64 / 3][l64 % 3] : 0.f;
+            float v = d * d;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            if (l64 == 0) a.sample_part[(long)b * 8 + 7] = v;
+        }
+    }
     if (!a.g_kp3d) return;
     // ---- backward, deterministic gather
     // every wave scans its sixteenth of each pair list, branch-free (selects, so the LDS loads pipeline); partials are summed
@@ -385,6 +423,7 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
         if (k >= 1) s += gpart[k - 1][i];
         for (int c = 1; c < 21; ++c) if (c_parents[c] == k) s -= gpart[c - 1][i];
         gP[k][i] = s * vj[k];
+        if constexpr (REG) gP[k][i] += a.w_mano * a.lam_mano_joints * 2.f / nJ * (P[k][i] - T[k][i]);
     }
     if (lane < 24) {
         int c = lane / 3, i = lane % 3;
@@ -401,7 +440,13 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
         gP[21][lane] = s;
     }
     __syncthreads();
-    if (lane < 22) {     // xyz -> uvd
+    if constexpr (REG) {
+        const int P_ = 3 + a.ncomps;
+        if (lane < 63) a.g_kp3d[(long)b * 63 + lane] = gP[lane / 3][lane % 3];       // joints_3d_abs = joints_3d + root
+        if (lane < 3) a.g_box6d[(long)b * a.box_stride + lane] = gP[21][lane];       // centre = root + transf[0:3]
+        if (lane < P_) a.g_pose[(long)b * P_ + lane] = lane < 3 ? 0.f : a.w_mano * a.lam_pose_reg * 2.f / (B_ * (float)a.ncomps) * r_pose;
+        if (lane < 10) a.g_shape[(long)b * 10 + lane] = a.w_mano * a.lam_shape_reg * 2.f / (B_ * 10.f) * r_shape;
+    } else if (lane < 22) {     // xyz -> uvd
         float u = kp[lane * 3], v = kp[lane * 3 + 1];
         float z = P[lane][2];
         float gx = gP[lane][0], gy = gP[lane][1], gz = gP[lane][2];
@@ -427,12 +472,14 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
         float gb[3]; cross3(gzr, xh, gb);
         float dx = dot3(xh, gx), ga[3];
         for (int i = 0; i < 3; ++i) ga[i] = (gx[i] - xh[i] * dx) / an;        // x = a / |a|
-        float* o = a.g_box6d + (long)b * 6;
+        float* o = REG ? a.g_box6d + (long)b * a.box_stride + 3 : a.g_box6d + (long)b * 6;
         o[0] = ga[0]; o[1] = ga[1]; o[2] = ga[2]; o[3] = gb[0]; o[4] = gb[1]; o[5] = gb[2];
     }
 }
 
 // losses[8]: joints_3d_loss, corners_3d_loss, joint_ord_loss, part_ord_loss, scene_ord_loss, final_loss, mean epe_j, mean epe_c
+// REG: losses[16], + [8] mano_shape, [9] mano_pca_pose, [10] ManoLoss's joints_3d_loss, [11] joints_loss_output, [12] hand_ord_loss_output
+template <int REG>
 __global__ __launch_bounds__(64) void pose_loss_finalize(const float* __restrict__ sample_part, PoseLossArgs a, float* __restrict__ losses) {
     const int lane = threadIdx.x;
     // column sums over the batch in double: lane-strided partials (independent loads), then a butterfly in fixed order
@@ -444,6 +491,14 @@ __global__ __launch_bounds__(64) void pose_loss_finalize(const float* __restrict
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
         col[c] = s;
+    }
+    double reg_s = 0.0, reg_p = 0.0;
+    if constexpr (REG) {      // the two regularisers: mean(shape^2), mean(pose[:, 3:]^2), same fixed order
+        const int P_ = 3 + a.ncomps;
+        for (int i = lane; i < a.B * 10; i += 64) { const double x = (double)a.mano_shape[i]; reg_s += x * x; }
+        for (int i = lane; i < a.B * P_; i += 64) { const double x = (i % P_) >= 3 ? (double)a.mano_pose[i] : 0.0; reg_p += x * x; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { reg_s += __shfl_xor(reg_s, o, 64); reg_p += __shfl_xor(reg_p, o, 64); }
     }
     if (lane != 0) return;
     const float B_ = (float)a.B;
@@ -465,6 +520,15 @@ __global__ __launch_bounds__(64) void pose_loss_finalize(const float* __restrict
     losses[5] = a.w_jointsloss * (a.lam_joints * v[0] + a.lam_corners * v[1]) +
                 a.w_handord * (a.lam_hand_joint * v[2] + a.lam_hand_part * v[3]) +
                 a.w_sceneord * (a.lam_scene * v[4]) + a.w_sym * (a.lam_sym * symv);
+    if constexpr (REG) {
+        const float ms = (float)(reg_s / (double)(B_ * 10.f)), mp = (float)(reg_p / (double)(B_ * (float)a.ncomps));
+        const float mj = (float)(col[7] / (double)(B_ * 63.f));
+        losses[8] = ms; losses[9] = mp; losses[10] = mj;
+        losses[11] = a.lam_joints * v[0] + a.lam_corners * v[1];
+        losses[12] = a.lam_hand_joint * v[2] + a.lam_hand_part * v[3];
+        losses[13] = losses[14] = losses[15] = 0.f;
+        losses[5] += a.w_mano * (a.lam_shape_reg * ms + a.lam_pose_reg * mp + a.lam_mano_joints * mj);
+    }
 }
 
 static int pose_loss_impl(const float* kp3d, const float* box6d, int box_stride, const float* root_joint,
@@ -500,13 +564,13 @@ static int pose_loss_impl(const float* kp3d, const float* box6d, int box_stride,
         a.sym_R = sym->R; a.sym_t = sym->t; a.obj_idx = sym->obj_idx; a.obj_transf = sym->obj_transf;
         a.symK = sym->K; a.lam_sym = sym->lambda; a.w_sym = sym->weight; a.sym_loss = sym->loss_out;
     }
-    pose_loss_kernel<<<B, PL_WAVES * 64, 0, as_stream(stream)>>>(a);
+    pose_loss_kernel<0><<<B, PL_WAVES * 64, 0, as_stream(stream)>>>(a);
     AB_LAUNCH_CHECK();
     // guard the normalisers of disabled losses
     PoseLossArgs f = a;
     if (f.njp == 0) { f.njp = 1; f.npp = 1; f.nvh = 1; }
     if (f.nsp == 0) { f.nsp = 1; f.nvs = 1; }
-    pose_loss_finalize<<<1, 64, 0, as_stream(stream)>>>(sample_part, f, losses);
+    pose_loss_finalize<0><<<1, 64, 0, as_stream(stream)>>>(sample_part, f, losses);
     AB_LAUNCH_CHECK();
     return 0;
 }
@@ -618,4 +682,47 @@ extern "C" int ab_pose_loss_sym(const float* kp3d, const float* box6d, int box_s
                           corners_vis, hand_views, nvh, j0, j1, njp, p0, p1, npp, scene_views, nvs, s0, s1, nsp, B, center_idx,
                           res_w, res_h, weights8_host, joints_abs, corners_abs, rotmat, uvd2d, sample_part, losses, g_kp3d,
                           g_box6d, stream, sym);
+}
+
+// ---- the regression-based model's criterion (HOPRegNet + [ManoLoss, JointsLoss, HandOrdLoss, SceneOrdLoss]): pose_loss_kernel<1>
+// weights12_host = {LAMBDA_JOINTS_3D, LAMBDA_CORNERS_3D, LAMBDA_JOINTS_LEVEL, LAMBDA_PART_LEVEL, LAMBDA_SCENE_LEVEL, LAMBDAS[JointsLoss],
+// LAMBDAS[HandOrdLoss], LAMBDAS[SceneOrdLoss], LAMBDA_SHAPE_REG, LAMBDA_POSE_REG, ManoLoss.LAMBDA_JOINTS_3D, LAMBDAS[ManoLoss]}.  An ordinal
+// loss is present exactly when its draw buffers are passed (its scalars are reported even under a zero weight, as the registry does).
+extern "C" int ab_reg_pose_loss(const float* joints_pred, const float* mano_pca_pose, const float* mano_shape, const float* transf,
+                                int transf_stride, const float* root_joint, const float* cam_intr, const float* corners_can,
+                                const float* joints_3d, const float* corners_3d, const float* joints_vis, const float* corners_vis,
+                                const float* hand_views, int nvh, const int64_t* j0, const int64_t* j1, int njp, const int64_t* p0,
+                                const int64_t* p1, int npp, const float* scene_views, int nvs, const int64_t* s0, const int64_t* s1,
+                                int nsp, int B, int ncomps, const float* weights12_host, float* joints_abs, float* corners_abs,
+                                float* rotmat, float* sample_part, float* losses, float* g_joints, float* g_pose, float* g_shape,
+                                float* g_transf, void* stream) {
+    if (!joints_pred || !mano_pca_pose || !mano_shape || !transf || !root_joint || !cam_intr || !corners_can || !joints_3d || !corners_3d ||
+        !joints_vis || !corners_vis || !weights12_host || !joints_abs || !corners_abs || !rotmat || !sample_part || !losses)
+        return AB_EINVAL;
+    if (g_joints && (!g_pose || !g_shape || !g_transf)) return AB_EINVAL;
+    if (B < 1 || ncomps < 1 || ncomps > 45 || transf_stride < 9) return AB_ESHAPE;
+    const bool hand = hand_views && j0 && j1 && p0 && p1 && nvh > 0, scene = scene_views && s0 && s1 && nvs > 0;
+    if (hand && (njp < 0 || npp < 0 || njp > PL_MAXPAIR || npp > PL_MAXPAIR || nvh > PL_MAXVIEW)) return AB_ESHAPE;
+    if (scene && (nsp < 0 || nsp > PL_MAXPAIR || nvs > PL_MAXVIEW)) return AB_ESHAPE;
+    const float* w = weights12_host;
+    PoseLossArgs a = {};
+    a.kp3d = joints_pred; a.box6d = transf; a.box_stride = transf_stride; a.root_joint = root_joint; a.cam_intr = cam_intr;
+    a.corners_can = corners_can; a.joints_3d = joints_3d; a.corners_3d = corners_3d; a.joints_vis = joints_vis; a.corners_vis = corners_vis;
+    if (hand) { a.hand_views = hand_views; a.j0 = j0; a.j1 = j1; a.p0 = p0; a.p1 = p1; a.nvh = nvh; a.njp = njp; a.npp = npp; }
+    if (scene) { a.scene_views = scene_views; a.s0 = s0; a.s1 = s1; a.nvs = nvs; a.nsp = nsp; }
+    a.B = B; a.res_w = a.res_h = 1.f; a.depth_range = 0.4f;
+    a.lam_joints = w[0]; a.lam_corners = w[1]; a.lam_hand_joint = w[2]; a.lam_hand_part = w[3]; a.lam_scene = w[4];
+    a.w_jointsloss = w[5]; a.w_handord = hand ? w[6] : 0.f; a.w_sceneord = scene ? w[7] : 0.f;
+    a.lam_shape_reg = w[8]; a.lam_pose_reg = w[9]; a.lam_mano_joints = w[10]; a.w_mano = w[11];
+    a.mano_pose = mano_pca_pose; a.mano_shape = mano_shape; a.ncomps = ncomps;
+    a.joints_abs = joints_abs; a.corners_abs = corners_abs; a.rotmat = rotmat; a.sample_part = sample_part;
+    a.g_kp3d = g_joints; a.g_box6d = g_transf; a.g_pose = g_pose; a.g_shape = g_shape;
+    pose_loss_kernel<1><<<B, PL_WAVES * 64, 0, as_stream(stream)>>>(a);
+    AB_LAUNCH_CHECK();
+    PoseLossArgs f = a;      // guard the normalisers of absent losses
+    if (!hand || f.njp == 0 || f.npp == 0) { f.njp = f.njp ? f.njp : 1; f.npp = f.npp ? f.npp : 1; f.nvh = f.nvh ? f.nvh : 1; }
+    if (!scene || f.nsp == 0) { f.nsp = 1; f.nvs = f.nvs ? f.nvs : 1; }
+    pose_loss_finalize<1><<<1, 64, 0, as_stream(stream)>>>(sample_part, f, losses);
+    AB_LAUNCH_CHECK();
+    return 0;
 }

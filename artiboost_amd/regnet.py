@@ -78,6 +78,8 @@ class HOPRegNetHIP(nn.Module):
                           "pass a converted checkpoint through ARCH.PRETRAINED")
         self.ncomps = int(head["NCOMPS"])
         self.P = 3 + self.ncomps
+        # ARCH.FUSED_STEP: true -- TrainStep runs this model without autograd (criterions.FusedRegCriterion) and replays the step as hipGraphs
+        self.FUSED_STEP = bool(cfg.get("FUSED_STEP", False))
         dev = cfg.get("DEVICE", "cuda")
         cd = cfg.get("COMPUTE_DTYPE", "bf16x3")
         self.store = ParamStore(device=dev, layers=BACKBONES[bb["TYPE"]][1], reg_heads=self.ncomps)

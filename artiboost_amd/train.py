@@ -111,7 +111,21 @@ class TrainStep:
         self.fused = None
         # the key of this model's outputs in Arch's result dict: its config TYPE (the class name can differ: HOPRegNet on the HIP kernels)
         self.model_key = next((t for t, v in getattr(arch_model, "models", {}).items() if v["id"] == 0), type(self.hb).__name__)
-        if not getattr(self.hb, "HAS_BOX_HEAD", True):               # SimpleBaseline: the fused pose/loss kernel is HybridBaseline's assembly
+        # HOPRegNet built with ARCH.FUSED_STEP: its own fused criterion (ab_reg_pose_loss) and two linear graphs; the trunk-only layout has no
+        # staged backward, so with a process group the unsplit schedule applies (all-reduce between the two graphs)
+        self.reg = bool(getattr(self.hb, "FUSED_STEP", False))
+        if self.reg:
+            self.split = False
+            if fused_criterion:
+                from .criterions import FusedRegCriterion
+                try:
+                    self.fused = FusedRegCriterion(criterion, self.hb.ncomps, example_batch)
+                except NotImplementedError:   # a loss outside the kernel, or a hand_verts_3d target: the registry losses through autograd
+                    self.fused = None
+            if self.fused is None:
+                self.use_graph = False
+            fused_criterion = False
+        elif not getattr(self.hb, "HAS_BOX_HEAD", True):             # SimpleBaseline: the fused pose/loss kernel is HybridBaseline's assembly
             fused_criterion = False
             self.split = False
             self.use_graph = False
@@ -171,6 +185,8 @@ class TrainStep:
         if not net._packed:
             net.pack_weights()
         net.image_plane = getattr(self, "_plane", "f32") if st.get("image_nhwc4_padded") is not None else "f32"
+        if self.reg:
+            return self._fwd_bwd_reg()
         logits, _ = net.forward(image=st.get(Queries.IMAGE), xpad=st.get("image_nhwc4_padded"))
         kp3d, conf, stat = net.head_fwd(logits)
         o = self.fused(kp3d, net.last["box_raw"], net.last["box_raw"].shape[-1], st)
@@ -180,6 +196,16 @@ class TrainStep:
         preds = dict(o, kp3d=kp3d, kp3d_confd=conf)
         return preds, o["losses"], o
 
+    def _fwd_bwd_reg(self):
+        """HOPRegNet: trunk + heads + MANO -> fused regbased criterion (+backward) -> MANO / heads / trunk backward, no autograd."""
+        hb, st = self.hb, self.static
+        pose, shape, verts, joints, full, transf = hb._run(st.get(Queries.IMAGE), st.get("image_nhwc4_padded"), save=True)
+        o = self.fused(joints, pose, shape, transf, st)
+        hb._backward(o["g_pose"], o["g_shape"], None, o["g_joints"], None, o["g_transf"])
+        hb.flat_param.grad = hb.store.grad
+        bridge = {"hand_verts_3d": verts, "joints_3d": joints, "mano_shape": shape, "mano_pca_pose": pose, "mano_full_pose": full, "transf": transf}
+        return bridge, o["losses"], o
+
     _capturing_split = False
 
     def predictions(self):
@@ -188,6 +214,10 @@ class TrainStep:
         derived here (a few small device ops, outside the graphs)."""
         if self.fused is None:
             return self.out[0]
+        if self.reg:      # HOPRegNet's 18 keys from the bridge outputs (the camera projections stay torch ops, as in its forward)
+            from .hpregnet import combine_outputs, mano_outputs, object_outputs
+            mano = {k: v for k, v in self.out[0].items() if k != "transf"}
+            return combine_outputs(mano_outputs(mano, self.static, self.dev), object_outputs(self.out[0]["transf"], self.static, self.dev))
         o, st = self.fused.out, self.static
         ja, ca, R = o["joints_3d_abs"], o["corners_3d_abs"], o["box_rot_rotmat"]
         root = ja[:, self.hb.center_idx:self.hb.center_idx + 1]
@@ -379,7 +409,7 @@ class TrainStep:
 class DeferredEpochMetrics:
     """Feeds an Evaluator without a device synchronisation per step (the reference's epoch_pass calls
     `evaluator.feed_all(predicts, batch, losses)` after every batch, train_artiboost.py:96-98, which moves tensors to the host
-    each time).  The fused pose/loss kernel already leaves every sample's joint / corner EPE in mm and the eight loss scalars
+    each time).  The fused pose/loss kernel (ab_pose_loss, or ab_reg_pose_loss for HOPRegNet) already leaves every sample's joint / corner EPE in mm and the loss scalars
     on the device: `collect()` stacks them (device-side copies on the step's stream), `flush()` makes ONE transfer at the end
     of the epoch and replays the steps into the metrics in their original order, so Mean3DEPE, LossesMetric and
     ValMetricMean3DEPE2 (last write per CCV triplet wins) end up exactly as with per-step feeding."""
@@ -391,7 +421,7 @@ class DeferredEpochMetrics:
         self.direct = [m for m in (evaluator.metrics_list if evaluator is not None else []) if not self._deferrable(m)]
         B, dev = ts.static[Queries.ROOT_JOINT].shape[0], ts.dev
         self.epe = torch.zeros((capacity, B, 2), dtype=torch.float32, device=dev)         # (joints, corners) mm
-        self.losses = torch.zeros((capacity, 8), dtype=torch.float32, device=dev)
+        self.losses = torch.zeros((capacity, getattr(ts.fused, "LOSS_WIDTH", 8)), dtype=torch.float32, device=dev)     # the criterion's loss vector
         self.ids = torch.zeros((capacity, B, 4), dtype=torch.int64, device=dev)           # obj, persp, grasp, is_synth
 
     @staticmethod
@@ -420,7 +450,7 @@ class DeferredEpochMetrics:
         n = self.n
         epe, losses, ids = self.epe[:n].cpu().numpy(), self.losses[:n].cpu().numpy(), self.ids[:n].cpu().numpy()
         col = {"joints_3d_abs": 0, "corners_3d_abs": 1}
-        keys = self.ts.fused.LOSS_KEYS
+        keys = [(i, k) for i, k in enumerate(self.ts.fused.LOSS_KEYS) if k is not None]      # (None: a slot that is no entry of the loss dict)
         for m in evaluator.metrics_list:
             if m in self.direct:
                 continue
@@ -436,8 +466,8 @@ class DeferredEpochMetrics:
                         m.avg_meters[key].update(float(epe[s, :, col[key]].sum()), n=epe.shape[1])
             elif isinstance(m, LossesMetric):
                 for s in range(n):
-                    m.feed(None, None, losses={k: losses[s, i] for i, k in enumerate(keys)})
+                    m.feed(None, None, losses={k: losses[s, i] for i, k in keys})
         if summarizer is not None:
             for s in range(n):
-                summarizer.summarize_losses({k: losses[s, i] for i, k in enumerate(keys)})
+                summarizer.summarize_losses({k: losses[s, i] for i, k in keys})
         self.n = 0

@@ -408,6 +408,25 @@ int ab_pose_loss_sym(const float* kp3d, const float* box6d, int box_stride, cons
                      int center_idx, float res_w, float res_h, const float* weights8_host, const ab_symcorner* sym,
                      float* joints_abs, float* corners_abs, float* rotmat, float* uvd2d, float* sample_part, float* losses,
                      float* g_kp3d, float* g_box6d, void* stream);
+/* The criterion of the regression-based model (HOPRegNet) in the same kernel, one launch + the finalize pass, deterministic:
+ * replaces anakin/models/hpregnet.py:112-147 (joints_3d_abs = MANO joints + the TARGET's root_joint; corners_3d_abs =
+ * ortho6d_to_rotmat(transf[3:9]) * corners_can + root_joint + transf[0:3]), anakin/criterions/honetloss.py:12-73 (ManoLoss: mean(shape^2),
+ * mean(pose[:, 3:]^2), unmasked joint MSE), jointloss.py:25-67, ordinal.py:144-227, 262-306, criterion.py:57-67, the per-sample EPE of
+ * anakin/metrics/val_metric.py:84-106, and their autograd backward.  joints_pred [B,21,3] (root-relative), mano_pca_pose [B,3+ncomps],
+ * mano_shape [B,10], transf rows of 9 with pitch transf_stride >= 9.  An ordinal loss is present exactly when its draw buffers are passed.
+ * weights12_host (HOST pointer) = the eight of ab_pose_loss, then LAMBDA_SHAPE_REG, LAMBDA_POSE_REG, ManoLoss's LAMBDA_JOINTS_3D,
+ * LAMBDAS[ManoLoss].  outputs: joints_abs [B,21,3], corners_abs [B,8,3], rotmat [B,3,3], sample_part [B,8] ([5],[6] = joint / corner EPE in
+ * mm, [7] = the sample's unmasked squared joint error), losses float[16] = the eight of ab_pose_loss, [8] mano_shape, [9] mano_pca_pose,
+ * [10] ManoLoss's joints_3d_loss, [11] joints_loss_output, [12] hand_ord_loss_output, [13..15] zero; gradients of final_loss: g_joints
+ * [B,21,3], g_pose [B,3+ncomps], g_shape [B,10], g_transf (pitch transf_stride; 9 values per row written).  NULL g_joints: forward only. */
+int ab_reg_pose_loss(const float* joints_pred, const float* mano_pca_pose, const float* mano_shape, const float* transf,
+                     int transf_stride, const float* root_joint, const float* cam_intr, const float* corners_can,
+                     const float* joints_3d, const float* corners_3d, const float* joints_vis, const float* corners_vis,
+                     const float* hand_views, int nvh, const int64_t* j0, const int64_t* j1, int njp, const int64_t* p0,
+                     const int64_t* p1, int npp, const float* scene_views, int nvs, const int64_t* s0, const int64_t* s1,
+                     int nsp, int B, int ncomps, const float* weights12_host, float* joints_abs, float* corners_abs,
+                     float* rotmat, float* sample_part, float* losses, float* g_joints, float* g_pose, float* g_shape,
+                     float* g_transf, void* stream);
 
 /* ---- R3/R4/R5: batched online synthesis (rasterise + z-buffer + shade + background + colour jitter + crop) --------
  * replaces: anakin/utils/renderer.py:101-136 (Renderer.__call__: pyrender/OpenGL draw, background putmask),
@@ -657,6 +676,7 @@ int ab_draw_meshes(const float* hand_verts, const int32_t* hand_faces, int nhf, 
  * @check ab_linear_wgrad: g >= M*N; x >= M*K; dw >= N*K; db >= N
  * @check ab_nearest_dist: strided: dist; x >= B*P1*3; rot >= B*9; obj_idx >= B; scale shift >= P1; idx_out >= B*P1
  * @check ab_pose_loss_sym: strided: box6d g_box6d; kp3d g_kp3d >= B*22*3; root_joint >= B*3; cam_intr >= B*9
+ * @check ab_reg_pose_loss: strided: transf g_transf; joints_pred joints_3d joints_abs g_joints >= B*63; mano_pca_pose g_pose >= B*(3+ncomps); mano_shape g_shape >= B*10; root_joint >= B*3; cam_intr >= B*9; corners_can corners_3d corners_abs >= B*24; joints_vis >= B*21; corners_vis >= B*8; rotmat >= B*9; sample_part >= B*8; losses >= 16; hand_views >= nvh*3; scene_views >= nvs*3; j0 j1 >= njp; p0 p1 >= npp; s0 s1 >= nsp; weights12_host >= 12
  * @check ab_linear_fused: strided: residual y; x >= M*K; w >= N*K; bias scale shift >= N
  * @check ab_mano_lbs: pose >= B*48; betas >= B*10; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; hands_mean >= 45; verts >= B*778*3; joints >= B*21*3; T_abs >= B*16*16
  * @check ab_mano_pca_fwd: pose_coeffs >= B*(3+ncomps); betas >= B*10; comps >= ncomps*45; hands_mean >= 45; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; verts >= B*778*3; joints >= B*21*3; full_pose >= B*48

@@ -1,6 +1,7 @@
 """Timing of the regression-based model (HOPRegNet on the HIP kernels, config/ho3dv2_regbased_artiboost_mi355x.yaml) on a seeded synthetic
 batch, one GPU:
-   train : TrainStep's eager step -- forward + the config's criterion (registry losses through autograd) + backward + clip/Adam
+   train : TrainStep's eager step -- forward + the config's criterion (registry losses through autograd) + backward + clip/Adam;
+           --fused: ARCH.FUSED_STEP, the fused criterion kernel and the step replayed as two hipGraphs
    eval  : eval-mode forward (trunk + heads + MANO + the torch-op projections)
 One JSON line per (mode, size)."""
 import argparse
@@ -23,6 +24,7 @@ ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--dtype", default="bf16x3")
 ap.add_argument("--modes", default="train,eval")
+ap.add_argument("--fused", action="store_true", help="ARCH.FUSED_STEP: the fused regbased criterion + graph-replayed step")
 a = ap.parse_args()
 
 from gen_batch import make_batch
@@ -48,7 +50,7 @@ def timed(fn, steps, warmup):
 cfg = yaml.safe_load(open(os.path.join(ROOT, "config", "ho3dv2_regbased_artiboost_mi355x.yaml")))
 for size in [int(s) for s in a.sizes.split(",")]:
     preset = dict(cfg["DATA_PRESET"], IMAGE_SIZE=[size, size], HEATMAP_SIZE=[size // 8, size // 8])
-    arch = dict(cfg["ARCH"], COMPUTE_DTYPE=a.dtype, DEVICE="cuda", INIT_SEED=1)
+    arch = dict(cfg["ARCH"], COMPUTE_DTYPE=a.dtype, DEVICE="cuda", INIT_SEED=1, **({"FUSED_STEP": True} if a.fused else {}))
     model = Arch({"ARCH": arch}, R.build_arch_model_list(arch, preset_cfg=preset))
     batch = {k: v.cuda() for k, v in make_batch(a.bs, size, 5).items()}
     for mode in a.modes.split(","):
@@ -58,10 +60,11 @@ for size in [int(s) for s in a.sizes.split(",")]:
             opt.max_norm = cfg["TRAIN"]["GRAD_CLIP"]
             model.train()
             ts = TrainStep(model, crit, opt, batch, use_graph=True)
+            assert (ts.fused is not None and ts.use_graph) == a.fused
             dt = timed(ts, a.steps, a.warmup)
         else:
             model.eval()
             with torch.no_grad():
                 dt = timed(lambda: model(batch), a.steps, a.warmup)
         print(json.dumps({"mode": mode, "size": size, "bs": a.bs, "dtype": a.dtype, "ms": round(dt * 1e3, 3),
-                          "samples_per_s": round(a.bs / dt, 1)}), flush=True)
+                          "samples_per_s": round(a.bs / dt, 1), **({"fused": True} if a.fused else {})}), flush=True)

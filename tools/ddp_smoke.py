@@ -19,6 +19,8 @@ from artiboost_amd.synth import ArtiBoostLoader
 from artiboost_amd.train import TrainStep
 
 rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+# --model regbased: HOPRegNet with ARCH.FUSED_STEP -- two linear graphs, the whole-gradient all-reduce between them (no staged backward)
+regbased = "--model" in sys.argv and sys.argv[sys.argv.index("--model") + 1] == "regbased"
 import random
 import numpy as np
 random.seed(100 + rank); np.random.seed(100 + rank); torch.manual_seed(100 + rank)      # the ordinal losses draw their pairs from these
@@ -31,9 +33,11 @@ if backend == "nccl":
     rccl_env_defaults()
 dist.init_process_group(backend)
 root = os.path.join(os.path.dirname(__file__), "..")
-cfg = yaml.safe_load(open(os.path.join(root, "config", "ho3dv2_clasbased_artiboost_mi355x.yaml")))
+cfg = yaml.safe_load(open(os.path.join(root, "config", "ho3dv2_regbased_artiboost_mi355x_fused.yaml" if regbased else "ho3dv2_clasbased_artiboost_mi355x.yaml")))
+if regbased:
+    import artiboost_amd.hpregnet  # noqa: F401  (registers HOPRegNet)
 dtype = os.environ.get("AB_DDP_DTYPE", "bf16x3")
-overlap = os.environ.get("AB_DDP_OVERLAP", "1") != "0"
+overlap = os.environ.get("AB_DDP_OVERLAP", "1") != "0" and not regbased
 arch = dict(cfg["ARCH"], COMPUTE_DTYPE=dtype, DEVICE=dev, INIT_SEED=1)
 model = Arch({"ARCH": arch}, R.build_arch_model_list(arch, preset_cfg=cfg["DATA_PRESET"]))
 crit = Criterion(cfg, R.build_criterion_loss_list(cfg["CRITERION"], preset_cfg=cfg["DATA_PRESET"], LAMBDAS=cfg["LAMBDAS"]))
@@ -49,7 +53,8 @@ model.train()
 ts = TrainStep(model, crit, opt, static, use_graph=True, dist_group=dist.group.WORLD, renderer=loader,
                pipeline_render="opt" if overlap else False)
 ts.static = static
-assert ts.split, "world_size > 1 must take the split-graph path"
+assert ts.split or regbased, "world_size > 1 must take the split-graph path"
+assert not regbased or (ts.fused is not None and ts.use_graph and not ts.split)
 ts.prime(loader, 0)
 for i in range(5):
     ts.stage(loader, i % len(loader))
@@ -61,7 +66,7 @@ ws = [torch.empty_like(w) for _ in range(world)]
 dist.all_gather(ws, w)
 same = all(torch.equal(ws[0], x) for x in ws)
 if rank == 0:
-    print(f"backend={backend} world={world} dtype={dtype} render_overlap={overlap} comm={ts.comm} final_loss={float(losses[5]):.9f} "
+    print(f"{'model=regbased ' if regbased else ''}backend={backend} world={world} dtype={dtype} render_overlap={overlap} comm={ts.comm} final_loss={float(losses[5]):.9f} "
           f"weight_sum={float(w.double().sum()):.12f} weights_identical_across_ranks={same}")
 assert same
 dist.destroy_process_group()
