@@ -1,1 +1,2 @@
-from artiboost_amd.criterions import Criterion, HandOrdLoss, JointsLoss, SceneOrdLoss, SymCornerLoss  # noqa: F401  (registers the LOSS types)
+from artiboost_amd.criterions import (AlignLoss, ChamferLoss, Criterion, HandOrdLoss, JointsLoss, ManoLoss, ObjLoss, SceneOrdLoss,  # noqa: F401
+                                       SymCornerLoss)      # registers the eight LOSS types of anakin/criterions/__init__.py

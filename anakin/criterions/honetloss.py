@@ -1,1 +1,1 @@
-from artiboost_amd.criterions import ManoLoss  # noqa: F401  (anakin/criterions/honetloss.py:12)
+from artiboost_amd.criterions import ManoLoss, ObjLoss  # noqa: F401  (anakin/criterions/honetloss.py:12,77)

@@ -652,3 +652,123 @@ class FusedRegCriterion:
         """Host view of the loss scalars of the last call under the keys of Criterion.compute_losses (synchronises)."""
         v = self.out["losses"].cpu()
         return {k: (None if s is None else v[s]) for k, s in self.key_slots.items()}
+
+
+# ---- mesh-level losses (DESIGN.md section 19) --------------------------------------------------------------------------------------------
+def _refuse_device(name, dev):
+    """No HIP kernel backs these two losses yet, and eager device torch ops are not a route of this build (a brute-force [N,M] distance
+    matrix per sample; a batched 3x3 torch.svd with a host synchronisation per step): a HIP tensor is an error, not a silent fallback."""
+    if dev.type == "cuda":
+        raise RuntimeError(f"{name} has no HIP kernel in this build: it runs on CPU tensors only (DESIGN.md section 19)")
+
+
+def chamfer_distance_torch(x, y):
+    """Brute-force, gather-based, differentiable stand-in for chamfer_distance.ChamferDistance (the un-pinned CUDA extension of
+    chamferloss.py:17): x [B,N,3], y [B,M,3] -> squared distances dist_xy [B,N], dist_yx [B,M] and the indices.  One sample at a time:
+    the [N,M] distance matrix of one sample is the only large temporary."""
+    dxy, dyx, ixy, iyx = [], [], [], []
+    for xb, yb in zip(x, y):
+        with torch.no_grad():
+            d = ((xb[:, None, :] - yb[None, :, :]) ** 2).sum(-1)
+            i, j = d.argmin(1), d.argmin(0)
+        dxy.append(((xb - yb[i]) ** 2).sum(-1)); dyx.append(((xb[j] - yb) ** 2).sum(-1))
+        ixy.append(i); iyx.append(j)
+    return torch.stack(dxy), torch.stack(dyx), torch.stack(ixy), torch.stack(iyx)
+
+
+@LOSS.register_module
+class ChamferLoss(TensorLoss):
+    """anakin/criterions/chamferloss.py:11-52.  The predicted cloud is R_pred can + boxroot, the target obj_verts_3d + root_joint (the
+    reference's padded [B,N,3] batch, datasets.ho_collate); both are multiplied by any(corners_vis) and compared by the two-way squared
+    nearest-neighbour distance.  Torch ops over chamfer_distance_torch, CPU tensors only."""
+
+    def __init__(self, **cfg):
+        super().__init__()
+        self.lambda_chamfer = cfg.get("LAMBDA_CHAMFER", 0.0)
+
+    def __call__(self, preds, targs, **kwargs):
+        final_loss, losses = super().__call__(preds, targs, **kwargs)
+        chamfer_loss = None
+        if self.lambda_chamfer:
+            dev = final_loss.device
+            _refuse_device("ChamferLoss", dev)
+            rot, tsl = preds["box_rot_rotmat"], preds["boxroot_3d_abs"]
+            keep = torch.any(targs[Queries.CORNERS_VIS].to(dev) != 0, dim=1).to(rot.dtype)
+            can = targs[Queries.OBJ_VERTS_CAN].to(dev)
+            v3d, root = targs[Queries.OBJ_VERTS_3D].to(dev), targs[Queries.ROOT_JOINT].to(dev)
+            pred = torch.matmul(rot, can.permute(0, 2, 1)).permute(0, 2, 1) + tsl
+            pred = torch.einsum("bij,b->bij", pred, keep)
+            targ = torch.einsum("bij,b->bij", v3d + root.unsqueeze(1), keep)
+            dist_xy, dist_yx, _, _ = chamfer_distance_torch(pred, targ)
+            chamfer_loss = torch.mean(dist_xy) + torch.mean(dist_yx)
+            final_loss = final_loss + self.lambda_chamfer * chamfer_loss
+        losses["chamfer_loss"] = chamfer_loss
+        losses[self.output_key] = final_loss
+        return final_loss, losses
+
+
+@LOSS.register_module
+class AlignLoss(TensorLoss):
+    """anakin/criterions/alignloss.py:12-80: the reference's torch ops (batched torch.svd under autograd), CPU tensors only."""
+
+    def __init__(self, **cfg):
+        super().__init__()
+        self.lambda_procrustes_align = cfg.get("LAMBDA_PROCRUSTES_ALIGN", 1.0)
+        self.lambda_st_align = cfg.get("LAMBDA_ST_ALIGN", 0.0)
+
+    def __call__(self, preds, targs, **kwargs):
+        final_loss, losses = super().__call__(preds, targs, **kwargs)
+        dev = final_loss.device
+        pred = preds["joints_3d_abs"]
+        loss = None
+        if self.lambda_procrustes_align:
+            _refuse_device("AlignLoss", dev)
+            xyz = (targs[Queries.JOINTS_3D] + targs[Queries.ROOT_JOINT].unsqueeze(1)).to(dev)
+            loss = F.mse_loss(self.procrustes_align(xyz, pred), xyz)
+            final_loss = final_loss + self.lambda_procrustes_align * loss
+        losses["procrustes_aligned_loss"] = loss
+        if self.lambda_st_align:
+            raise NotImplementedError()
+        losses["st_aligned_loss"] = None
+        losses[self.output_key] = final_loss
+        return final_loss, losses
+
+    @staticmethod
+    def torch_orthogonal_procrustes(A, B):
+        u, w, v = torch.svd(B.transpose(1, 2).bmm(A).transpose(1, 2))
+        R = u.bmm(v.transpose(1, 2))
+        scale = w.sum(dim=1, keepdim=True).unsqueeze(-1)
+        return R, scale
+
+    @staticmethod
+    def procrustes_align(xyz, pred_xyz):
+        tsl = xyz.mean(1, keepdim=True)
+        pred_tsl = pred_xyz.mean(1, keepdim=True)
+        xyz_tsl = xyz - tsl
+        pred_xyz_tsl = pred_xyz - pred_tsl
+        scale = torch.norm(xyz_tsl, dim=(1, 2), keepdim=True) + 1e-8
+        xyz_tsl_scale = xyz_tsl / scale
+        pred_scale = torch.norm(pred_xyz_tsl, dim=(1, 2), keepdim=True) + 1e-8
+        pred_xyz_tsl_scale = pred_xyz_tsl / pred_scale
+        R, s = AlignLoss.torch_orthogonal_procrustes(xyz_tsl_scale, pred_xyz_tsl_scale)
+        return torch.bmm(pred_xyz_tsl_scale, R.transpose(1, 2)) * s * scale + tsl
+
+
+@LOSS.register_module
+class ObjLoss(TensorLoss):
+    """anakin/criterions/honetloss.py:76-97: MSE on the posed object vertices.  Torch ops only: it reads preds["obj_verts_3d_abs"], which
+    only the reference's HoNet produces."""
+
+    def __init__(self, **cfg):
+        super().__init__()
+        self.lambda_obj_verts_3d = cfg["LAMBDA_OBJ_VERTS_3D"]
+
+    def __call__(self, preds, targs, **kwargs):
+        final_loss, losses = super().__call__(preds, targs, **kwargs)
+        loss = None
+        if self.lambda_obj_verts_3d and Queries.OBJ_VERTS_3D in targs:
+            p = preds["obj_verts_3d_abs"]
+            loss = F.mse_loss(p, targs[Queries.OBJ_VERTS_3D].to(p.device) + targs[Queries.ROOT_JOINT].to(p.device).unsqueeze(1))
+            final_loss = final_loss + self.lambda_obj_verts_3d * loss
+        losses["obj_verts_3d_loss"] = loss
+        return final_loss, losses

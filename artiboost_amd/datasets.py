@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .realdata import HOdataSource, annot_center_scale
-from .registry import CONST, DATASET
+from .registry import CONST, DATASET, Queries
 
 
 class _DownloadedSet(HOdataSource):
@@ -258,8 +258,22 @@ class SynthOnly(_DownloadedSet):
 
 
 def ho_collate(batch):
-    """hodata.py:17-62 for the fixed-size queries of the hot path (every sample dict carries same-shaped arrays): stack per
-    key.  (The variable-length OBJ_VERTS_* padding of the reference applies to mesh queries no model of this path reads.)"""
+    """hodata.py:17-62: the variable-length mesh queries (OBJ_VERTS_3D / OBJ_VERTS_CAN / OBJ_VERTS_2D) are padded by repetition to the
+    longest of the batch and a PADDING_MASK field (ones over each sample's own vertices) is added; every other query is stacked per
+    key.  A batch without mesh queries collates as before."""
+    extend = [q for q in (Queries.OBJ_VERTS_3D, Queries.OBJ_VERTS_CAN, Queries.OBJ_VERTS_2D) if q in batch[0]]
+    if extend:
+        batch = [dict(b) for b in batch]
+    for q in extend:
+        nmax = max(b[q].shape[0] for b in batch)
+        for b in batch:
+            v = np.asarray(b[q])
+            n = v.shape[0]
+            b[q] = np.concatenate([v] * int(nmax / n + 1))[:nmax]
+            if Queries.PADDING_MASK not in b:
+                mask = np.zeros(nmax, dtype=np.int64)
+                mask[:n] = 1
+                b[Queries.PADDING_MASK] = mask
     out = {}
     for k in batch[0]:
         v = [b[k] for b in batch]

@@ -197,6 +197,10 @@ class Queries:
     JOINTS_VIS = "joints_vis"
     OBJ_TRANSF = "obj_transf"
     OBJ_IDX = "obj_idx"
+    OBJ_VERTS_CAN = "obj_verts_can"
+    OBJ_VERTS_3D = "obj_verts_3d"
+    OBJ_VERTS_2D = "obj_verts_2d"
+    PADDING_MASK = "padding_mask"
 
 
 class SynthQueries:
