@@ -757,7 +757,7 @@ class AlignLoss(TensorLoss):
 @LOSS.register_module
 class ObjLoss(TensorLoss):
     """anakin/criterions/honetloss.py:76-97: MSE on the posed object vertices.  Torch ops only: it reads preds["obj_verts_3d_abs"], which
-    only the reference's HoNet produces."""
+    HoNet produces (honet.HoNet / regnet.HoNetHIP)."""
 
     def __init__(self, **cfg):
         super().__init__()

@@ -51,7 +51,7 @@ class ParamStore:
     """Flat parameter / gradient / running-stat storage with reference <-> kernel layout conversion."""
 
     def __init__(self, nclasses=22, depth=28, device="cuda", layers=(3, 4, 6, 3), head_prefix="hybrid_head", box_head=True,
-                 block="basic", box_dims=(512, 256, 128), reg_heads=None):
+                 block="basic", box_dims=(512, 256, 128), reg_heads=None, reg_model="HOPRegNet"):
         """layers: BasicBlock counts per stage ((3,4,6,3) = ResNet-34, (2,2,2,2) = ResNet-18: resnet.py:236-248); head_prefix: the
         IntegralDeconvHead's attribute name in the reference module ("hybrid_head" in HybridBaseline, "pose_head" in SimpleBaseline:
         hybridbaseline.py:31, simplebaseline.py:207); box_head: MLP_O present (HybridBaseline only).
@@ -59,7 +59,12 @@ class ParamStore:
         kernels): a padding class has zero weights, zero bias and receives zero gradient.
         reg_heads=ncomps: the trunk-only layout of HOPRegNet (hpregnet.py:18-150) -- the backbone under the reference's `base_net.`
         names, no IntegralDeconvHead and no MLP_O, and the regression heads of ManoBranch (mano.py:46-137: 512 -> 512 -> 512, pose
-        512 -> 3 + ncomps, shape 512 -> 10) and HOPRegNet.TransHead (512 -> 256 -> 9) as fp32 linear layers in the same flat buffer."""
+        512 -> 3 + ncomps, shape 512 -> 10) and HOPRegNet.TransHead (512 -> 256 -> 9) as fp32 linear layers in the same flat buffer.
+        reg_model="HoNet" (with reg_heads): the same trunk-only layout with HoNet's head set (honetMANO.py:36-41) -- ManoBranch, then
+        `mano_transhead` (512 -> 256 -> 3) and `obj_transhead` (512 -> 256 -> 6) in place of `obj_transfhead`."""
+        if reg_model not in ("HOPRegNet", "HoNet"):
+            raise ValueError(f"reg_model {reg_model!r}: HOPRegNet or HoNet")
+        self.reg_model = reg_model
         self.nclasses, self.depth = nclasses, depth
         self.nclasses_pad = nclasses + (nclasses & 1)
         self.layers, self.hp, self.box_head = tuple(layers), head_prefix, bool(box_head)
@@ -161,8 +166,12 @@ class ParamStore:
 
     def _build_reg_heads(self):
         F, P = self.feat_ch, 3 + self.reg_ncomps
-        for name, o, i in (("mano_branch.base_layer.0", 512, F), ("mano_branch.base_layer.2", 512, 512), ("mano_branch.pose_reg", P, 512),
-                           ("mano_branch.shape_reg.0", 10, 512), ("obj_transfhead.decoder.0", F // 2, F), ("obj_transfhead.final_layer", 9, F // 2)):
+        trans = ((("obj_transfhead", 9),) if self.reg_model == "HOPRegNet" else (("mano_transhead", 3), ("obj_transhead", 6)))
+        heads = [("mano_branch.base_layer.0", 512, F), ("mano_branch.base_layer.2", 512, 512), ("mano_branch.pose_reg", P, 512),
+                 ("mano_branch.shape_reg.0", 10, 512)]
+        for th, o in trans:
+            heads += [(th + ".decoder.0", F // 2, F), (th + ".final_layer", o, F // 2)]
+        for name, o, i in heads:
             op = _round_up(o, self.REG_PAD)
             self._add(name + ".weight", "linear" if op == o else "linear_pad", (o, i), (op, 1, 1, i))
             self._add(name + ".bias", "vec" if op == o else "vec_pad", (o,), (op,))
@@ -308,7 +317,7 @@ class ParamStore:
                 sd[name] = (torch.rand(shp, generator=g) * 2 - 1) * bound
             elif name.endswith(".weight") and e.kind == "vec":
                 sd[name] = torch.ones(shp)
-            elif "box_head" in name or "fc.bias" in name or name.startswith(("mano_branch.", "obj_transfhead.")):
+            elif "box_head" in name or "fc.bias" in name or name.startswith(("mano_branch.", "obj_transfhead.", "mano_transhead.", "obj_transhead.")):
                 fan_in = self.entries[name.replace(".bias", ".weight")].ref_shape[1]
                 sd[name] = (torch.rand(shp, generator=g) * 2 - 1) / math.sqrt(fan_in)
             else:

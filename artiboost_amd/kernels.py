@@ -874,6 +874,81 @@ def mano_pca_bwd(pose_coeffs, betas, tables, g_verts, g_joints, g_full_pose=None
     return g_pc, g_b
 
 
+HONET_FWD_OUT = ("root_joint", "joints_3d_abs", "hand_verts_3d_abs", "joints_2d", "hand_verts_2d", "obj_center", "box_rot_rotmat",
+                 "obj_verts_3d_abs", "obj_verts_2d", "corners_3d_abs", "corners_2d", "corners_3d", "obj_verts_3d")
+
+
+def _honet_rows(t, w, what):
+    """A [B, >= w] fp32 view whose rows are addressed through their pitch: -> the pitch in floats."""
+    if t.dim() != 2 or t.shape[1] < w or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{what} must be fp32 rows of at least {w} unit-stride columns, got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
+    return t.stride(0)
+
+
+def _honet_inputs(hand_st, obj_st, cam_intr, joints_3d, hand_verts_3d, obj_verts_can, corners_can, factors, image_size, off_z):
+    B, N = obj_verts_can.shape[0], obj_verts_can.shape[1]
+    for t, shp, what in ((cam_intr, (B, 3, 3), "cam_intr"), (joints_3d, (B, 21, 3), "joints_3d"), (hand_verts_3d, (B, 778, 3), "hand_verts_3d"),
+                         (obj_verts_can, (B, N, 3), "obj_verts_can"), (corners_can, (B, 8, 3), "corners_can")):
+        if t is not None and (t.numel() != shp[0] * shp[1] * shp[2] or t.dtype != torch.float32):
+            raise ValueError(f"honet_recover: {what} must be fp32 {shp}, got {t.dtype} {tuple(t.shape)}")
+    if hand_st.shape[0] != B or obj_st.shape[0] != B or N < 1:
+        raise ValueError(f"honet_recover: {hand_st.shape[0]} / {obj_st.shape[0]} head rows for {B} samples of {N} vertices")
+    hp, op = _honet_rows(hand_st, 3, "hand_st"), _honet_rows(obj_st, 6, "obj_st")
+    return B, N, (L.view_ptr(hand_st), L.i(hp), L.view_ptr(obj_st), L.i(op), L.ptr(cam_intr), L.ptr(joints_3d), L.ptr(hand_verts_3d),
+                  L.ptr(obj_verts_can), L.ptr(corners_can), L.i(B), L.i(N), L.f(factors[0]), L.f(factors[1]), L.f(image_size[0]),
+                  L.f(image_size[1]), L.f(off_z))
+
+
+def honet_recover_fwd(hand_st, obj_st, cam_intr, joints_3d, hand_verts_3d, obj_verts_can, corners_can, factors, image_size, off_z=0.4,
+                      want_rel_verts=True):
+    """HoNet's recovery stage (ab_honet_recover_fwd).  hand_st [B, >= 3] / obj_st [B, >= 6]: fp32 row views (any row pitch) of the
+    TransHeads' outputs; cam_intr [B,3,3]; joints_3d [B,21,3], hand_verts_3d [B,778,3]; obj_verts_can [B,N,3]; corners_can [B,8,3] or
+    None; factors (OBJ_TRANS_FACTOR, OBJ_SCALE_FACTOR); image_size (width, height).  -> dict of HONET_FWD_OUT (the model's key names;
+    root_joint / obj_center [B,1,3], box_rot_rotmat [B,3,3]); the corner entries are None without corners_can, obj_verts_3d without
+    want_rel_verts."""
+    B, N, args = _honet_inputs(hand_st, obj_st, cam_intr, joints_3d, hand_verts_3d, obj_verts_can, corners_can, factors, image_size, off_z)
+    z = lambda *s: torch.empty(s, dtype=torch.float32, device=obj_verts_can.device)      # noqa: E731
+    cz = (lambda *s: z(*s)) if corners_can is not None else (lambda *s: None)
+    o = dict(root_joint=z(B, 1, 3), joints_3d_abs=z(B, 21, 3), hand_verts_3d_abs=z(B, 778, 3), joints_2d=z(B, 21, 2), hand_verts_2d=z(B, 778, 2),
+             obj_center=z(B, 1, 3), box_rot_rotmat=z(B, 3, 3), obj_verts_3d_abs=z(B, N, 3), obj_verts_2d=z(B, N, 2), corners_3d_abs=cz(B, 8, 3),
+             corners_2d=cz(B, 8, 2), corners_3d=cz(B, 8, 3), obj_verts_3d=z(B, N, 3) if want_rel_verts else None)
+    L.check(L.lib().ab_honet_recover_fwd(*args, *(L.ptr(o[k]) for k in HONET_FWD_OUT), L.stream()), "ab_honet_recover_fwd")
+    return o
+
+
+def honet_recover_bwd(hand_st, obj_st, cam_intr, joints_3d, hand_verts_3d, obj_verts_can, corners_can, factors, image_size, grads, off_z=0.4,
+                      g_hand_st=None, g_obj_st=None):
+    """Reverse of honet_recover_fwd (ab_honet_recover_bwd).  grads: {HONET_FWD_OUT name: gradient or None / absent = zero}.
+    g_hand_st / g_obj_st: optional fp32 row views to write the (scale, trans) / (scale, trans, axis-angle) gradients into (their first
+    3 / 6 columns; the rest is not touched); allocated dense when None.  -> (g_hand_st, g_obj_st, g_joints_3d [B,21,3],
+    g_hand_verts_3d [B,778,3]).  Fixed-order reductions: bit-reproducible."""
+    B, N, args = _honet_inputs(hand_st, obj_st, cam_intr, joints_3d, hand_verts_3d, obj_verts_can, corners_can, factors, image_size, off_z)
+    dev = obj_verts_can.device
+    z = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)      # noqa: E731
+    g_hand_st = z(B, 3) if g_hand_st is None else g_hand_st
+    g_obj_st = z(B, 6) if g_obj_st is None else g_obj_st
+    if g_hand_st.shape[0] != B or g_obj_st.shape[0] != B:
+        raise ValueError("honet_recover_bwd: g_hand_st / g_obj_st need one row per sample")
+    ghp, gop = _honet_rows(g_hand_st, 3, "g_hand_st"), _honet_rows(g_obj_st, 6, "g_obj_st")
+    gs = []
+    for k in HONET_FWD_OUT:
+        g = grads.get(k)
+        if g is not None:
+            want = B * {"root_joint": 3, "obj_center": 3, "box_rot_rotmat": 9, "joints_3d_abs": 63, "joints_2d": 42, "hand_verts_3d_abs": 2334,
+                        "hand_verts_2d": 1556, "obj_verts_3d_abs": 3 * N, "obj_verts_3d": 3 * N, "obj_verts_2d": 2 * N, "corners_3d_abs": 24,
+                        "corners_3d": 24, "corners_2d": 16}[k]
+            if g.numel() != want or g.dtype != torch.float32:
+                raise ValueError(f"honet_recover_bwd: gradient of {k} must be fp32 with {want} elements, got {g.dtype} {tuple(g.shape)}")
+            if corners_can is None and k.startswith("corners"):
+                raise ValueError(f"honet_recover_bwd: a gradient of {k} without corners_can")
+        gs.append(L.ptr(g))
+    g_j, g_v = z(B, 21, 3), z(B, 778, 3)
+    ws = torch.empty((L.lib().ab_honet_recover_workspace(L.i(B), L.i(N)),), dtype=torch.uint8, device=dev)
+    L.check(L.lib().ab_honet_recover_bwd(*args, *gs, L.view_ptr(g_hand_st), L.i(ghp), L.view_ptr(g_obj_st), L.i(gop), L.ptr(g_j), L.ptr(g_v),
+                                         L.ptr(ws), L.stream()), "ab_honet_recover_bwd")
+    return g_hand_st, g_obj_st, g_j, g_v
+
+
 FIT_NP = 59             # parameters per hand of ab_mano_fit: so3 48 | beta 10 | bone 1
 
 

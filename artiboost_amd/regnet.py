@@ -13,7 +13,10 @@ Autograd boundary: ONE torch.autograd.Function (_RegBridge, as models._NetBridge
 outputs (mano_pca_pose, mano_shape, hand_verts_3d, joints_3d, mano_full_pose, transf [N, 9]); its backward runs MANO bwd -> head bwd ->
 trunk bwd, writes store.grad and hands it to flat_param.grad.  The camera projections and the 6-D rotation of the object stay torch ops
 on those outputs (hpregnet.mano_outputs / object_outputs), so the model returns the CPU module's 18 keys and the registry losses and
-metrics run unchanged."""
+metrics run unchanged.
+
+HoNetHIP (below) is HoNet (anakin/models/honetMANO.py) on the same trunk, ManoBranch heads and MANO kernels; its camera-frame stage is
+one kernel pair (ab_honet_recover_fwd / _bwd) inside its bridge instead of torch ops outside it."""
 import os
 from collections import OrderedDict
 from typing import Dict
@@ -23,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
+from .honet import HoNet
 from .hpregnet import HOPRegNet, combine_outputs, load_hand_model, mano_outputs, object_outputs
 from .hybridnet import HybridNet, ParamStore
 from .models import BACKBONES, HybridBaseline
@@ -52,6 +56,8 @@ class _RegBridge(torch.autograd.Function):
 class HOPRegNetHIP(nn.Module):
     HAS_BOX_HEAD = False             # (TrainStep: no MLP_O box head -- the fused pose/loss kernel is HybridBaseline's assembly)
     CHECKPOINT_NAME = "HOPRegNet"    # checkpoint files are interchangeable with the torch module's
+    TORCH_MODULE = HOPRegNet         # the registry's torch module of the same model: its checkpoint cleaning
+    REG_MODEL = "HOPRegNet"          # ParamStore(reg_model=...): which head set follows the trunk in the flat buffer
 
     @enable_lower_param
     def __init__(self, **cfg):
@@ -80,9 +86,10 @@ class HOPRegNetHIP(nn.Module):
         self.P = 3 + self.ncomps
         # ARCH.FUSED_STEP: true -- TrainStep runs this model without autograd (criterions.FusedRegCriterion) and replays the step as hipGraphs
         self.FUSED_STEP = bool(cfg.get("FUSED_STEP", False))
+        self._read_cfg(cfg)
         dev = cfg.get("DEVICE", "cuda")
         cd = cfg.get("COMPUTE_DTYPE", "bf16x3")
-        self.store = ParamStore(device=dev, layers=BACKBONES[bb["TYPE"]][1], reg_heads=self.ncomps)
+        self.store = ParamStore(device=dev, layers=BACKBONES[bb["TYPE"]][1], reg_heads=self.ncomps, reg_model=self.REG_MODEL)
         self.store.init_reference_like(seed=int(cfg.get("INIT_SEED", 1)))
         self.net = HybridNet(self.store, image_size=self.inp_res,
                              compute_dtype=(torch.bfloat16 if cd in ("bf16", torch.bfloat16) else
@@ -103,16 +110,19 @@ class HOPRegNetHIP(nn.Module):
         pretrained = cfg.get("PRETRAINED", "")
         if pretrained:
             if not os.path.isfile(pretrained):
-                raise FileNotFoundError(f"=> No HOPRegNet checkpoints file found in {pretrained}")
+                raise FileNotFoundError(f"=> No {self.CHECKPOINT_NAME} checkpoints file found in {pretrained}")
             ck = torch.load(pretrained, map_location="cpu")
             self.load_state_dict(ck["state_dict"] if isinstance(ck, dict) and "state_dict" in ck else ck, strict=True)
+
+    def _read_cfg(self, cfg):
+        """Subclass hook, called before the store is built: the model's own config keys and refusals."""
 
     # --- checkpoints in the reference layout (the torch module's keys: base_net.*, mano_branch.*, obj_transfhead.*)
     def state_dict(self, *a, **k):
         return OrderedDict((k_, v.cpu()) for k_, v in self.store.reference_state_dict().items())
 
     def load_state_dict(self, sd, strict=True):
-        sd = HOPRegNet.clean_reference_state_dict(sd)
+        sd = self.TORCH_MODULE.clean_reference_state_dict(sd)
         if strict:
             expected = set(self.store.reference_state_dict().keys())
             unexpected = sorted(set(sd) - expected)
@@ -132,7 +142,7 @@ class HOPRegNetHIP(nn.Module):
     _plane_of = HybridBaseline._plane_of
 
     def _replicate_for_data_parallel(self):
-        raise RuntimeError("HOPRegNet (HIP) cannot be replicated by nn.DataParallel: its parameters live in one device's flat buffer; "
+        raise RuntimeError(f"{self.CHECKPOINT_NAME} (HIP) cannot be replicated by nn.DataParallel: its parameters live in one device's flat buffer; "
                            "restrict DataParallel to one device (--gpu_id 0 / CUDA_VISIBLE_DEVICES=0)")
 
     # --- the device computation
@@ -165,11 +175,10 @@ class HOPRegNetHIP(nn.Module):
                 g[:, :t.shape[1]] += t
         return g
 
-    def _backward(self, g_pose, g_shape, g_verts, g_joints, g_full, g_transf):
-        S, p, dev = self._saved, self.store, self.store.device
-        if S is None:
-            raise RuntimeError("backward without a grad-mode training forward")
-        self._saved = None
+    def _hand_branch_backward(self, S, g_pose, g_shape, g_verts, g_joints, g_full):
+        """MANO bwd -> pose_reg / shape_reg -> ManoBranch's MLP: writes their weight gradients, -> the gradient wrt base_layer.0's
+        output (h1), whose data gradient the caller adds to the other branches' at res_layer4_mean."""
+        p, dev = self.store, self.store.device
         N = S["fmean"].shape[0]
         c = lambda t: None if t is None else t.contiguous().float()      # noqa: E731
         gvt = c(g_verts) if g_verts is not None else torch.zeros((N, 778, 3), dtype=torch.float32, device=dev)
@@ -177,26 +186,50 @@ class HOPRegNetHIP(nn.Module):
         g_pc, g_b = K.mano_pca_bwd(S["pose"], S["shape"], self.mano, gvt, gjt, c(g_full), self.center_idx)
         gp = self._padded(HEADS[2], N, g_pc, c(g_pose))
         gs = self._padded(HEADS[3], N, g_b, c(g_shape))
-        gt = self._padded(HEADS[5], N, c(g_transf))
-        gv = lambda n: p.gview(n + ".weight").view(p.entries[n + ".weight"].kshape[0], -1)      # noqa: E731
-        gb = lambda n: p.gview(n + ".bias")                                                       # noqa: E731
-        wt = lambda n: self.net.box_t[n + ".weight"]                                              # noqa: E731  ([in][out] copies)
-        # hand branch: pose_reg and shape_reg share their input (h2); its gradient is the sum of theirs, pose first
+        gv, gb, wt = self._gv, self._gb, self._wt
+        # pose_reg and shape_reg share their input (h2); its gradient is the sum of theirs, pose first
         K.linear_wgrad(gp, S["h2"], gv(HEADS[2]), gb(HEADS[2]))
         K.linear_wgrad(gs, S["h2"], gv(HEADS[3]), gb(HEADS[3]))
         gh2 = K.linear_dgrad(gp, wt(HEADS[2]), act_out=S["h2"]) + K.linear_dgrad(gs, wt(HEADS[3]), act_out=S["h2"])
         K.linear_wgrad(gh2, S["h1"], gv(HEADS[1]), gb(HEADS[1]))
         gh1 = K.linear_dgrad(gh2, wt(HEADS[1]), act_out=S["h1"])
         K.linear_wgrad(gh1, S["fmean"], gv(HEADS[0]), gb(HEADS[0]))
-        # object branch
-        K.linear_wgrad(gt, S["d1"], gv(HEADS[5]), gb(HEADS[5]))
-        gd1 = K.linear_dgrad(gt, wt(HEADS[5]), act_out=S["d1"])
-        K.linear_wgrad(gd1, S["fmean"], gv(HEADS[4]), gb(HEADS[4]))
+        return gh1
+
+    def _gv(self, n):
+        return self.store.gview(n + ".weight").view(self.store.entries[n + ".weight"].kshape[0], -1)
+
+    def _gb(self, n):
+        return self.store.gview(n + ".bias")
+
+    def _wt(self, n):
+        return self.net.box_t[n + ".weight"]      # ([in][out] copies)
+
+    def _transhead_backward(self, S, g, dec, fin, act):
+        """TransHead (decoder.0 + ReLU + final_layer) from g, the padded gradient of its output: writes the weight gradients, -> the
+        gradient wrt decoder.0's output."""
+        K.linear_wgrad(g, S[act], self._gv(fin), self._gb(fin))
+        gd = K.linear_dgrad(g, self._wt(fin), act_out=S[act])
+        K.linear_wgrad(gd, S["fmean"], self._gv(dec), self._gb(dec))
+        return gd
+
+    def _backward(self, g_pose, g_shape, g_verts, g_joints, g_full, g_transf):
+        S = self._saved
+        if S is None:
+            raise RuntimeError("backward without a grad-mode training forward")
+        self._saved = None
+        N = S["fmean"].shape[0]
+        c = lambda t: None if t is None else t.contiguous().float()      # noqa: E731
+        gt = self._padded(HEADS[5], N, c(g_transf))
+        wt = self._wt
+        gh1 = self._hand_branch_backward(S, g_pose, g_shape, g_verts, g_joints, g_full)
+        gd1 = self._transhead_backward(S, gt, HEADS[4], HEADS[5], "d1")
         # res_layer4_mean feeds both branches: hand + object, in that order
         g_mean = K.linear_dgrad(gh1, wt(HEADS[0])) + K.linear_dgrad(gd1, wt(HEADS[4]))
         self.net.backward(g_mean=g_mean)
 
-    def forward(self, inputs: Dict):
+    def _image_of(self, inputs):
+        """-> (image, xpad) of the batch on the device, the trunk's image plane set and the weight copies fresh."""
         dev = self.store.device
         xpad = inputs.get("image_nhwc4_padded")
         image = None
@@ -208,6 +241,11 @@ class HOPRegNetHIP(nn.Module):
         if not self.net._packed or self.flat_param._version != getattr(self, "_seen_version", -1):
             self.net.pack_weights()      # torch-side update (e.g. torch.optim.Adam); the fused optimizer repacks itself
             self._seen_version = self.flat_param._version
+        return image, xpad
+
+    def forward(self, inputs: Dict):
+        dev = self.store.device
+        image, xpad = self._image_of(inputs)
         if self.training and torch.is_grad_enabled():
             pose, shape, verts, joints, full, transf = _RegBridge.apply(self.flat_param, self, image, xpad)
         else:
@@ -215,3 +253,120 @@ class HOPRegNetHIP(nn.Module):
                 pose, shape, verts, joints, full, transf = self._run(image, xpad, save=False)
         mano = {"hand_verts_3d": verts, "joints_3d": joints, "mano_shape": shape, "mano_pca_pose": pose, "mano_full_pose": full}
         return combine_outputs(mano_outputs(mano, inputs, dev), object_outputs(transf, inputs, dev))
+
+
+# ------------------------------------------------------------------------------------------------ HoNet
+HONET_TRANS = ("mano_transhead.decoder.0", "mano_transhead.final_layer", "obj_transhead.decoder.0", "obj_transhead.final_layer")
+# the bridge's outputs after the five of the MANO branch and the two TransHead rows: ab_honet_recover_fwd's, under the model's keys
+HONET_GEO = K.HONET_FWD_OUT
+
+
+class _HoBridge(torch.autograd.Function):
+    """forward: HIP trunk + heads + MANO + recovery; backward: recovery bwd -> MANO bwd -> heads bwd -> trunk bwd into the flat gradient."""
+
+    @staticmethod
+    def forward(ctx, flat_param, owner, image, xpad, geo):
+        out = owner._run(image, xpad, True, geo)
+        ctx.owner = owner
+        return out
+
+    @staticmethod
+    def backward(ctx, *grads):
+        owner = ctx.owner
+        owner._backward(*grads)
+        owner.flat_param.grad = owner.store.grad      # the kernels wrote it; no copy, no accumulation
+        return None, None, None, None, None
+
+
+class HoNetHIP(HOPRegNetHIP):
+    """HoNet (anakin/models/honetMANO.py:19-286; the torch module is honet.HoNet) on the HIP kernels: HOPRegNetHIP's trunk, ManoBranch heads
+    and MANO kernels, two TransHeads (512 -> 256 -> 3 / 6) on the fp32 linear kernels, and the recovery stage -- placement from the predicted
+    scale / translation, Rodrigues, rotation of the canonical object vertices, every projection -- as ab_honet_recover_fwd / _bwd.  One
+    autograd Function (_HoBridge) whose outputs are the differentiable entries of the returned dict; the dict is the torch module's, key
+    for key.  No fused criterion and no graph capture: TrainStep takes its eager route."""
+    CHECKPOINT_NAME = "HoNet"
+
+    TORCH_MODULE = HoNet
+    REG_MODEL = "HoNet"
+
+    def _read_cfg(self, cfg):
+        if self.FUSED_STEP:
+            raise NotImplementedError("HoNet with FUSED_STEP: true -- there is no fused criterion and no captured step for HoNet; "
+                                      "train it on the eager route (leave ARCH.FUSED_STEP out)")
+        self.obj_trans_factor, self.obj_scale_factor = float(cfg["OBJ_TRANS_FACTOR"]), float(cfg["OBJ_SCALE_FACTOR"])
+
+    def _geo_of(self, inputs):
+        """The batch's geometric inputs of the recovery stage on the device: (cam_intr, obj_verts_can, corners_can | None)."""
+        dev = self.store.device
+        f = lambda t: t.to(dev, torch.float32, non_blocking=True).contiguous()      # noqa: E731
+        img = inputs.get(Queries.IMAGE)
+        if img is not None and (int(img.shape[3]), int(img.shape[2])) != (int(self.inp_res[0]), int(self.inp_res[1])):
+            raise ValueError(f"HoNet: image {tuple(img.shape)} does not match DATA_PRESET.IMAGE_SIZE {tuple(self.inp_res)}")
+        return (f(inputs[Queries.CAM_INTR]), f(inputs[Queries.OBJ_VERTS_CAN]),
+                f(inputs[Queries.CORNERS_CAN]) if Queries.CORNERS_3D in inputs else None)
+
+    def _run(self, image, xpad, save, geo):
+        """-> (mano_pca_pose, mano_shape, hand_verts_3d, joints_3d, mano_full_pose, hand_st [N,3], obj_st [N,6], *HONET_GEO)."""
+        cam_intr, can, ccan = geo
+        fmean = self.net.forward(image=image, xpad=xpad)                    # res_layer4_mean [N, 512] f32
+        h1 = self._lin(fmean, HEADS[0], relu=True)
+        h2 = self._lin(h1, HEADS[1], relu=True)
+        pose = self._lin(h2, HEADS[2])[:, :self.P].contiguous()
+        shape = self._lin(h2, HEADS[3])[:, :10].contiguous()
+        m1 = self._lin(fmean, HONET_TRANS[0], relu=True)
+        hst = self._lin(m1, HONET_TRANS[1])[:, :3]                          # rows of the padded output: the kernels take the pitch
+        o1 = self._lin(fmean, HONET_TRANS[2], relu=True)
+        ost = self._lin(o1, HONET_TRANS[3])[:, :6]
+        verts, joints, full = K.mano_pca_fwd(pose, shape, self.mano, self.center_idx)
+        o = K.honet_recover_fwd(hst, ost, cam_intr, joints, verts, can, ccan, (self.obj_trans_factor, self.obj_scale_factor), self.inp_res)
+        self._saved = dict(fmean=fmean, h1=h1, h2=h2, m1=m1, o1=o1, pose=pose, shape=shape, hst=hst, ost=ost, verts=verts, joints=joints,
+                           geo=geo) if save else None
+        return (pose, shape, verts, joints, full, hst, ost) + tuple(o[k] for k in HONET_GEO)
+
+    def _backward(self, g_pose, g_shape, g_verts, g_joints, g_full, g_hst, g_ost, *g_geo):
+        S = self._saved
+        if S is None:
+            raise RuntimeError("backward without a grad-mode training forward")
+        self._saved = None
+        N = S["fmean"].shape[0]
+        c = lambda t: None if t is None else t.contiguous().float()      # noqa: E731
+        cam_intr, can, ccan = S["geo"]
+        # recovery: the kernel overwrites the first 3 / 6 columns of the padded head gradients; direct gradients on the rows are added
+        gh, go = self._padded(HONET_TRANS[1], N), self._padded(HONET_TRANS[3], N)
+        _, _, g_j, g_v = K.honet_recover_bwd(S["hst"], S["ost"], cam_intr, S["joints"], S["verts"], can, ccan,
+                                             (self.obj_trans_factor, self.obj_scale_factor), self.inp_res,
+                                             {k: c(g) for k, g in zip(HONET_GEO, g_geo)}, g_hand_st=gh[:, :3], g_obj_st=go[:, :6])
+        if g_hst is not None:
+            gh[:, :3] += g_hst
+        if g_ost is not None:
+            go[:, :6] += g_ost
+        if g_joints is not None:
+            g_j += g_joints
+        if g_verts is not None:
+            g_v += g_verts
+        gh1 = self._hand_branch_backward(S, g_pose, g_shape, g_v, g_j, g_full)
+        gm1 = self._transhead_backward(S, gh, HONET_TRANS[0], HONET_TRANS[1], "m1")
+        go1 = self._transhead_backward(S, go, HONET_TRANS[2], HONET_TRANS[3], "o1")
+        # res_layer4_mean feeds three branches: ManoBranch + hand TransHead + object TransHead, in that order
+        wt = self._wt
+        g_mean = (K.linear_dgrad(gh1, wt(HEADS[0])) + K.linear_dgrad(gm1, wt(HONET_TRANS[0]))) + K.linear_dgrad(go1, wt(HONET_TRANS[2]))
+        self.net.backward(g_mean=g_mean)
+
+    def forward(self, inputs: Dict):
+        image, xpad = self._image_of(inputs)
+        geo = self._geo_of(inputs)
+        if self.training and torch.is_grad_enabled():
+            out = _HoBridge.apply(self.flat_param, self, image, xpad, geo)
+        else:
+            with torch.no_grad():
+                out = self._run(image, xpad, False, geo)
+        pose, shape, verts, joints, full, hst, ost = out[:7]
+        B = hst.shape[0]
+        res = {"hand_verts_3d": verts, "joints_3d": joints, "mano_shape": shape, "mano_pca_pose": pose, "mano_full_pose": full}
+        res.update(zip(HONET_GEO, out[7:]))
+        h_scale, h_trans, o_scale, o_trans = hst[:, :1], hst[:, 1:], ost[:, :1], ost[:, 1:3]
+        res.update(hand_pred_trans=h_trans, hand_pred_scale=h_scale, hand_trans=h_trans.unsqueeze(1) * self.obj_trans_factor,
+                   hand_scale=h_scale.reshape(B, 1, 1) * self.obj_scale_factor, obj_pred_scale=o_scale, obj_pred_trans=o_trans,
+                   obj_rot=ost[:, 3:], obj_scale=o_scale.reshape(B, 1, 1) * self.obj_scale_factor,
+                   obj_trans=o_trans.unsqueeze(1) * self.obj_trans_factor, boxroot_3d_abs=res["obj_center"])
+        return res

@@ -395,6 +395,33 @@ def gt_core_batch(K, j3d, j2d, c3d, c2d, corners_can, obj_transf, center, scale,
     return out
 
 
+def mesh_vertex_table(assets, n):
+    """[n_obj, n, 3] float32: n canonical vertices of every object of the scene assets, evenly spaced over its vertex list (an object
+    with fewer than n vertices repeats them, as the padded collate does)."""
+    out = np.zeros((assets.n_obj, n, 3), np.float32)
+    for i in range(assets.n_obj):
+        v = assets.obj_verts[assets.obj_vert_off[i]:assets.obj_vert_off[i + 1]]
+        out[i] = v[(np.arange(n) * len(v)) // n if len(v) >= n else np.arange(n) % len(v)]
+    return out
+
+
+def add_mesh_queries(batch, table, obj_id, hand_verts, obj_pose):
+    """The mesh queries HoNet and ObjLoss / ManoLoss's vertex term read, from what a synthetic batch already holds (torch ops on the
+    batch's device).  table [n_obj,n,3] (mesh_vertex_table), obj_id [B]; hand_verts [B,778,3] and obj_pose [B,4,4]: the epoch's
+    un-augmented camera-frame hand vertices and object pose.  Writes into `batch`
+      OBJ_VERTS_CAN [B,n,3] = table[obj_id]
+      OBJ_VERTS_3D  [B,n,3] = R . can + t - root          (R | t = OBJ_TRANSF, root = ROOT_JOINT)
+      hand_verts_3d [B,778,3] = rm . hand_verts - root     (rm = R . obj_pose_R^T: the in-plane rotation of the augmentation)"""
+    T, root = batch[Queries.OBJ_TRANSF], batch[Queries.ROOT_JOINT]
+    can = table[obj_id]
+    R = T[:, :3, :3]
+    rm = R @ obj_pose[:, :3, :3].to(R.dtype).transpose(1, 2)
+    batch[Queries.OBJ_VERTS_CAN] = can
+    batch[Queries.OBJ_VERTS_3D] = can @ R.transpose(1, 2) + T[:, None, :3, 3] - root[:, None]
+    batch["hand_verts_3d"] = hand_verts.to(R.dtype) @ rm.transpose(1, 2) - root[:, None]
+    return batch
+
+
 # --------------------------------------------------------------------------- the loader
 class LazyImageBatch(dict):
     """A batch dict whose `image` entry (the reference's collated float CHW image, rendered_dataset.py:267-271) is produced on first
@@ -521,6 +548,10 @@ class ArtiBoostLoader:
         self.update_method_key = cfg.get("UPDATE_METHOD", "method_1")
         self.n_epochs = cfg.get("EPOCH", 100)
         self.use_synth = self.synth_len > 0
+        # MANAGER.MESH_QUERIES: n > 0 -- the batches of __iter__ (the eager route) also carry OBJ_VERTS_CAN / OBJ_VERTS_3D [B,n,3] and
+        # hand_verts_3d (add_mesh_queries): what HoNet, ObjLoss and ManoLoss's vertex term read.  Absent / 0: batches as before.
+        self.mesh_queries = int(cfg.get("MESH_QUERIES", 0) or 0)
+        self._mesh_table = None
         self._seed = random_seed
         self.rng = np.random.default_rng(random_seed)
         self.torch_gen = torch.Generator().manual_seed(random_seed)
@@ -817,7 +848,20 @@ class ArtiBoostLoader:
             self.render_into(static, want_chw=not lazy)
             items = {k: v for k, v in static.items() if not k.startswith("_")}
             items[IMAGE_PLANE_KEY] = PlaneTag(plane)
+            self.add_mesh_queries(items, static)
             yield LazyImageBatch(items, (lambda: chw_from_padded(pad, plane)) if lazy else None)
+
+    def add_mesh_queries(self, items, static=None):
+        """MANAGER.MESH_QUERIES: writes the mesh queries (add_mesh_queries) of the batch staged in `static` (default: `items` itself, a
+        static batch an eager loop feeds to the model directly) into `items`; nothing without the key."""
+        if not self.mesh_queries:
+            return items
+        static = items if static is None else static
+        if self._mesh_table is None:
+            self._mesh_table = torch.from_numpy(mesh_vertex_table(self.assets, self.mesh_queries)).to(static[SynthQueries.OBJ_ID].device)
+        off = SAMPLE_DTYPE.fields["obj_pose"][1]
+        pose = static["_samples"][:, off:off + 64].contiguous().view(torch.float32).view(-1, 4, 4)
+        return add_mesh_queries(items, self._mesh_table, static[SynthQueries.OBJ_ID], static["_hand_verts"], pose)
 
     # ------------------------------------------------------------------ mining (artiboost_loader.py:292-340,503-598)
     def get_evaluator_result(self, evaluator):

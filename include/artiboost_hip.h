@@ -571,6 +571,38 @@ int ab_mano_pca_bwd(const float* pose_coeffs, const float* betas, const float* c
                     const float* weights, int ncomps, int center_idx, int B, const float* g_verts, const float* g_joints,
                     const float* g_full_pose, float* g_pose_coeffs, float* g_betas, void* stream);
 
+/* ---- HoNet's recovery stage, forward and backward (the hand-mesh + object-vertices model's per-vertex stage) ------------------------
+ * anakin/models/honetMANO.py:113-253 (recover_3d_proj, recover_mano, recover_object, forward).  hand_st: B rows of (scale, tx, ty),
+ * obj_st: B rows of (scale, tx, ty, axis-angle 3), each addressed through its row pitch in floats (the first columns of padded head
+ * outputs); cam_intr [B,9]; joints_3d [B,21,3] and hand_verts_3d [B,778,3] (MANO's, centred); obj_verts_can [B,N,3]; corners_can
+ * [B,8,3] or NULL (then the three corner outputs are not touched).  Placement of both (honetMANO.py:126-139), focal = cam_intr[0]:
+ *   Z0 = focal * scale * scale_factor + off_z,  XY0 = (trans * trans_factor + (img_w, img_h) / 2 - (cam_intr[2], cam_intr[5])) * Z0 / focal
+ * root_joint / obj_center [B,3] = (XY0, Z0) of the hand / object; rotmat [B,9] = Rodrigues of the axis-angle (the device function of the
+ * MANO kernels); *_abs = point + root_joint (hand) or rotmat . canonical + obj_center (object, corners); *_2d = cam_intr . p over its
+ * depth; corners_3d / obj_verts_3d = *_abs - root_joint (obj_verts_3d may be NULL: not written).  N >= 1, any value.
+ * ab_honet_recover_bwd: the exact reverse.  g_<output>: the gradient of each forward output, NULL = zero; the forward's inputs are read
+ * again (nothing is saved between the launches).  Writes (overwrites) g_hand_st B rows of 3, g_obj_st B rows of 6 (row pitches
+ * g_hand_pitch / g_obj_pitch), g_joints_3d [B,21,3], g_hand_verts_3d [B,778,3].  workspace: ab_honet_recover_workspace(B, N) bytes.
+ * The vertices of a sample are split over ab_honet_recover_chunks(N) workgroups (+ one for the hand and the corners); the per-chunk sums
+ * are added in chunk order by a second launch.  No float atomics, fixed-order reductions: bit-reproducible.                            */
+int ab_honet_recover_chunks(int N);
+long ab_honet_recover_workspace(int B, int N);
+int ab_honet_recover_fwd(const float* hand_st, int hand_pitch, const float* obj_st, int obj_pitch, const float* cam_intr,
+                         const float* joints_3d, const float* hand_verts_3d, const float* obj_verts_can, const float* corners_can,
+                         int B, int N, float trans_factor, float scale_factor, float img_w, float img_h, float off_z,
+                         float* root_joint, float* joints_3d_abs, float* hand_verts_3d_abs, float* joints_2d, float* hand_verts_2d,
+                         float* obj_center, float* rotmat, float* obj_verts_3d_abs, float* obj_verts_2d, float* corners_3d_abs,
+                         float* corners_2d, float* corners_3d, float* obj_verts_3d, void* stream);
+int ab_honet_recover_bwd(const float* hand_st, int hand_pitch, const float* obj_st, int obj_pitch, const float* cam_intr,
+                         const float* joints_3d, const float* hand_verts_3d, const float* obj_verts_can, const float* corners_can,
+                         int B, int N, float trans_factor, float scale_factor, float img_w, float img_h, float off_z,
+                         const float* g_root_joint, const float* g_joints_3d_abs, const float* g_hand_verts_3d_abs,
+                         const float* g_joints_2d, const float* g_hand_verts_2d, const float* g_obj_center, const float* g_rotmat,
+                         const float* g_obj_verts_3d_abs, const float* g_obj_verts_2d, const float* g_corners_3d_abs,
+                         const float* g_corners_2d, const float* g_corners_3d, const float* g_obj_verts_3d, float* g_hand_st,
+                         int g_hand_pitch, float* g_obj_st, int g_obj_pitch, float* g_joints_3d, float* g_hand_verts_3d,
+                         void* workspace, void* stream);
+
 /* ---- Hand-mesh fitting of the submission pass (IKNet initialisation + 20 Adam steps of a MANO fit, all hands in one launch) -----
  * anakin/postprocess/iknet/fittingunit.py:112-225 (FittingUnit.__call__: residuals :63-80, geo :43-60, mano_de :83-97) and
  * utils.py:13-41 (quaternion -> axis-angle).  quat [B,64]: the raw IKNet output (16 quaternions, normalised here); pred_joints
@@ -681,6 +713,8 @@ int ab_draw_meshes(const float* hand_verts, const int32_t* hand_faces, int nhf, 
  * @check ab_mano_lbs: pose >= B*48; betas >= B*10; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; hands_mean >= 45; verts >= B*778*3; joints >= B*21*3; T_abs >= B*16*16
  * @check ab_mano_pca_fwd: pose_coeffs >= B*(3+ncomps); betas >= B*10; comps >= ncomps*45; hands_mean >= 45; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; verts >= B*778*3; joints >= B*21*3; full_pose >= B*48
  * @check ab_mano_pca_bwd: pose_coeffs g_pose_coeffs >= B*(3+ncomps); betas g_betas >= B*10; comps >= ncomps*45; hands_mean >= 45; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; g_verts >= B*778*3; g_joints >= B*21*3; g_full_pose >= B*48
+ * @check ab_honet_recover_fwd: strided: hand_st obj_st; cam_intr rotmat >= B*9; joints_3d joints_3d_abs >= B*63; hand_verts_3d hand_verts_3d_abs >= B*778*3; obj_verts_can obj_verts_3d_abs obj_verts_3d >= B*N*3; corners_can corners_3d_abs corners_3d >= B*24; root_joint obj_center >= B*3; joints_2d >= B*42; hand_verts_2d >= B*778*2; obj_verts_2d >= B*N*2; corners_2d >= B*16
+ * @check ab_honet_recover_bwd: strided: hand_st obj_st g_hand_st g_obj_st; cam_intr g_rotmat >= B*9; joints_3d g_joints_3d_abs g_joints_3d >= B*63; hand_verts_3d g_hand_verts_3d_abs g_hand_verts_3d >= B*778*3; obj_verts_can g_obj_verts_3d_abs g_obj_verts_3d >= B*N*3; corners_can g_corners_3d_abs g_corners_3d >= B*24; g_root_joint g_obj_center >= B*3; g_joints_2d >= B*42; g_hand_verts_2d >= B*778*2; g_obj_verts_2d >= B*N*2; g_corners_2d >= B*16; bytes workspace >= ab_honet_recover_workspace(B,N)
  * @check ab_mano_fit: quat >= B*64; pred_joints >= B*63; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; J_template >= 48; J_shapedirs >= 480; params adam_m adam_v grad >= B*59; verts >= B*778*3; joints >= B*63; loss >= B*n_iter
  * @check ab_draw_meshes: hand_verts >= B*778*3; hand_faces >= nhf*3; adj_off >= 779; adj_face >= nadj; obj_verts obj_normals >= nov*3; obj_faces >= nof*3; obj_vert_off obj_face_off >= n_obj+1; obj_id >= B; obj_rot >= B*9; obj_tsl >= B*3; corners >= B*24; cam_intr >= B*9; image >= B*3*H*W; out >= B*H*4*W*3; bytes workspace >= ab_draw_workspace_bytes(B,W,H,max_obj_verts)
  */

@@ -288,6 +288,8 @@ def main():
             ts.prime(loader, 0)
             for bi in range(len(loader)):
                 ts.stage(loader, bi)
+                if not ts.use_graph:                                 # MANAGER.MESH_QUERIES, eager route only: the static graph batches stay as staged
+                    loader.add_mesh_queries(ts.static)
                 preds, losses, _ = ts()
                 if rec is not None:
                     rec.collect()
