@@ -468,6 +468,11 @@ def conv2d_fwd_x3(x, w_split, stride, pad, bias=None, want_stats=False, relu=Fal
     xh, xl = _planes(x)
     N, H, W, Cin = xh.shape
     _, Cout, kh, kw, _ = w_split.shape
+    if Cin % 32:        # the kernels read 32-channel chunks: zero planes up to the next chunk add exactly nothing to any output
+        padc = -Cin % 32
+        zpad = torch.nn.functional.pad
+        xh, xl, w_split = zpad(xh, (0, padc)), zpad(xl, (0, padc)), zpad(w_split, (0, padc))
+        Cin += padc
     Ho, Wo = conv_out(H, kh, stride, pad), conv_out(W, kw, stride, pad)
     y = torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=xh.device)
     lib = L.lib()

@@ -231,7 +231,8 @@ int ab_conv2d_stem_wgrad_x3(const void* xpad_hi, const void* xpad_lo, const void
 /* fp32 elementwise passes that write a convolution operand directly as split planes (no separate ab_split_f32 pass):
  * ab_bn_apply_x3 = ab_bn_apply on fp32 with out (optional fp32 copy, may be NULL) + planes; ab_bn_bwd_x3 = ab_bn_bwd /
  * ab_bn_bwd_apply on fp32 with dy as planes (nparts_given = 0: run the reduction into `part`; > 0: `part` holds that many
- * already reduced rows).  resnet.py:85-101, simplebaseline.py:171-172.                                             */
+ * already reduced rows).  resnet.py:85-101, simplebaseline.py:171-172.  ab_bn_apply_x3 / _respl take C % 4 == 0 (8 channels per
+ * thread, 4 where C % 8 == 4: the same bits); the other forms C % 8 == 0.                                            */
 int ab_bn_apply_x3(const float* y, const float* res, const float* bnp, long M, int C, int relu, float* out, void* out_hi,
                    void* out_lo, void* stream);
 /* ... the residual given as the raw output res_y of the block's downsample conv and ITS BatchNorm parameters res_bnp

@@ -191,7 +191,7 @@ def _segment_runs(runs, size, heat, B, seed, steps, dtype, build_optimizer):
         runs[seg] = (losses, evals, hb.store.flat.detach().cpu().clone(), hb.store.stats.cpu().clone())
 
 
-@pytest.mark.parametrize("g,B", [(224, 2), (256, 3)])
+@pytest.mark.parametrize("g,B", [(224, 2), (256, 3), (256, 4)])
 def test_eval_forward_with_folded_batchnorm_is_bit_identical(g, B, monkeypatch):
     """Eval-mode forward (BASELINE configs[1]: submit_reload.py / the TEST pass, resnet.py:85-101 under eval()) with the
     BatchNorm of every 3x3/s1 convolution folded into the conv epilogue (ab_conv2d_fwd_x3_evalbn: the fp32 conv outputs are never
