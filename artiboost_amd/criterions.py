@@ -654,6 +654,101 @@ class FusedRegCriterion:
         return {k: (None if s is None else v[s]) for k, s in self.key_slots.items()}
 
 
+class FusedMeshCriterion:
+    """HoNet's criterion in ONE HIP kernel + a finalize pass (ab_honet_loss, csrc/honet_loss.hip): ManoLoss with all four terms -- the
+    hand-vertex term included -- + ObjLoss + per-sample EPE + the gradient of final_loss wrt joints_3d_abs, hand_verts_3d_abs,
+    obj_verts_3d_abs, mano_pca_pose and mano_shape.  Built from a `Criterion` whose list is [ManoLoss] or [ManoLoss, ObjLoss]; anything else
+    raises NotImplementedError (the registry losses then run through autograd).  A term whose target the batch does not carry is dropped, as
+    the registry classes drop it (`key in targs`); `example_batch` fixes which ones the loss record reports."""
+
+    LOSS_WIDTH = 8           # floats of the kernel's loss vector
+    _SLOTS = ("mano_shape", "mano_pca_pose", "joints_3d_loss", "hand_verts_3d_loss", "obj_verts_3d_loss", "final_loss")
+    _TARGET = {"joints_3d_loss": Queries.JOINTS_3D, "hand_verts_3d_loss": "hand_verts_3d", "obj_verts_3d_loss": Queries.OBJ_VERTS_3D}
+
+    def __init__(self, criterion: Criterion, ncomps, example_batch=None):
+        import ctypes
+        self.crit = criterion
+        self.ncomps = int(ncomps)
+        self.mano = self.obj = None
+        for loss in criterion.loss_list:
+            if isinstance(loss, ManoLoss) and self.mano is None and self.obj is None:
+                self.mano = loss
+            elif isinstance(loss, ObjLoss) and self.mano is not None and self.obj is None:
+                self.obj = loss
+            else:
+                raise NotImplementedError(f"{type(loss).__name__} is not part of the fused mesh criterion ([ManoLoss] or [ManoLoss, ObjLoss])")
+        if self.mano is None:
+            raise NotImplementedError("the fused mesh criterion needs ManoLoss in the list")
+        m, lam = self.mano, criterion.loss_lambdas
+        self._on = {"mano_shape": bool(m.lambda_shape_reg), "mano_pca_pose": bool(m.lambda_pose_reg), "joints_3d_loss": bool(m.lambda_joints_3d),
+                    "hand_verts_3d_loss": bool(m.lambda_hand_verts_3d)}
+        w = [m.lambda_shape_reg, m.lambda_pose_reg, m.lambda_joints_3d, m.lambda_hand_verts_3d, 0.0, lam["ManoLoss"], 0.0]
+        if self.obj is not None:
+            self._on["obj_verts_3d_loss"] = bool(self.obj.lambda_obj_verts_3d)
+            w[4], w[6] = self.obj.lambda_obj_verts_3d, lam["ObjLoss"]
+        self.weights = (ctypes.c_float * 7)(*[float(x) for x in w])
+        self.key_slots = self._slots_for(example_batch)
+        keys = [None] * self.LOSS_WIDTH
+        for k, s in self.key_slots.items():
+            if s is not None:
+                keys[s] = k
+        self.LOSS_KEYS = tuple(keys)
+        self.out = None
+
+    def _slots_for(self, targs):
+        """key -> slot of the loss vector (None: the registry route reports None), in the registry's own update order."""
+        d = {}
+        for k, on in self._on.items():
+            t = self._TARGET.get(k)
+            d[k] = self._SLOTS.index(k) if on and (t is None or targs is None or t in targs) else None
+        d["final_loss"] = 5
+        return d
+
+    def draw(self, dev):
+        """No loss of this criterion draws random numbers; kept so that TrainStep treats every fused criterion alike."""
+
+    def _alloc(self, B, N, dev):
+        from . import _lib as L
+        z = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)   # noqa: E731
+        self.out = dict(sample_part=z(B, 8), losses=z(self.LOSS_WIDTH), g_joints_3d_abs=z(B, 21, 3), g_hand_verts_3d_abs=z(B, 778, 3),
+                        g_obj_verts_3d_abs=z(B, N, 3) if N else None, g_mano_pca_pose=z(B, 3 + self.ncomps), g_mano_shape=z(B, 10),
+                        workspace=torch.empty((L.lib().ab_honet_loss_workspace(L.i(B), L.i(N)),), dtype=torch.uint8, device=dev))
+        self._shape = (B, N, dev)
+
+    def __call__(self, joints_3d_abs, hand_verts_3d_abs, obj_verts_3d_abs, corners_3d_abs, mano_pca_pose, mano_shape, targs, backward=True):
+        """The model's absolute predictions (fp32, contiguous; corners_3d_abs may be None; obj_verts_3d_abs is not read without ObjLoss)
+        and the batch.  -> dict: losses [8], sample_part [B,8] and, with backward, the five g_* tensors (persistent buffers)."""
+        from . import _lib as L
+        B, dev = joints_3d_abs.shape[0], joints_3d_abs.device
+        if mano_pca_pose.shape[1] != 3 + self.ncomps:
+            raise ValueError(f"mano_pca_pose has {mano_pca_pose.shape[1]} columns, ncomps = {self.ncomps}")
+        if self.obj is None:
+            obj_verts_3d_abs = None
+        N = obj_verts_3d_abs.shape[1] if obj_verts_3d_abs is not None else 0
+        if self.out is None or self._shape != (B, N, dev):
+            self._alloc(B, N, dev)
+        o = self.out
+        self._last = self._slots_for(targs)
+        t = lambda k: targs[self._TARGET[k]] if self._last[k] is not None else None   # noqa: E731
+        tc = targs.get(Queries.CORNERS_3D) if corners_3d_abs is not None else None
+        g = lambda k: o[k] if backward else None   # noqa: E731
+        L.check(L.lib().ab_honet_loss(
+            L.ptr(joints_3d_abs), L.ptr(hand_verts_3d_abs), L.ptr(obj_verts_3d_abs), L.ptr(corners_3d_abs if tc is not None else None),
+            L.ptr(mano_pca_pose), L.ptr(mano_shape), L.ptr(targs[Queries.ROOT_JOINT]),
+            # (the joint target also feeds the EPE: it is passed whenever the batch has it, the weight decides the loss term)
+            L.ptr(targs.get(Queries.JOINTS_3D)), L.ptr(t("hand_verts_3d_loss")),
+            L.ptr(t("obj_verts_3d_loss") if self.obj is not None else None), L.ptr(tc), L.i(B), L.i(N), L.i(self.ncomps), self.weights,
+            L.ptr(o["sample_part"]), L.ptr(o["losses"]), L.ptr(g("g_joints_3d_abs")), L.ptr(g("g_hand_verts_3d_abs")),
+            L.ptr(g("g_obj_verts_3d_abs")), L.ptr(g("g_mano_pca_pose")), L.ptr(g("g_mano_shape")), L.ptr(o["workspace"]), L.stream()),
+            "ab_honet_loss")
+        return o
+
+    def losses_dict(self):
+        """Host view of the loss scalars of the last call under the keys of Criterion.compute_losses (synchronises)."""
+        v = self.out["losses"].cpu()
+        return {k: (None if s is None else v[s]) for k, s in self._last.items()}
+
+
 # ---- mesh-level losses (DESIGN.md section 19) --------------------------------------------------------------------------------------------
 def _refuse_device(name, dev):
     """No HIP kernel backs these two losses yet, and eager device torch ops are not a route of this build (a brute-force [N,M] distance

@@ -954,6 +954,29 @@ def honet_recover_bwd(hand_st, obj_st, cam_intr, joints_3d, hand_verts_3d, obj_v
     return g_hand_st, g_obj_st, g_j, g_v
 
 
+def mesh_queries(table, obj_id, obj_transf, root_joint, hand_verts, samples, pose_offset, out=None):
+    """ab_mesh_queries: synth.add_mesh_queries in one capturable launch.  table [n_obj,n,3] f32, obj_id int64 [B], obj_transf [B,4,4],
+    root_joint [B,3], hand_verts [B,778,3] f32; samples: the uint8 [B, pitch] render records, whose `obj_pose` field at byte pose_offset is
+    read in place.  out: (obj_verts_can [B,n,3], obj_verts_3d [B,n,3], hand_verts_3d [B,778,3]) to write into (allocated when None)."""
+    B, n = obj_id.shape[0], table.shape[1]
+    if samples.dtype != torch.uint8 or samples.dim() != 2 or samples.shape[0] != B or obj_id.dtype != torch.int64:
+        raise ValueError(f"mesh_queries: samples must be uint8 [{B}, pitch] and obj_id int64, got {samples.dtype} {tuple(samples.shape)} / {obj_id.dtype}")
+    for t, numel, what in ((table, table.shape[0] * n * 3, "table"), (obj_transf, B * 16, "obj_transf"), (root_joint, B * 3, "root_joint"),
+                           (hand_verts, B * 778 * 3, "hand_verts")):
+        if t.dtype != torch.float32 or t.numel() != numel:
+            raise ValueError(f"mesh_queries: {what} must be fp32 with {numel} elements, got {t.dtype} {tuple(t.shape)}")
+    if out is None:
+        z = lambda *s: torch.empty(s, dtype=torch.float32, device=table.device)      # noqa: E731
+        out = (z(B, n, 3), z(B, n, 3), z(B, 778, 3))
+    can, v3d, hv = out
+    if tuple(can.shape) != (B, n, 3) or tuple(v3d.shape) != (B, n, 3) or tuple(hv.shape) != (B, 778, 3) or any(t.dtype != torch.float32 for t in out):
+        raise ValueError(f"mesh_queries: outputs must be fp32 [{B},{n},3], [{B},{n},3], [{B},778,3]")
+    L.check(L.lib().ab_mesh_queries(L.ptr(table), L.i(table.shape[0]), L.i(n), L.ptr(obj_id), L.ptr(obj_transf), L.ptr(root_joint),
+                                    L.ptr(hand_verts), L.ptr(samples), L.l(samples.stride(0)), L.l(pose_offset), L.i(B), L.ptr(can), L.ptr(v3d),
+                                    L.ptr(hv), L.stream()), "ab_mesh_queries")
+    return out
+
+
 FIT_NP = 59             # parameters per hand of ab_mano_fit: so3 48 | beta 10 | bone 1
 
 

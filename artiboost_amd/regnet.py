@@ -283,7 +283,8 @@ class HoNetHIP(HOPRegNetHIP):
     and MANO kernels, two TransHeads (512 -> 256 -> 3 / 6) on the fp32 linear kernels, and the recovery stage -- placement from the predicted
     scale / translation, Rodrigues, rotation of the canonical object vertices, every projection -- as ab_honet_recover_fwd / _bwd.  One
     autograd Function (_HoBridge) whose outputs are the differentiable entries of the returned dict; the dict is the torch module's, key
-    for key.  No fused criterion and no graph capture: TrainStep takes its eager route."""
+    for key.  ARCH.FUSED_MESH_STEP: true -- TrainStep runs the model without autograd (criterions.FusedMeshCriterion on the recovery
+    outputs) and replays the step as two hipGraphs; without it TrainStep takes its eager route."""
     CHECKPOINT_NAME = "HoNet"
 
     TORCH_MODULE = HoNet
@@ -291,12 +292,14 @@ class HoNetHIP(HOPRegNetHIP):
 
     def _read_cfg(self, cfg):
         if self.FUSED_STEP:
-            raise NotImplementedError("HoNet with FUSED_STEP: true -- there is no fused criterion and no captured step for HoNet; "
-                                      "train it on the eager route (leave ARCH.FUSED_STEP out)")
+            raise NotImplementedError("HoNet with FUSED_STEP: true -- that key selects HOPRegNet's fused criterion; HoNet's fused mesh "
+                                      "criterion and captured step are ARCH.FUSED_MESH_STEP: true (leave ARCH.FUSED_STEP out)")
+        self.FUSED_MESH_STEP = bool(cfg.get("FUSED_MESH_STEP", False))
         self.obj_trans_factor, self.obj_scale_factor = float(cfg["OBJ_TRANS_FACTOR"]), float(cfg["OBJ_SCALE_FACTOR"])
 
     def _geo_of(self, inputs):
-        """The batch's geometric inputs of the recovery stage on the device: (cam_intr, obj_verts_can, corners_can | None)."""
+        """The batch's geometric inputs of the recovery stage on the device: (cam_intr, obj_verts_can, corners_can | None).  An fp32
+        contiguous tensor already on the device is handed on as it is (no copy): a captured step reads TrainStep's static tensors."""
         dev = self.store.device
         f = lambda t: t.to(dev, torch.float32, non_blocking=True).contiguous()      # noqa: E731
         img = inputs.get(Queries.IMAGE)
@@ -360,6 +363,10 @@ class HoNetHIP(HOPRegNetHIP):
         else:
             with torch.no_grad():
                 out = self._run(image, xpad, False, geo)
+        return self._assemble(out)
+
+    def _assemble(self, out):
+        """_run's outputs -> the torch module's dict, key for key."""
         pose, shape, verts, joints, full, hst, ost = out[:7]
         B = hst.shape[0]
         res = {"hand_verts_3d": verts, "joints_3d": joints, "mano_shape": shape, "mano_pca_pose": pose, "mano_full_pose": full}

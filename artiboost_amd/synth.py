@@ -863,6 +863,28 @@ class ArtiBoostLoader:
         pose = static["_samples"][:, off:off + 64].contiguous().view(torch.float32).view(-1, 4, 4)
         return add_mesh_queries(items, self._mesh_table, static[SynthQueries.OBJ_ID], static["_hand_verts"], pose)
 
+    MESH_QUERY_KEYS = (Queries.OBJ_VERTS_CAN, Queries.OBJ_VERTS_3D, "hand_verts_3d")
+
+    def mesh_queries_into(self, static):
+        """MANAGER.MESH_QUERIES on the captured route: the same three entries as add_mesh_queries, written by ONE kernel launch
+        (ab_mesh_queries) into tensors `static` keeps -- fixed addresses, no allocation after the first call, no host read, so the call
+        can sit inside a hipGraph right after render_into.  The first call (outside any capture) creates the vertex table and the three
+        tensors; nothing without the key."""
+        if not self.mesh_queries:
+            return static
+        from . import kernels as K
+        dev = static[SynthQueries.OBJ_ID].device
+        if self._mesh_table is None:
+            self._mesh_table = torch.from_numpy(mesh_vertex_table(self.assets, self.mesh_queries)).to(dev)
+        B, n = static[SynthQueries.OBJ_ID].shape[0], self.mesh_queries
+        for k, shp in zip(self.MESH_QUERY_KEYS, ((B, n, 3), (B, n, 3), (B, 778, 3))):
+            if k not in static:
+                static[k] = torch.zeros(shp, dtype=torch.float32, device=dev)
+        K.mesh_queries(self._mesh_table, static[SynthQueries.OBJ_ID], static[Queries.OBJ_TRANSF], static[Queries.ROOT_JOINT],
+                       static["_hand_verts"], static["_samples"], SAMPLE_DTYPE.fields["obj_pose"][1],
+                       out=tuple(static[k] for k in self.MESH_QUERY_KEYS))
+        return static
+
     # ------------------------------------------------------------------ mining (artiboost_loader.py:292-340,503-598)
     def get_evaluator_result(self, evaluator):
         """artiboost_loader.py:301-327: average of the per-(object, view, grasp) measures of every validation metric."""

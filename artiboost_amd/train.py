@@ -86,6 +86,11 @@ class TrainStep:
         # run; it is written straight into the learn buffer, which step i no longer reads by then -- no second image, no
         # copy.  Measured on one MI355X: 9505 vs 9890 samples/s without it -- like the other two-stream variants (see
         # DESIGN.md section 5) concurrency across streams costs more here than it hides; opt-in only.
+        # HoNet built with ARCH.FUSED_MESH_STEP (below): its mesh queries are made from the render inputs of the batch being learned, which
+        # the pipelined modes hold one batch ahead -- the step renders and learns in order instead
+        self.mesh = bool(getattr(self.hb, "FUSED_MESH_STEP", False))
+        if self.mesh:
+            pipeline_render = False
         self.pipeline_opt = bool(pipeline_render == "opt" and renderer is not None)
         self.g_render = None
         self.pipeline = bool(pipeline_render and not self.pipeline_opt and renderer is not None)
@@ -109,6 +114,7 @@ class TrainStep:
             self.rstatic["image_nhwc4_padded"] = torch.zeros_like(self.static["image_nhwc4_padded"])
             self.render_stream = torch.cuda.Stream(device=self.dev)
         self.fused = None
+        self.mesh_queries = False
         # the key of this model's outputs in Arch's result dict: its config TYPE (the class name can differ: HOPRegNet on the HIP kernels)
         self.model_key = next((t for t, v in getattr(arch_model, "models", {}).items() if v["id"] == 0), type(self.hb).__name__)
         # HOPRegNet built with ARCH.FUSED_STEP: its own fused criterion (ab_reg_pose_loss) and two linear graphs; the trunk-only layout has no
@@ -124,6 +130,24 @@ class TrainStep:
                     self.fused = None
             if self.fused is None:
                 self.use_graph = False
+            fused_criterion = False
+        elif self.mesh:
+            # HoNet built with ARCH.FUSED_MESH_STEP: the fused mesh criterion (ab_honet_loss) on the recovery outputs and the same two linear
+            # graphs.  A loader with MANAGER.MESH_QUERIES writes the three mesh queries inside the captured region (one ab_mesh_queries
+            # launch after the render) into tensors allocated here, before the criterion looks at the batch and before any capture
+            self.split = False
+            if fused_criterion:
+                from .criterions import FusedMeshCriterion
+                if getattr(renderer, "mesh_queries", 0) and hasattr(renderer, "mesh_queries_into"):
+                    renderer.mesh_queries_into(self.static)
+                    self.mesh_queries = True
+                try:
+                    self.fused = FusedMeshCriterion(criterion, self.hb.ncomps, self.static)
+                except NotImplementedError:   # a loss outside the kernel: the registry losses through autograd, eagerly
+                    self.fused = None
+            if self.fused is None:
+                self.use_graph = False
+                self.mesh_queries = False     # (the eager loop calls loader.add_mesh_queries itself)
             fused_criterion = False
         elif not getattr(self.hb, "HAS_BOX_HEAD", True):             # SimpleBaseline: the fused pose/loss kernel is HybridBaseline's assembly
             fused_criterion = False
@@ -153,6 +177,8 @@ class TrainStep:
             return out
         if self.renderer is not None and not self.pipeline_opt:
             self.renderer.render_into(self.static)
+            if self.mesh_queries:
+                self.renderer.mesh_queries_into(self.static)
         return self._learn()
 
     def _launch_render_next(self):
@@ -187,6 +213,8 @@ class TrainStep:
         net.image_plane = getattr(self, "_plane", "f32") if st.get("image_nhwc4_padded") is not None else "f32"
         if self.reg:
             return self._fwd_bwd_reg()
+        if self.mesh:
+            return self._fwd_bwd_mesh()
         logits, _ = net.forward(image=st.get(Queries.IMAGE), xpad=st.get("image_nhwc4_padded"))
         kp3d, conf, stat = net.head_fwd(logits)
         o = self.fused(kp3d, net.last["box_raw"], net.last["box_raw"].shape[-1], st)
@@ -206,6 +234,24 @@ class TrainStep:
         bridge = {"hand_verts_3d": verts, "joints_3d": joints, "mano_shape": shape, "mano_pca_pose": pose, "mano_full_pose": full, "transf": transf}
         return bridge, o["losses"], o
 
+    def _fwd_bwd_mesh(self):
+        """HoNet: trunk + heads + MANO + recovery -> fused mesh criterion (+backward) -> recovery / MANO / heads / trunk backward, no
+        autograd.  The recovery stage reads the static batch's own tensors (cam_intr, obj_verts_can, corners_can): fixed addresses."""
+        from .regnet import HONET_GEO
+        hb, st = self.hb, self.static
+        geo = hb._geo_of(st)
+        out = hb._run(st.get(Queries.IMAGE), st.get("image_nhwc4_padded"), True, geo)
+        rec = dict(zip(HONET_GEO, out[7:]))
+        o = self.fused(rec["joints_3d_abs"], rec["hand_verts_3d_abs"], rec["obj_verts_3d_abs"], rec["corners_3d_abs"], out[0], out[1], st)
+        # the five gradients; the TransHead rows (g_hst / g_ost) and the untouched recovery outputs get none
+        hb._backward(o["g_mano_pca_pose"], o["g_mano_shape"], None, None, None, None, None, *(o.get("g_" + k) for k in HONET_GEO))
+        hb.flat_param.grad = hb.store.grad
+        return out, o["losses"], o
+
+    def _draw(self):
+        """Per-step host draws of the losses into their device buffers (outside the graphs); the mesh criterion has none."""
+        (self.fused if self.mesh and self.fused is not None else self.crit).draw(self.dev)
+
     _capturing_split = False
 
     def predictions(self):
@@ -214,6 +260,8 @@ class TrainStep:
         derived here (a few small device ops, outside the graphs)."""
         if self.fused is None:
             return self.out[0]
+        if self.mesh:     # HoNet's dict from the bridge outputs, as HoNetHIP.forward assembles it
+            return self.hb._assemble(self.out[0])
         if self.reg:      # HOPRegNet's 18 keys from the bridge outputs (the camera projections stay torch ops, as in its forward)
             from .hpregnet import combine_outputs, mano_outputs, object_outputs
             mano = {k: v for k, v in self.out[0].items() if k != "transf"}
@@ -291,7 +339,7 @@ class TrainStep:
         # afterwards, so a graph-replayed run is the same sequence of updates as the eager one, bit for bit, and a
         # checkpoint can be loaded before the first step.
         snap = self._snapshot()
-        self.crit.draw(self.dev)
+        self._draw()
         self.opt.advance_hyper()
         self.opt.graph_steps = 0
         torch.cuda.synchronize(self.dev)
@@ -364,7 +412,7 @@ class TrainStep:
             self.load_batch(batch)
         if not self.use_graph:
             if self.fused is not None:
-                self.crit.draw(self.dev)
+                self._draw()
             self.out = self._fwd_bwd()
             if self.pipeline_opt:
                 cur = torch.cuda.current_stream(self.dev)
@@ -379,7 +427,7 @@ class TrainStep:
         else:
             if self.g_fwd_bwd is None:
                 self._capture()
-            self.crit.draw(self.dev)
+            self._draw()
             self.opt.advance_hyper()
             self.g_fwd_bwd.replay()
             self.hb.store.num_batches_tracked += 1           # the replayed forward is a training-mode BatchNorm forward

@@ -604,6 +604,40 @@ int ab_honet_recover_bwd(const float* hand_st, int hand_pitch, const float* obj_
                          int g_hand_pitch, float* g_obj_st, int g_obj_pitch, float* g_joints_3d, float* g_hand_verts_3d,
                          void* workspace, void* stream);
 
+/* ---- HoNet's mesh queries and fused mesh criterion (csrc/honet_loss.hip): what a captured HoNet training step runs around the network ----
+ * ab_mesh_queries: artiboost_amd/synth.py add_mesh_queries in one launch.  table [n_obj,n,3] (synth.mesh_vertex_table), obj_id int64 [B],
+ * obj_transf [B,4,4] (R | t), root_joint [B,3], hand_verts [B,778,3] (the epoch's un-augmented camera-frame vertices); the object pose is
+ * read in place from the 96-byte render records: `samples` is their byte base, sample_pitch the record pitch and pose_offset the offset of
+ * the row-major 4x4 `obj_pose` field, both in bytes and multiples of 4.  Writes, in full,
+ *   obj_verts_can [B,n,3] = table[clamp(obj_id, 0, n_obj - 1)]   (bit copies; an id outside the table never reads outside it)
+ *   obj_verts_3d  [B,n,3] = R . can + t - root
+ *   hand_verts_3d [B,778,3] = (R . Rpose^T) . hand_verts - root
+ * No allocation, no host read, no atomics; any n >= 1, B >= 1.
+ * ab_honet_loss: anakin/criterions/honetloss.py:12-97 (ManoLoss: mean(shape^2), mean(pose[:, 3:]^2), joint MSE, hand-vertex MSE; ObjLoss:
+ * object-vertex MSE), criterion.py:57-67, the per-sample EPE of anakin/metrics/val_metric.py:84-106, and their autograd backward.
+ * Predictions: joints_3d_abs [B,21,3], hand_verts_3d_abs [B,778,3], obj_verts_3d_abs [B,N,3] (NULL with N = 0: no object term),
+ * corners_3d_abs [B,8,3] or NULL, mano_pca_pose [B,3+ncomps], mano_shape [B,10].  Targets, root-relative (the kernel adds root_joint
+ * [B,3], the TARGET's root): joints_3d, hand_verts_3d, obj_verts_3d, corners_3d; a NULL target drops its term (value 0, zero gradient).
+ * weights7_host (HOST pointer) = LAMBDA_SHAPE_REG, LAMBDA_POSE_REG, ManoLoss's LAMBDA_JOINTS_3D, LAMBDA_HAND_VERTS_3D, LAMBDA_OBJ_VERTS_3D,
+ * LAMBDAS[ManoLoss], LAMBDAS[ObjLoss].  The means are over B*10, B*ncomps, B*63, B*2334, B*N*3 elements.
+ * Outputs: losses float[8] = mano_shape, mano_pca_pose, joints_3d_loss, hand_verts_3d_loss, obj_verts_3d_loss, final_loss, batch-mean joint
+ * EPE, batch-mean corner EPE (mm); sample_part [B,8] = the sample's five squared sums, [5] / [6] its joint / corner EPE in mm (0 without
+ * the target or the corners), [7] zero.  Gradients of final_loss, each written (overwritten) when its pointer is not NULL: g_joints_3d_abs,
+ * g_hand_verts_3d_abs, g_obj_verts_3d_abs, g_mano_pca_pose (root-rotation columns zero), g_mano_shape.  workspace:
+ * ab_honet_loss_workspace(B, N) bytes.  A sample's object vertices are split over ab_honet_loss_chunks(N) workgroups (+ one for the hand);
+ * each reduces in a fixed order into its own row, a finalize launch adds the rows in chunk order and the samples in double.  No float
+ * atomics: two calls give the same bits, and the loss bits do not depend on which gradients are asked for.                              */
+int ab_mesh_queries(const float* table, int n_obj, int n, const int64_t* obj_id, const float* obj_transf, const float* root_joint,
+                    const float* hand_verts, const uint8_t* samples, long sample_pitch, long pose_offset, int B, float* obj_verts_can,
+                    float* obj_verts_3d, float* hand_verts_3d, void* stream);
+int ab_honet_loss_chunks(int N);
+long ab_honet_loss_workspace(int B, int N);
+int ab_honet_loss(const float* joints_3d_abs, const float* hand_verts_3d_abs, const float* obj_verts_3d_abs, const float* corners_3d_abs,
+                  const float* mano_pca_pose, const float* mano_shape, const float* root_joint, const float* joints_3d,
+                  const float* hand_verts_3d, const float* obj_verts_3d, const float* corners_3d, int B, int N, int ncomps,
+                  const float* weights7_host, float* sample_part, float* losses, float* g_joints_3d_abs, float* g_hand_verts_3d_abs,
+                  float* g_obj_verts_3d_abs, float* g_mano_pca_pose, float* g_mano_shape, void* workspace, void* stream);
+
 /* ---- Hand-mesh fitting of the submission pass (IKNet initialisation + 20 Adam steps of a MANO fit, all hands in one launch) -----
  * anakin/postprocess/iknet/fittingunit.py:112-225 (FittingUnit.__call__: residuals :63-80, geo :43-60, mano_de :83-97) and
  * utils.py:13-41 (quaternion -> axis-angle).  quat [B,64]: the raw IKNet output (16 quaternions, normalised here); pred_joints
@@ -716,6 +750,8 @@ int ab_draw_meshes(const float* hand_verts, const int32_t* hand_faces, int nhf, 
  * @check ab_mano_pca_bwd: pose_coeffs g_pose_coeffs >= B*(3+ncomps); betas g_betas >= B*10; comps >= ncomps*45; hands_mean >= 45; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; g_verts >= B*778*3; g_joints >= B*21*3; g_full_pose >= B*48
  * @check ab_honet_recover_fwd: strided: hand_st obj_st; cam_intr rotmat >= B*9; joints_3d joints_3d_abs >= B*63; hand_verts_3d hand_verts_3d_abs >= B*778*3; obj_verts_can obj_verts_3d_abs obj_verts_3d >= B*N*3; corners_can corners_3d_abs corners_3d >= B*24; root_joint obj_center >= B*3; joints_2d >= B*42; hand_verts_2d >= B*778*2; obj_verts_2d >= B*N*2; corners_2d >= B*16
  * @check ab_honet_recover_bwd: strided: hand_st obj_st g_hand_st g_obj_st; cam_intr g_rotmat >= B*9; joints_3d g_joints_3d_abs g_joints_3d >= B*63; hand_verts_3d g_hand_verts_3d_abs g_hand_verts_3d >= B*778*3; obj_verts_can g_obj_verts_3d_abs g_obj_verts_3d >= B*N*3; corners_can g_corners_3d_abs g_corners_3d >= B*24; g_root_joint g_obj_center >= B*3; g_joints_2d >= B*42; g_hand_verts_2d >= B*778*2; g_obj_verts_2d >= B*N*2; g_corners_2d >= B*16; bytes workspace >= ab_honet_recover_workspace(B,N)
+ * @check ab_mesh_queries: table >= n_obj*n*3; obj_id >= B; obj_transf >= B*16; root_joint >= B*3; hand_verts hand_verts_3d >= B*778*3; bytes samples >= (B-1)*sample_pitch+pose_offset+64; obj_verts_can obj_verts_3d >= B*n*3
+ * @check ab_honet_loss: joints_3d_abs joints_3d g_joints_3d_abs >= B*63; hand_verts_3d_abs hand_verts_3d g_hand_verts_3d_abs >= B*778*3; obj_verts_3d_abs obj_verts_3d g_obj_verts_3d_abs >= B*N*3; corners_3d_abs corners_3d >= B*24; mano_pca_pose g_mano_pca_pose >= B*(3+ncomps); mano_shape g_mano_shape >= B*10; root_joint >= B*3; weights7_host >= 7; sample_part >= B*8; losses >= 8; bytes workspace >= ab_honet_loss_workspace(B,N)
  * @check ab_mano_fit: quat >= B*64; pred_joints >= B*63; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; J_template >= 48; J_shapedirs >= 480; params adam_m adam_v grad >= B*59; verts >= B*778*3; joints >= B*63; loss >= B*n_iter
  * @check ab_draw_meshes: hand_verts >= B*778*3; hand_faces >= nhf*3; adj_off >= 779; adj_face >= nadj; obj_verts obj_normals >= nov*3; obj_faces >= nof*3; obj_vert_off obj_face_off >= n_obj+1; obj_id >= B; obj_rot >= B*9; obj_tsl >= B*3; corners >= B*24; cam_intr >= B*9; image >= B*3*H*W; out >= B*H*4*W*3; bytes workspace >= ab_draw_workspace_bytes(B,W,H,max_obj_verts)
  */

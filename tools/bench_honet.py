@@ -10,7 +10,14 @@
   step_ms       the whole eager train step (TrainStep: HoNetHIP forward, ManoLoss + ObjLoss, backward, fused clip + Adam) at B = 64,
                 128 x 128, ResNet-18, bf16x3, for both N: median and range over `--steps` steps after `--warmup`
 
-Usage: python tools/bench_honet.py [--pairs 15] [--inner 20] [--steps 30] [--warmup 5]"""
+  --fused       instead of the above: the eager train step against the graph-replayed fused one (ARCH.FUSED_MESH_STEP: FusedMeshCriterion,
+                two hipGraphs) at B = 64, 128 x 128, ResNet-18, bf16x3, N = 300 and 4000.  Two models and optimizers in one process,
+                measured as alternating pairs (eager, fused, eager, fused, ...), each sample the device-event time per step of `--inner`
+                back-to-back steps ending in a synchronise; medians with ranges over `--pairs` pairs, the ratio of the medians, and the
+                number of kernel launches one replayed step holds (counted by the profiler in a window of its own, after the timing).
+                The eager route is the one `step_ms` measures, untouched by the fused one.
+
+Usage: python tools/bench_honet.py [--pairs 15] [--inner 20] [--steps 30] [--warmup 5] [--fused]"""
 import argparse
 import json
 import os
@@ -87,7 +94,7 @@ def bench_recover(B, N, pairs, inner):
     return {"torch": _stats(t), "hip": _stats(h), "ratio_of_medians": round(statistics.median(t) / statistics.median(h), 2)}
 
 
-def bench_step(B, N, steps, warmup):
+def _train_step(B, N, fused=False):
     import artiboost_amd.honet  # noqa: F401
     from artiboost_amd import registry as R
     from artiboost_amd.criterions import Criterion
@@ -97,6 +104,8 @@ def bench_step(B, N, steps, warmup):
     arch = {"TYPE": "HoNet", "PRETRAINED": "", "PREVIOUS": [], "OBJ_TRANS_FACTOR": 100, "OBJ_SCALE_FACTOR": 0.0001, "DEVICE": "cuda",
             "BACKBONE": {"TYPE": "ResNet18", "PRETRAINED": False, "FREEZE_BATCHNORM": False},
             "HEAD": {"TYPE": "ManoBranch", "MANO_ASSETS_ROOT": "assets/mano_v1_2", "INPUT_DIM": 512, "NCOMPS": 15, "USE_PCA": True, "USE_SHAPE": True}}
+    if fused:
+        arch["FUSED_MESH_STEP"] = True
     preset = {"IMAGE_SIZE": list(SIZE), "HEATMAP_SIZE": [16, 16], "CENTER_IDX": 0}
     crit_cfg = [{"TYPE": "ManoLoss", "LAMBDA_JOINTS_3D": 1.0, "LAMBDA_HAND_VERTS_3D": 1.0, "LAMBDA_SHAPE_REG": 5.0e-7, "LAMBDA_POSE_REG": 5.0e-6},
                 {"TYPE": "ObjLoss", "LAMBDA_OBJ_VERTS_3D": 1.0}]
@@ -109,12 +118,45 @@ def bench_step(B, N, steps, warmup):
     batch = {"image": (torch.rand(B, 3, SIZE[1], SIZE[0], generator=g) - 0.5).cuda(), "cam_intr": K, "corners_can": ccan, "obj_verts_can": can,
              "root_joint": torch.tensor([0.0, 0.0, 0.5]).repeat(B, 1).cuda(), "joints_3d": joints, "hand_verts_3d": verts,
              "obj_verts_3d": can + 0.05, "corners_3d": ccan + 0.05}
-    ts = TrainStep(model, crit, opt, batch, use_graph=True)
+    return TrainStep(model, crit, opt, batch, use_graph=True)
+
+
+def bench_step(B, N, steps, warmup):
+    ts = _train_step(B, N)
     for _ in range(warmup):
         ts()
     torch.cuda.synchronize()
     v = [_event_ms(ts, 1) for _ in range(steps)]
     return _stats(v)
+
+
+def _launches_per_step(ts, steps=3):
+    """Kernel launches of one step, counted by the profiler over `steps` steps (None when the profiler reports no device activity)."""
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        for _ in range(steps):
+            ts()
+        torch.cuda.synchronize()
+    n = sum(1 for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA") and "memcpy" not in e.name.lower()
+            and "memset" not in e.name.lower())
+    return round(n / steps, 1) if n else None
+
+
+def bench_fused(B, N, pairs, inner, warmup):
+    eager, fused = _train_step(B, N), _train_step(B, N, fused=True)
+    assert eager.fused is None and not eager.use_graph and fused.fused is not None and fused.use_graph
+    for ts in (eager, fused):
+        for _ in range(warmup):
+            ts()
+    torch.cuda.synchronize()
+    e, f = [], []
+    for _ in range(pairs):
+        e.append(_event_ms(eager, inner))
+        f.append(_event_ms(fused, inner))
+    out = {"eager": _stats(e), "fused": _stats(f), "ratio_of_medians": round(statistics.median(e) / statistics.median(f), 3)}
+    out["kernel_launches_per_step"] = {"eager": _launches_per_step(eager), "fused": _launches_per_step(fused)}
+    return out
 
 
 def main():
@@ -124,9 +166,16 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--fused", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_honet needs a HIP device")
+    if a.fused:
+        out = {"B": 64, "size": list(SIZE), "dtype": "bf16x3", "pairs": a.pairs, "inner": a.inner, "fused_step_ms": {}}
+        for N in (300, 4000):
+            out["fused_step_ms"][str(N)] = bench_fused(64, N, a.pairs, a.inner, a.warmup)
+        print(json.dumps(out))
+        return
     out = {"B": 64, "recover_ms": {}, "step_ms": {}}
     for N in (1000, 4000):
         out["recover_ms"][str(N)] = bench_recover(64, N, a.pairs, a.inner)

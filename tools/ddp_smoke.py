@@ -20,7 +20,10 @@ from artiboost_amd.train import TrainStep
 
 rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
 # --model regbased: HOPRegNet with ARCH.FUSED_STEP -- two linear graphs, the whole-gradient all-reduce between them (no staged backward)
-regbased = "--model" in sys.argv and sys.argv[sys.argv.index("--model") + 1] == "regbased"
+# --model honet:    HoNet with ARCH.FUSED_MESH_STEP -- the same schedule, the mesh queries made inside the first graph
+which = sys.argv[sys.argv.index("--model") + 1] if "--model" in sys.argv else ""
+honet = which == "honet"
+regbased = which == "regbased" or honet          # (the linear two-graph schedule)
 import random
 import numpy as np
 random.seed(100 + rank); np.random.seed(100 + rank); torch.manual_seed(100 + rank)      # the ordinal losses draw their pairs from these
@@ -33,8 +36,12 @@ if backend == "nccl":
     rccl_env_defaults()
 dist.init_process_group(backend)
 root = os.path.join(os.path.dirname(__file__), "..")
-cfg = yaml.safe_load(open(os.path.join(root, "config", "ho3dv2_regbased_artiboost_mi355x_fused.yaml" if regbased else "ho3dv2_clasbased_artiboost_mi355x.yaml")))
-if regbased:
+cfg = yaml.safe_load(open(os.path.join(root, "config", "ho3dv2_honet_mi355x_fused.yaml" if honet else "ho3dv2_regbased_artiboost_mi355x_fused.yaml"
+                                       if regbased else "ho3dv2_clasbased_artiboost_mi355x.yaml")))
+if honet:
+    import artiboost_amd.honet  # noqa: F401  (registers HoNet)
+    cfg["DATA_PRESET"] = dict(cfg["DATA_PRESET"], IMAGE_SIZE=[128, 128], HEATMAP_SIZE=[16, 16])
+elif regbased:
     import artiboost_amd.hpregnet  # noqa: F401  (registers HOPRegNet)
 dtype = os.environ.get("AB_DDP_DTYPE", "bf16x3")
 overlap = os.environ.get("AB_DDP_OVERLAP", "1") != "0" and not regbased
@@ -66,7 +73,7 @@ ws = [torch.empty_like(w) for _ in range(world)]
 dist.all_gather(ws, w)
 same = all(torch.equal(ws[0], x) for x in ws)
 if rank == 0:
-    print(f"{'model=regbased ' if regbased else ''}backend={backend} world={world} dtype={dtype} render_overlap={overlap} comm={ts.comm} final_loss={float(losses[5]):.9f} "
+    print(f"{f'model={which} ' if regbased else ''}backend={backend} world={world} dtype={dtype} render_overlap={overlap} comm={ts.comm} final_loss={float(losses[5]):.9f} "
           f"weight_sum={float(w.double().sum()):.12f} weights_identical_across_ranks={same}")
 assert same
 dist.destroy_process_group()
