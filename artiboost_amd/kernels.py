@@ -977,6 +977,32 @@ def mesh_queries(table, obj_id, obj_transf, root_joint, hand_verts, samples, pos
     return out
 
 
+def mssd(can, obj_transf, obj_idx, sym_R, sym_t, sym_count, pred_R=None, pred_t=None, pred_pts=None, center=None, out=None):
+    """ab_mssd: per-sample maximum symmetry-aware surface distance in metres, min over the object's TRUE symmetry set of the max over the
+    points.  can [B,V,3], obj_transf [B,4,4] f32; obj_idx int64 [B] (1-based, clamped into the table); sym_R [n_obj,Kmax,3,3] / sym_t
+    [n_obj,Kmax,3(,1)] f32 in metres, sym_count int32 [n_obj] (table entries past a row's count are never read).  Rigid mode: pred_R [B,3,3]
+    and pred_t [B,(1,)3]; points mode: pred_pts [B,V,3] instead.  center [B,3] or None (zero).  -> mssd [B] f32 (`out` when given)."""
+    B, V = can.shape[0], can.shape[1]
+    n_obj, Kmax = sym_R.shape[0], sym_R.shape[1]
+    if obj_idx.dtype != torch.int64 or sym_count.dtype != torch.int32:
+        raise ValueError(f"mssd: obj_idx must be int64 and sym_count int32, got {obj_idx.dtype} / {sym_count.dtype}")
+    if (pred_pts is None) == (pred_R is None) or (pred_R is None) != (pred_t is None):
+        raise ValueError("mssd: pass either pred_R and pred_t (rigid mode) or pred_pts (points mode)")
+    for t, numel, what in ((can, B * V * 3, "can"), (obj_transf, B * 16, "obj_transf"), (obj_idx, B, "obj_idx"), (sym_R, n_obj * Kmax * 9, "sym_R"),
+                           (sym_t, n_obj * Kmax * 3, "sym_t"), (sym_count, n_obj, "sym_count"), (pred_R, B * 9, "pred_R"), (pred_t, B * 3, "pred_t"),
+                           (pred_pts, B * V * 3, "pred_pts"), (center, B * 3, "center")):
+        if t is not None and (t.numel() != numel or (t.dtype != torch.float32 and what not in ("obj_idx", "sym_count"))):
+            raise ValueError(f"mssd: {what} must hold {numel} elements (fp32 but for the indices), got {t.dtype} {tuple(t.shape)}")
+    if out is None:
+        out = torch.empty((B,), dtype=torch.float32, device=can.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B,):
+        raise ValueError(f"mssd: out must be fp32 [{B}]")
+    ins = [L.ptr(t) for t in (can, obj_transf, obj_idx, sym_R, sym_t, sym_count, pred_R, pred_t, pred_pts, center)]      # device tensors, or an error
+    ws = _workspace(L.lib().ab_mssd_workspace(L.i(B), L.i(Kmax), L.i(V)), can.device)
+    L.check(L.lib().ab_mssd(*ins[:6], L.i(n_obj), L.i(Kmax), *ins[6:], L.i(B), L.i(V), L.ptr(out), L.ptr(ws), L.stream()), "ab_mssd")
+    return out
+
+
 FIT_NP = 59             # parameters per hand of ab_mano_fit: so3 48 | beta 10 | bone 1
 
 

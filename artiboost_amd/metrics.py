@@ -192,11 +192,12 @@ class Evaluator:
     The reference's `feed_all` (called after every batch, train_artiboost.py:96-98) moves tensors to the host inside every metric
     (`.item()` per loss scalar, `.cpu()` per error vector): on a GPU that runs ahead of the host each of them stalls the loop until the
     device has drained.  Here a metric with the two-phase API (Metric.feed_device / feed_host: Mean3DEPE, ValMetricMean3DEPE2,
-    LossesMetric) only ENQUEUES its arithmetic; the few hundred bytes it needs on the host are packed into one pinned buffer with one
-    asynchronous copy + an event, and applied when a later feed_all finds the event complete -- at most `max_lag` steps late (1: the
+    LossesMetric, the PCK family, ValMetricAR2) only ENQUEUES its arithmetic; the few hundred bytes it needs on the host are packed into
+    one pinned buffer with one asynchronous copy + an event, and applied when a later feed_all finds the event complete -- at most `max_lag` steps late (1: the
     progress string of train_artiboost.py:105 shows the numbers through the previous step).  Every read of the measures
     (`metrics_list`, `get_measures_all*`, `dump_images`, `reset_all`) applies what is still in flight first, so at those points the
-    state equals per-step blocking feeds exactly.  Metrics without the API (PCK, AR, Vis*) are fed at once, as before.
+    state equals per-step blocking feeds exactly.  AR has no host part (its per-object sums stay on the device until they are read);
+    the Vis* metrics draw on the host and are fed at once.
     AB_EVAL_BLOCKING=1 (or max_lag=0): every feed applied before feed_all returns."""
 
     def __init__(self, cfg, metrics_list, max_lag=None):
@@ -425,15 +426,23 @@ class PCKMetric(Metric):
         self.data = [[] for _ in range(self.num_kp)]
         self.count = 0
 
-    def feed(self, preds, targs, **kwargs):
+    def feed_device(self, preds, targs, **kwargs):
+        """[(B, N) distances (fp32 for fp32 predictions), (B, N) uint8 visibility], both on the predictions' device: nothing is read back."""
         kp, kt, kv = self.keys
         p, t = preds[kp].detach(), targs[kt].to(preds[kp].device)
-        dist = torch.sqrt(torch.sum((p - t) ** 2, dim=-1)).cpu().numpy()           # (B, N)
-        vis = np.asarray(targs[kv].detach().cpu()).astype(bool)
-        assert dist.ndim == 2 and vis.shape == dist.shape
+        dist = torch.sqrt(torch.sum((p - t) ** 2, dim=-1))                          # (B, N)
+        vis = (torch.as_tensor(targs[kv]).detach().to(dist.device) != 0).to(torch.uint8)
+        assert dist.dim() == 2 and vis.shape == dist.shape
+        return [dist, vis]
+
+    def feed_host(self, arrays, **kwargs):
+        dist, vis = arrays[0], arrays[1].astype(bool)
         for i in range(self.num_kp):
             self.data[i].extend(dist[vis[:, i], i].tolist())
         self.count += dist.shape[0]
+
+    def feed(self, preds, targs, **kwargs):
+        self.feed_host([t.cpu().numpy() for t in self.feed_device(preds, targs)])
 
     def _get_pck(self, kp_id, threshold):
         if not self.data[kp_id]:
@@ -476,8 +485,17 @@ Obj2DPCKMetric = _pck("Obj2DPCKMetric", 8, ("corners_2d", "corners_2d", "corners
 class _MSSDBase:
     """Maximum symmetry-aware surface distance (anakin/metrics/bopAR.py:74-195, val_metric.py:235-327): per sample
     min over the object's symmetry set of max over the model points of ||sym(gt) - pred||.  The reference loops over the
-    object classes with boolean masks (a device synchronisation per class); here the symmetry sets are padded to one
-    length with identities (the identity is in every set, so the minimum is unchanged) and the whole batch is one product."""
+    object classes with boolean masks (a device synchronisation per class); here the whole batch is one call.
+
+    Each object keeps its OWN set, as in the reference: BOP's get_symmetry_transformations enumerates the discretised continuous
+    rotations from i = 1, so the set of an object with a continuous symmetry does NOT contain the identity, and a perfect
+    prediction of such an object scores the distance to its nearest listed rotation, not 0.  The table [n_obj, Kmax] is padded by
+    repeating a row's FIRST transform (the minimum over the row is unchanged, exactly); `sym_count` holds the true lengths.
+    USE_HO3D_YCB: ext (S.R (ext x) + S.t) = (ext S.R ext) x + ext S.t and ext only flips signs, so it is folded into the table once.
+
+    HIP tensors: kernels.mssd (csrc/mssd.hip) -- rigid mode for vertices, points mode for corners, the centre offset when configured;
+    it reads only the first `sym_count` entries of a row and builds no [B, K, V, 3] temporary.  AB_MSSD_TORCH=1 keeps the torch
+    expression there; CPU tensors always take it."""
 
     def __init__(self, **cfg):
         import json
@@ -490,34 +508,45 @@ class _MSSDBase:
         self.center_idx = cfg["DATA_PRESET"]["CENTER_IDX"] if cfg.get("MSSD_USE_CENTER_IDX", False) else None
         syms = [get_symmetry_transformations(info[str(i)], step) for i in range(1, self.n_obj + 1)]
         kmax = max(len(x) for x in syms)
-        R = np.tile(np.eye(3), (self.n_obj, kmax, 1, 1))
+        R = np.zeros((self.n_obj, kmax, 3, 3))
         t = np.zeros((self.n_obj, kmax, 3, 1))
+        ext = np.diag([1.0, -1.0, -1.0]) if self.use_ho3d_ycb else np.eye(3)
         for i, tr in enumerate(syms):
-            for k, x in enumerate(tr):
-                R[i, k], t[i, k] = x["R"], x["t"]
+            for k in range(kmax):
+                x = tr[k] if k < len(tr) else tr[0]
+                R[i, k], t[i, k] = ext @ x["R"] @ ext, ext @ x["t"]
         self.R, self.t = torch.Tensor(R), torch.Tensor(t) / 1000.0                 # mm -> m
+        self.sym_count = torch.tensor([len(x) for x in syms], dtype=torch.int32)
         self._dev = None
 
     def values(self, preds, targs):
         """-> (obj_idx [B] int64 1-based, mssd [B] in metres), both on the predictions' device."""
+        import os
         dev = preds["box_rot_rotmat"].device
         if self._dev != dev:
-            self.R, self.t, self._dev = self.R.to(dev), self.t.to(dev), dev
+            self.R, self.t, self.sym_count, self._dev = self.R.to(dev), self.t.to(dev), self.sym_count.to(dev), dev
         can = targs[Queries.CORNERS_CAN if self.mssd_use_corners else "obj_verts_can"].to(dev)
         transf = targs[Queries.OBJ_TRANSF].to(dev)
         obj_idx = targs[Queries.OBJ_IDX].to(dev).long()
+        center = None
+        if self.center_idx is not None:
+            center = targs[Queries.ROOT_JOINT].to(dev) - preds["joints_3d_abs"][:, self.center_idx].detach()
+        if dev.type == "cuda" and os.environ.get("AB_MSSD_TORCH") != "1":
+            from . import kernels as K
+            f = lambda x: None if x is None else x.detach().to(torch.float32).contiguous()      # noqa: E731
+            if self.mssd_use_corners:
+                mode = dict(pred_pts=f(preds["corners_3d_abs"]))
+            else:
+                mode = dict(pred_R=f(preds["box_rot_rotmat"]), pred_t=f(preds["boxroot_3d_abs"]))
+            return obj_idx, K.mssd(f(can), f(transf), obj_idx.contiguous(), self.R, self.t, self.sym_count, center=f(center), **mode)
         sym_R, sym_t = self.R[obj_idx - 1], self.t[obj_idx - 1]                      # [B,K,3,3], [B,K,3,1]
-        if not self.use_ho3d_ycb:
-            sym_can = (torch.einsum("bkmn,bvn->bkmv", sym_R, can) + sym_t).transpose(-2, -1)
-        else:
-            ext = torch.tensor([[1.0, 0.0, 0.0], [0.0, -1.0, 0.0], [0.0, 0.0, -1.0]], dtype=torch.float32, device=dev)
-            sym_can = (ext @ (torch.einsum("bkmn,bnv->bkmv", sym_R, ext @ can.transpose(-2, -1)) + sym_t)).transpose(-2, -1)
+        sym_can = (torch.einsum("bkmn,bvn->bkmv", sym_R, can) + sym_t).transpose(-2, -1)
         sym_abs = (torch.einsum("bij,bklj->bkil", transf[:, :3, :3], sym_can) + transf[:, None, :3, 3:]).transpose(-2, -1)
         if self.mssd_use_corners:
             pred_abs = preds["corners_3d_abs"]
         else:
             pred_abs = (preds["box_rot_rotmat"] @ can.transpose(-2, -1)).transpose(-2, -1) + preds["boxroot_3d_abs"]
-        if self.center_idx is None:
+        if center is None:
             d = sym_abs - pred_abs.unsqueeze(1)
         else:
             d = ((sym_abs - targs[Queries.ROOT_JOINT].to(dev)[:, None, None, :]) -
@@ -590,17 +619,26 @@ class ValMetricAR2(Metric):
     def reset(self):
         self.storage = {}
 
-    def feed(self, preds, targs, **kwargs):
+    def feed_device(self, preds, targs, **kwargs):
+        """[(B, 4) int64 (obj_id, persp_id, grasp_id, is_synth), (B,) int64 obj_idx, (B,) fp32 MSSD in mm] on the predictions' device."""
         if self.mssd is None:
-            return
+            return None
         obj_idx, v = self.mssd.values(preds, targs)
-        order = torch.argsort(obj_idx, stable=True).cpu().numpy()        # the reference visits the object classes in order:
-        vals = (v * 1000.0).cpu().numpy()                                # later classes overwrite earlier ones on a repeated triplet
-        flags = np.asarray(targs[SynthQueries.IS_SYNTH].cpu()).astype(bool)
-        ids = np.stack([np.asarray(targs[k].cpu()) for k in (SynthQueries.OBJ_ID, SynthQueries.PERSP_ID, SynthQueries.GRASP_ID)], 1)
-        for i in order:
-            if flags[i]:
-                self.storage[tuple(int(x) for x in ids[i])] = vals[i]
+        ids = torch.stack([torch.as_tensor(targs[k]).to(device=v.device, dtype=torch.int64) for k in
+                           (SynthQueries.OBJ_ID, SynthQueries.PERSP_ID, SynthQueries.GRASP_ID, SynthQueries.IS_SYNTH)], 1)
+        return [ids, obj_idx, (v * 1000.0).to(torch.float32)]
+
+    def feed_host(self, arrays, **kwargs):
+        ids, obj_idx, vals = arrays[0].tolist(), arrays[1], arrays[2]
+        for i in np.argsort(obj_idx, kind="stable"):                     # the reference visits the object classes in order:
+            t = ids[i]                                                   # later classes overwrite earlier ones on a repeated triplet
+            if t[3]:
+                self.storage[(t[0], t[1], t[2])] = vals[i]
+
+    def feed(self, preds, targs, **kwargs):
+        res = self.feed_device(preds, targs)
+        if res is not None:
+            self.feed_host([t.cpu().numpy() for t in res])
 
     def get_measures(self, **kwargs):
         return {"mssd": self.storage} if self.mssd is not None else {}

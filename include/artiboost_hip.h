@@ -683,6 +683,27 @@ int ab_draw_meshes(const float* hand_verts, const int32_t* hand_faces, int nhf, 
                    const float* obj_rot, const float* obj_tsl, const float* corners, const float* cam_intr, const float* image, int B, int W,
                    int H, uint8_t* out, void* workspace, void* stream);
 
+/* ---- Maximum symmetry-aware surface distance of the evaluator (csrc/mssd.hip) -----------------------------------
+ * anakin/metrics/bopAR.py:131-175 (MSSD.feed) and val_metric.py:272-320: what AR and ValMetricAR2 accumulate.  Per sample b, with the
+ * symmetry set S = sym[clamp(obj_idx[b] - 1, 0, n_obj - 1)] at its TRUE length sym_count[obj] (clamped to 0 .. Kmax),
+ *   mssd[b] = min over k < sym_count of max over v < V of || R_gt (S_k.R can_v + S_k.t) + t_gt - pred_v - c_b ||      (metres)
+ * can [B,V,3]; obj_transf [B,4,4] row-major (R_gt | t_gt in its first three rows; the fourth is not read); obj_idx int64 [B], 1-based, an
+ * id outside the table is clamped into it (as ab_mesh_queries does); sym_R [n_obj,Kmax,9] row-major, sym_t [n_obj,Kmax,3] in metres,
+ * sym_count int32 [n_obj]: entries of a table row at or past its count are never read.  An empty set (count < 1) gives +inf.
+ *   rigid mode  (pred_pts NULL): pred_v = pred_R[b] can_v + pred_t[b] with pred_R [B,9] (box_rot_rotmat), pred_t [B,3] (boxroot_3d_abs);
+ *                                the residual is one 3x4 affine map per (b, k) applied to can_v.
+ *   points mode (pred_pts [B,V,3], pred_R and pred_t NULL): pred_v read from memory (MSSD_USE_CORNERS: corners_3d_abs).
+ * center [B,3] or NULL (zero): c_b = root_joint - joints_3d_abs[:, center_idx] of MSSD_USE_CENTER_IDX.  USE_HO3D_YCB needs no mode: the
+ * sign flips fold into the table (ext S.R ext, ext S.t), exactly.
+ * mssd [B] is written in full.  workspace: ab_mssd_workspace(B, Kmax, V) bytes (one partial per sample and chunk of 64 symmetries).
+ * Squared lengths are compared and ONE square root is taken at the end.  No atomics; a vertex's residual does not depend on where the
+ * vertex or the sample sits and max / min are order-independent, so the bits are the same across calls, for a sample alone or inside a
+ * batch, and under repetition padding of the vertices.  1 <= B <= 65535, V >= 1, n_obj >= 1, 1 <= Kmax <= 64 * 65535.                  */
+long ab_mssd_workspace(int B, int Kmax, int V);
+int ab_mssd(const float* can, const float* obj_transf, const int64_t* obj_idx, const float* sym_R, const float* sym_t,
+            const int32_t* sym_count, int n_obj, int Kmax, const float* pred_R, const float* pred_t, const float* pred_pts,
+            const float* center, int B, int V, float* mssd, void* workspace, void* stream);
+
 /* ---- Argument contracts of the dispatcher ops (torch.ops.artiboost_hip.*, libartiboost_torch.so) ------------------------------------------
  * The C entry points above take raw pointers and trust their caller.  Their PyTorch-dispatcher form (ops that "validate
  * with TORCH_CHECK") is generated from this header by artiboost_amd/gen_torch_ops.py and checks, before the C call, for EVERY op:
@@ -754,6 +775,7 @@ int ab_draw_meshes(const float* hand_verts, const int32_t* hand_faces, int nhf, 
  * @check ab_honet_loss: joints_3d_abs joints_3d g_joints_3d_abs >= B*63; hand_verts_3d_abs hand_verts_3d g_hand_verts_3d_abs >= B*778*3; obj_verts_3d_abs obj_verts_3d g_obj_verts_3d_abs >= B*N*3; corners_3d_abs corners_3d >= B*24; mano_pca_pose g_mano_pca_pose >= B*(3+ncomps); mano_shape g_mano_shape >= B*10; root_joint >= B*3; weights7_host >= 7; sample_part >= B*8; losses >= 8; bytes workspace >= ab_honet_loss_workspace(B,N)
  * @check ab_mano_fit: quat >= B*64; pred_joints >= B*63; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; J_template >= 48; J_shapedirs >= 480; params adam_m adam_v grad >= B*59; verts >= B*778*3; joints >= B*63; loss >= B*n_iter
  * @check ab_draw_meshes: hand_verts >= B*778*3; hand_faces >= nhf*3; adj_off >= 779; adj_face >= nadj; obj_verts obj_normals >= nov*3; obj_faces >= nof*3; obj_vert_off obj_face_off >= n_obj+1; obj_id >= B; obj_rot >= B*9; obj_tsl >= B*3; corners >= B*24; cam_intr >= B*9; image >= B*3*H*W; out >= B*H*4*W*3; bytes workspace >= ab_draw_workspace_bytes(B,W,H,max_obj_verts)
+ * @check ab_mssd: can pred_pts >= B*V*3; obj_transf >= B*16; obj_idx mssd >= B; sym_R >= n_obj*Kmax*9; sym_t >= n_obj*Kmax*3; sym_count >= n_obj; pred_R >= B*9; pred_t center >= B*3; bytes workspace >= ab_mssd_workspace(B,Kmax,V)
  */
 
 #ifdef __cplusplus
