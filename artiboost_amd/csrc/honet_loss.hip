@@ -230,3 +230,61 @@ extern "C" int ab_mesh_queries(const float* table, int n_obj, int n, const int64
     AB_LAUNCH_CHECK();
     return 0;
 }
+
+// ---- the mesh queries of REAL frames (realdata.RealBatcher) --------------------------------------------------------
+// Same launch shape as mesh_queries_kernel.  The host composes, per sample, two row-major 3x4 affine maps in float64 (realdata.real_mesh_maps):
+// obj_map places the canonical object vertices, hand_map the MANO vertices of ab_mano_lbs; thread 0 of a block stages both in LDS.  A point is
+// ((m0 x + m1 y) + m2 z) + m3 per row, in that order (-ffp-contract=off: no fma), so the bits do not depend on the batch or the call.
+struct rmq_place {
+    float obj[12], hand[12];
+    long row;               // the clamped table row of the sample's object
+};
+
+__device__ __forceinline__ void rmq_apply(const float* __restrict__ m, const float c[3], float* __restrict__ dst, size_t i) {
+    hl_st3(dst, i,
+           (((m[0] * c[0] + m[1] * c[1]) + m[2] * c[2]) + m[3]),
+           (((m[4] * c[0] + m[5] * c[1]) + m[6] * c[2]) + m[7]),
+           (((m[8] * c[0] + m[9] * c[1]) + m[10] * c[2]) + m[11]));
+}
+
+__global__ __launch_bounds__(256) void real_mesh_queries_kernel(
+        const float* __restrict__ table, int n_rows, int n, const int64_t* __restrict__ row, const float* __restrict__ obj_map,
+        const float* __restrict__ hand_map, const float* __restrict__ mano_verts, float* __restrict__ obj_verts_can,
+        float* __restrict__ obj_verts_3d, float* __restrict__ hand_verts_3d) {
+    __shared__ rmq_place P;
+    const int b = blockIdx.y, tid = threadIdx.x;
+    if (tid == 0) {
+        for (int k = 0; k < 12; ++k) {
+            P.obj[k] = obj_map[(size_t)b * 12 + k];
+            P.hand[k] = hand_map[(size_t)b * 12 + k];
+        }
+        const int64_t id = row[b];
+        P.row = id < 0 ? 0 : (id >= n_rows ? (long)n_rows - 1 : (long)id);      // a row outside the table is clamped into it
+    }
+    __syncthreads();
+    const int p = blockIdx.x * MQ_CHUNK + tid;
+    if (p >= n + NV) return;
+    float c[3];
+    if (p < n) {
+        const size_t i = (size_t)b * n + p;
+        hl_ld3(table, (size_t)P.row * n + p, c);
+        hl_st3(obj_verts_can, i, c[0], c[1], c[2]);
+        rmq_apply(P.obj, c, obj_verts_3d, i);
+    } else {
+        const size_t i = (size_t)b * NV + (p - n);
+        hl_ld3(mano_verts, i, c);
+        rmq_apply(P.hand, c, hand_verts_3d, i);
+    }
+}
+
+extern "C" int ab_real_mesh_queries(const float* table, int n_rows, int n, const int64_t* row, const float* obj_map, const float* hand_map,
+                                    const float* mano_verts, int B, float* obj_verts_can, float* obj_verts_3d, float* hand_verts_3d,
+                                    void* stream) {
+    if (B == 0) return 0;                                   // an empty real half: nothing to write, no launch
+    if (B < 0 || B > 65535 || n < 1 || n_rows < 1) return AB_EINVAL;
+    if (!table || !row || !obj_map || !hand_map || !mano_verts || !obj_verts_can || !obj_verts_3d || !hand_verts_3d) return AB_EINVAL;
+    real_mesh_queries_kernel<<<dim3((n + NV + MQ_CHUNK - 1) / MQ_CHUNK, B), 256, 0, as_stream(stream)>>>(
+        table, n_rows, n, row, obj_map, hand_map, mano_verts, obj_verts_can, obj_verts_3d, hand_verts_3d);
+    AB_LAUNCH_CHECK();
+    return 0;
+}

@@ -134,6 +134,8 @@ class HO3D(_DownloadedSet):
                     pickle.dump(ann, f, protocol=4)
                 os.replace(tmp, cache)
         self.ann = ann
+        self._mano_cache = cache[:-len(".ab.pkl")] + ".mano.ab.pkl" if bool(preset.get("USE_CACHE", True)) else None
+        self._hand = None                                               # get_hand_params: read (and cached) on first use only
         self.sample_idxs = list(range(len(ann["frames"])))
         if self.mini_factor != 1.0:                                     # ho3d.py:112-114
             import random
@@ -141,6 +143,7 @@ class HO3D(_DownloadedSet):
             self.sample_idxs = self.sample_idxs[:int(self.mini_factor * len(self.sample_idxs))]
         self.name2id = {v: k for k, v in CONST.YCB_IDX2CLASSES.items()}
         self._can, self._faces = {}, {}
+        self._mesh_rows = None
 
     def _read_annotations(self, seq_frames):
         n = len(seq_frames)
@@ -158,6 +161,66 @@ class HO3D(_DownloadedSet):
                 out["hand_bbox"][i] = a["handBoundingBox"]
             out["obj_name"].append(a["objName"])
         return out
+
+    def _read_hand_params(self):
+        """handPose / handBeta / handTrans of every frame (ho3d.py:238-251).  Evaluation frames carry the root joint only: the reference
+        substitutes a zero pose, a zero shape and handTrans = that root (:171-175), and so does this."""
+        frames = self.ann["frames"]
+        n = len(frames)
+        out = dict(frames=list(frames), pose=np.zeros((n, 48), np.float32), shape=np.zeros((n, 10), np.float32), tsl=np.zeros((n, 3), np.float32))
+        for i, (seq, frame) in enumerate(frames):
+            with open(os.path.join(self.root, self.subfolder, seq, "meta", f"{frame}.pkl"), "rb") as f:
+                a = pickle.load(f, encoding="latin1")
+            j = np.asarray(a["handJoints3D"], np.float32)
+            if j.size == 3:
+                out["tsl"][i] = j.reshape(3)
+            else:
+                out["pose"][i], out["shape"][i] = np.asarray(a["handPose"]).reshape(48), np.asarray(a["handBeta"]).reshape(10)
+                out["tsl"][i] = np.asarray(a["handTrans"]).reshape(3)
+        return out
+
+    def _hand_params(self):
+        """The MANO annotation table, from its own cache file next to the annotation index (<md5>.mano.ab.pkl: written on first use with
+        the same write-to-temporary-then-rename step; the .ab.pkl file is neither read again nor rewritten)."""
+        if self._hand is None:
+            path, hand = self._mano_cache, None
+            if path is not None and os.path.exists(path):
+                with open(path, "rb") as f:
+                    hand = pickle.load(f)
+                if hand.get("frames") != self.ann["frames"]:
+                    hand = None
+            if hand is None:
+                hand = self._read_hand_params()
+                if path is not None:
+                    os.makedirs(os.path.dirname(path), exist_ok=True)
+                    tmp = f"{path}.{os.getpid()}.tmp"
+                    with open(tmp, "wb") as f:
+                        pickle.dump(hand, f, protocol=4)
+                    os.replace(tmp, path)
+            self._hand = hand
+        return self._hand
+
+    def get_hand_params(self, idx):
+        """_ho3d_get_hand_info (ho3d.py:238-251) -> (pose [48], shape [10], tsl [3]) float32: MANO axis-angle pose, shape coefficients and
+        translation in the dataset's OpenGL camera frame; evaluation frames: zeros, zeros, the root joint."""
+        h, i = self._hand_params(), self.sample_idxs[idx]
+        return h["pose"][i], h["shape"][i], h["tsl"][i]
+
+    def mesh_vertex_table(self, n):
+        """-> (table [n_obj_names, n, 3] float32, {obj_name: row}): n vertices of every object's canonical mesh (get_obj_verts_can),
+        evenly spaced over its vertex list by the index rule of synth.mesh_vertex_table (an object with fewer than n vertices repeats them)."""
+        names = sorted(self.obj_verts)
+        table = np.zeros((len(names), n, 3), np.float32)
+        for r, obj in enumerate(names):
+            v = self._verts_can(obj)
+            table[r] = v[(np.arange(n) * len(v)) // n if len(v) >= n else np.arange(n) % len(v)]
+        return table, {obj: r for r, obj in enumerate(names)}
+
+    def get_mesh_annots(self, idx):
+        pose, shape, tsl = self.get_hand_params(idx)
+        if self._mesh_rows is None:
+            self._mesh_rows = {obj: r for r, obj in enumerate(sorted(self.obj_verts))}
+        return dict(hand_pose=pose, hand_shape=shape, hand_tsl=tsl, table_row=self._mesh_rows[self.ann["obj_name"][self.sample_idxs[idx]]])
 
     # ---- HOdataSource
     def __len__(self):
@@ -194,8 +257,11 @@ class HO3D(_DownloadedSet):
     def get_obj_verts_can(self, idx):
         """ho3d.py:376-385: the object's mesh in the OpenCV frame minus its bounding-box centre -> (verts_can float32, centre, None)."""
         obj = self.ann["obj_name"][self.sample_idxs[idx]]
+        return self._verts_can(obj), self._canonical(obj), None
+
+    def _verts_can(self, obj):
         v = self.CAM_EXTR.dot(self.obj_verts[obj].transpose()).transpose()
-        return np.asarray(v - self._canonical(obj), np.float32), self._canonical(obj), None
+        return np.asarray(v - self._canonical(obj), np.float32)
 
     def get_obj_faces(self, idx):
         """ho3d.py:356-362: int32 faces of the object's mesh (YCB_models_supp/<obj>/textured_simple_ds.obj), read once per object."""

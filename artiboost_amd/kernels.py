@@ -977,6 +977,29 @@ def mesh_queries(table, obj_id, obj_transf, root_joint, hand_verts, samples, pos
     return out
 
 
+def real_mesh_queries(table, row, obj_map, hand_map, mano_verts, out=None):
+    """ab_real_mesh_queries: the mesh queries of REAL frames in one launch (realdata.RealBatcher).  table [n_rows,n,3]
+    f32 (datasets.HO3D.mesh_vertex_table), row int64 [B] (clamped into the table), obj_map / hand_map [B,3,4] f32 (realdata.real_mesh_maps),
+    mano_verts [B,778,3] f32 (ab_mano_lbs).  out: (obj_verts_can [B,n,3], obj_verts_3d [B,n,3], hand_verts_3d [B,778,3]) to write into
+    (allocated when None).  B == 0: nothing is launched."""
+    B, n = row.shape[0], table.shape[1]
+    if row.dtype != torch.int64 or row.dim() != 1:
+        raise ValueError(f"real_mesh_queries: row must be int64 [B], got {row.dtype} {tuple(row.shape)}")
+    for t, numel, what in ((table, table.shape[0] * n * 3, "table"), (obj_map, B * 12, "obj_map"), (hand_map, B * 12, "hand_map"),
+                           (mano_verts, B * 778 * 3, "mano_verts")):
+        if t.dtype != torch.float32 or t.numel() != numel:
+            raise ValueError(f"real_mesh_queries: {what} must be fp32 with {numel} elements, got {t.dtype} {tuple(t.shape)}")
+    if out is None:
+        z = lambda *s: torch.empty(s, dtype=torch.float32, device=table.device)      # noqa: E731
+        out = (z(B, n, 3), z(B, n, 3), z(B, 778, 3))
+    can, v3d, hv = out
+    if tuple(can.shape) != (B, n, 3) or tuple(v3d.shape) != (B, n, 3) or tuple(hv.shape) != (B, 778, 3) or any(t.dtype != torch.float32 for t in out):
+        raise ValueError(f"real_mesh_queries: outputs must be fp32 [{B},{n},3], [{B},{n},3], [{B},778,3]")
+    L.check(L.lib().ab_real_mesh_queries(L.ptr(table), L.i(table.shape[0]), L.i(n), L.ptr(row), L.ptr(obj_map), L.ptr(hand_map),
+                                         L.ptr(mano_verts), L.i(B), L.ptr(can), L.ptr(v3d), L.ptr(hv), L.stream()), "ab_real_mesh_queries")
+    return out
+
+
 def mssd(can, obj_transf, obj_idx, sym_R, sym_t, sym_count, pred_R=None, pred_t=None, pred_pts=None, center=None, out=None):
     """ab_mssd: per-sample maximum symmetry-aware surface distance in metres, min over the object's TRUE symmetry set of the max over the
     points.  can [B,V,3], obj_transf [B,4,4] f32; obj_idx int64 [B] (1-based, clamped into the table); sym_R [n_obj,Kmax,3,3] / sym_t

@@ -39,6 +39,16 @@ class HOdataSource:
         obj_transf (4,4), obj_idx int, side str, bbox_center (2,), bbox_scale float (get_center_scale_wrt_bbox)."""
         raise NotImplementedError
 
+    def get_mesh_annots(self, idx):
+        """What a frame's mesh queries need beyond get_annots (RealBatcher(mesh_queries=n)):
+        dict: hand_pose (48,) axis-angle MANO pose, hand_shape (10,), hand_tsl (3,) -- the dataset's own MANO annotation, in ITS camera frame
+        (real_mesh_maps applies the extrinsic) -- and table_row int, the frame's object as a row of mesh_vertex_table(n)."""
+        raise NotImplementedError(f"{type(self).__name__} provides no mesh annotations (get_mesh_annots / mesh_vertex_table)")
+
+    def mesh_vertex_table(self, n):
+        """-> (table [n_rows, n, 3] float32 of canonical object vertices, {object name: row}); see get_mesh_annots."""
+        raise NotImplementedError(f"{type(self).__name__} provides no mesh annotations (get_mesh_annots / mesh_vertex_table)")
+
 
 def annot_center_scale(pts2d):
     """HOdata.get_annot_center / get_annot_scale (hodata.py:162-186): int-truncated centre, max span."""
@@ -119,7 +129,39 @@ def assemble_real_gt_batch(anns, image_size, raw_size, draws, center_idx=0, bbox
                         center_idx, raw_j2d=raw_j2, raw_c2d=raw_c2, train_split=train_split)
     out["flip"] = flip
     out[Queries.OBJ_IDX] = np.array([int(a["obj_idx"]) for a in anns], np.int64)
+    # the in-plane rotation as the chain above applied it (float32 entries, hodata.py:364-368): what real_mesh_maps composes with
+    rm = np.zeros((S, 3, 3), np.float32)
+    rm[:, 0, 0], rm[:, 0, 1], rm[:, 1, 0], rm[:, 1, 1], rm[:, 2, 2] = np.cos(rot), -np.sin(rot), np.sin(rot), np.cos(rot), 1.0
+    out["rot_mat"] = rm
     return out
+
+
+CAM_EXTR = np.diag([1.0, -1.0, -1.0])       # ho3d.py:44-49: the datasets' OpenGL -> OpenCV camera flip (rotation part; it has no translation)
+
+
+def real_mesh_maps(anns, mesh_anns, r, center_idx=None):
+    """The two affine maps per sample that place a real frame's meshes where HOdata.__getitem__ places its joints and corners (DESIGN.md
+    section 22).  anns: the get_annots dicts, mesh_anns: the get_mesh_annots dicts, r: assemble_real_gt_batch's result for the same samples
+    (its "rot_mat" rm, "flip" and ROOT_JOINT -- the root of joint `center_idx`, which is therefore not read again here).  With
+    E = diag(1,-1,-1) (cam_extr), F = diag(-1,1,1) for a flipped sample else the identity, R_base | t_base the annotation's obj_transf:
+      obj_map  = [rm F R_base | rm F t_base - root]        OBJ_VERTS_3D  = obj_map . [can; 1]
+      hand_map = [rm F E      | rm F E handTrans - root]   hand_verts_3d = hand_map . [mano(handPose, handBeta).verts; 1]
+    -> (obj_map, hand_map), [S,3,4] float32 each: composed in float64, cast once."""
+    S = len(anns)
+    rm = np.asarray(r["rot_mat"], np.float64)
+    root = np.asarray(r[Queries.ROOT_JOINT], np.float64)
+    F = np.tile(np.eye(3), (S, 1, 1))
+    F[np.asarray(r["flip"], bool), 0, 0] = -1.0
+    A = rm @ F
+    T = np.stack([np.asarray(a["obj_transf"], np.float64) for a in anns]).reshape(S, 4, 4)
+    tsl = np.stack([np.asarray(m["hand_tsl"], np.float64).reshape(3) for m in mesh_anns]).reshape(S, 3)
+    obj_map, hand_map = np.zeros((S, 3, 4)), np.zeros((S, 3, 4))
+    obj_map[:, :, :3] = A @ T[:, :3, :3]
+    obj_map[:, :, 3] = np.einsum("sij,sj->si", A, T[:, :3, 3]) - root
+    AE = A @ CAM_EXTR
+    hand_map[:, :, :3] = AE
+    hand_map[:, :, 3] = np.einsum("sij,sj->si", AE, tsl) - root
+    return obj_map.astype(np.float32), hand_map.astype(np.float32)
 
 
 class RealBatcher:
@@ -128,7 +170,20 @@ class RealBatcher:
                Queries.CORNERS_2D, Queries.CORNERS_VIS, Queries.CORNERS_CAN, Queries.OBJ_TRANSF)
 
     def __init__(self, source: HOdataSource, cfg_preset, aug=True, aug_param=None, device="cuda", compute_dtype=torch.bfloat16, seed=1,
-                 num_workers=None):
+                 num_workers=None, mesh_queries: int = 0, mano=None):
+        # mesh_queries = n > 0: every batch also carries OBJ_VERTS_CAN [B,n,3], OBJ_VERTS_3D [B,n,3] and hand_verts_3d [B,778,3] (what HoNet,
+        # ObjLoss and ManoLoss's vertex term read; the definition: DESIGN.md section 22), made on the device by ab_mano_lbs (`mano`: a
+        # synth.ManoLayerHIP) + ab_real_mesh_queries.  0: batches exactly as before.
+        self.mesh_queries = int(mesh_queries or 0)
+        self.mano = mano
+        self._mesh_table = None         # the source's vertex table on the device, uploaded with the first batch
+        if self.mesh_queries:
+            if mano is None:
+                raise ValueError(f"RealBatcher(mesh_queries={self.mesh_queries}) needs mano=synth.ManoLayerHIP(...): hand_verts_3d is the MANO "
+                                 "mesh of the frame's annotated pose")
+            for name in ("get_mesh_annots", "mesh_vertex_table"):
+                if getattr(type(source), name, None) in (None, getattr(HOdataSource, name)):
+                    raise ValueError(f"RealBatcher(mesh_queries={self.mesh_queries}): the source {type(source).__name__} does not implement {name}")
         # compute_dtype "u8n": the padded frames as ONE bf16 plane of the odd integers 2 v - 255 (AB_DT_U8N; see synth.ArtiBoostLoader)
         self.image_plane = "u8n" if (isinstance(compute_dtype, str) and compute_dtype == "u8n") else "f32"
         if self.image_plane == "u8n":
@@ -296,7 +351,8 @@ class RealBatcher:
             from .png import pool
             list(pool(self.num_workers).map(one, enumerate(idxs)))
         # splits other than train / trainval: JOINTS_VIS / CORNERS_VIS are forced to ones (hodata.py:296-313, 389-391)
-        r = assemble_real_gt_batch([self.src.get_annots(idx) for idx in idxs], self.image_size, self.src.raw_size, draws, self.center_idx,
+        anns = [self.src.get_annots(idx) for idx in idxs]
+        r = assemble_real_gt_batch(anns, self.image_size, self.src.raw_size, draws, self.center_idx,
                                    self.bbox_expand, self.center_jit, self.scale_jit, self.src.sides,
                                    train_split=getattr(self.src, "data_split", "train") in ("train", "trainval"))
         gt = {k: r[k] for k in self.GT_KEYS}
@@ -310,8 +366,25 @@ class RealBatcher:
             blur = None
         else:
             order, factor, blur = draws["order"], draws["factor"], draws["blur"]
-        return dict(frames=stage, files=files, file_kind=kind, file_infos=infos, gt={k: np.asarray(v, np.float32) for k, v in gt.items()}, inv=inv, flip=flip, obj_idx=obj_idx,
+        host = dict(frames=stage, files=files, file_kind=kind, file_infos=infos, gt={k: np.asarray(v, np.float32) for k, v in gt.items()}, inv=inv, flip=flip, obj_idx=obj_idx,
                     order=order, factor=factor, blur=blur, idxs=np.asarray(idxs, np.int64))
+        if self.mesh_queries:
+            ma = [self.src.get_mesh_annots(idx) for idx in idxs]
+            obj_map, hand_map = real_mesh_maps(anns, ma, r, self.center_idx)
+            host["mesh"] = dict(pose=np.stack([np.asarray(m["hand_pose"], np.float32).reshape(48) for m in ma]).reshape(n, 48),
+                                shape=np.stack([np.asarray(m["hand_shape"], np.float32).reshape(10) for m in ma]).reshape(n, 10),
+                                obj_map=obj_map, hand_map=hand_map, row=np.array([int(m["table_row"]) for m in ma], np.int64))
+        return host
+
+    def _mesh_queries_into(self, b, up):
+        """The three mesh queries of the batch whose small arrays `up` holds: ab_mano_lbs on the annotated pose / shape, then ONE
+        ab_real_mesh_queries launch, both on the current stream."""
+        from . import kernels as K
+        if self._mesh_table is None:
+            self._mesh_table = torch.from_numpy(np.ascontiguousarray(self.src.mesh_vertex_table(self.mesh_queries)[0], np.float32)).to(self.dev)
+        verts = self.mano(up["__mq_pose"], up["__mq_shape"])[0]
+        can, v3d, hv = K.real_mesh_queries(self._mesh_table, up["__mq_row"], up["__mq_obj_map"], up["__mq_hand_map"], verts)
+        b[Queries.OBJ_VERTS_CAN], b[Queries.OBJ_VERTS_3D], b["hand_verts_3d"] = can, v3d, hv
 
     def _upload(self, arrays):
         """{name: host array} -> {name: device tensor} through ONE pinned blob and ONE asynchronous copy.  The small per-batch arrays
@@ -407,6 +480,8 @@ class RealBatcher:
         small = dict(host["gt"], __order=host["order"], __factor=host["factor"], __inv=host["inv"], __flip=host["flip"], __blur=host["blur"],
                      __obj_idx=np.asarray(host["obj_idx"], np.int64), __idxs=self._sample_idx_of(host["idxs"]),
                      __is_synth=np.zeros(n, np.bool_), __minus1=np.full(n, -1, np.int64))
+        if self.mesh_queries:
+            small.update({"__mq_" + k: v for k, v in host["mesh"].items()})
         up = self._upload(small)                   # every small array of the batch: one pinned blob, one asynchronous copy
         self.augment(host, out_pad=out_pad, out_chw=chw,
                      dev=dict(order=up["__order"], factor=up["__factor"], inv=up["__inv"], flip=up["__flip"], blur=up.get("__blur")))
@@ -418,6 +493,8 @@ class RealBatcher:
             b[k] = up["__minus1"]                  # one read-only tensor for the three CCV ids of a real sample
         if chw is not None:
             b[Queries.IMAGE] = chw
+        if self.mesh_queries and n:
+            self._mesh_queries_into(b, up)
         return b
 
 
@@ -466,6 +543,10 @@ class MixedLoader:
         if self.synth is not None and self.n_synth and getattr(self.real, "image_plane", "f32") != getattr(self.synth, "image_plane", "f32"):
             raise ValueError("both halves of a mixed batch write ONE image tensor: build RealBatcher and ArtiBoostLoader with the same compute_dtype "
                              f"(real: {getattr(self.real, 'image_plane', 'f32')}, synthetic: {getattr(self.synth, 'image_plane', 'f32')})")
+        real_mq = int(getattr(self.real, "mesh_queries", 0) or 0)
+        if real_mq and self.n_synth and int(getattr(self.synth, "mesh_queries", 0) or 0) != real_mq:
+            raise ValueError("both halves of a mixed batch must carry the same mesh queries: RealBatcher(mesh_queries="
+                             f"{real_mq}) next to an ArtiBoostLoader with MANAGER.MESH_QUERIES = {int(getattr(self.synth, 'mesh_queries', 0) or 0)}")
 
     @staticmethod
     def n_synth_for(batch_size, real_len, synth_len):
@@ -526,6 +607,8 @@ class MixedLoader:
             # both halves write their frames straight into the batch's tensors: the renderer into rows n_real.. (no copy, no concatenation)
             self.synth.load_batch(static, bi)
             self.synth.render_into(static, want_chw=self.want_chw, out_pad=pad[self.n_real:], out_chw=None if chw is None else chw[self.n_real:])
+            if getattr(self.real, "mesh_queries", 0):      # the synthetic rows of the three mesh queries (ab_mesh_queries), into `static`
+                self.synth.mesh_queries_into(static)
             out = {"image_nhwc4_padded": pad, IMAGE_PLANE_KEY: PlaneTag(self.real.image_plane)}
             if chw is not None:
                 out[Queries.IMAGE] = chw

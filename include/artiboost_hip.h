@@ -626,10 +626,22 @@ int ab_honet_recover_bwd(const float* hand_st, int hand_pitch, const float* obj_
  * g_hand_verts_3d_abs, g_obj_verts_3d_abs, g_mano_pca_pose (root-rotation columns zero), g_mano_shape.  workspace:
  * ab_honet_loss_workspace(B, N) bytes.  A sample's object vertices are split over ab_honet_loss_chunks(N) workgroups (+ one for the hand);
  * each reduces in a fixed order into its own row, a finalize launch adds the rows in chunk order and the samples in double.  No float
- * atomics: two calls give the same bits, and the loss bits do not depend on which gradients are asked for.                              */
+ * atomics: two calls give the same bits, and the loss bits do not depend on which gradients are asked for.
+ * ab_real_mesh_queries: the same three queries for REAL frames (artiboost_amd/realdata.py RealBatcher).  The reference
+ * has the getters (anakin/datasets/ho3d.py:253-262 get_hand_verts_3d, :376-385 get_obj_verts_can, :401-413 get_obj_verts_transf) but
+ * HOdata.__getitem__ (hodata.py:315-450) never samples them; the definition is the per-point chain it applies to JOINTS_3D / CORNERS_3D
+ * (flip :336-343, in-plane rotation :364-368, root subtraction :371-381).  table [n_rows,n,3] (datasets.HO3D.mesh_vertex_table), row int64
+ * [B] (clamped into the table), obj_map / hand_map [B,3,4] row-major affine maps composed on the host in float64
+ * (realdata.real_mesh_maps), mano_verts [B,778,3] (ab_mano_lbs on the frame's handPose / handBeta).  Writes, in full,
+ *   obj_verts_can [B,n,3] = table[clamp(row, 0, n_rows - 1)]   (bit copies)
+ *   obj_verts_3d  [B,n,3] = obj_map . [can; 1]         hand_verts_3d [B,778,3] = hand_map . [mano_verts; 1]
+ * each coordinate ((m0 x + m1 y) + m2 z) + m3, unfused.  Grid and block of ab_mesh_queries.  B == 0 returns 0 without a launch; no
+ * allocation, no host read, no atomics: two calls give the same bits.                                                                  */
 int ab_mesh_queries(const float* table, int n_obj, int n, const int64_t* obj_id, const float* obj_transf, const float* root_joint,
                     const float* hand_verts, const uint8_t* samples, long sample_pitch, long pose_offset, int B, float* obj_verts_can,
                     float* obj_verts_3d, float* hand_verts_3d, void* stream);
+int ab_real_mesh_queries(const float* table, int n_rows, int n, const int64_t* row, const float* obj_map, const float* hand_map,
+                         const float* mano_verts, int B, float* obj_verts_can, float* obj_verts_3d, float* hand_verts_3d, void* stream);
 int ab_honet_loss_chunks(int N);
 long ab_honet_loss_workspace(int B, int N);
 int ab_honet_loss(const float* joints_3d_abs, const float* hand_verts_3d_abs, const float* obj_verts_3d_abs, const float* corners_3d_abs,
@@ -772,6 +784,7 @@ int ab_mssd(const float* can, const float* obj_transf, const int64_t* obj_idx, c
  * @check ab_honet_recover_fwd: strided: hand_st obj_st; cam_intr rotmat >= B*9; joints_3d joints_3d_abs >= B*63; hand_verts_3d hand_verts_3d_abs >= B*778*3; obj_verts_can obj_verts_3d_abs obj_verts_3d >= B*N*3; corners_can corners_3d_abs corners_3d >= B*24; root_joint obj_center >= B*3; joints_2d >= B*42; hand_verts_2d >= B*778*2; obj_verts_2d >= B*N*2; corners_2d >= B*16
  * @check ab_honet_recover_bwd: strided: hand_st obj_st g_hand_st g_obj_st; cam_intr g_rotmat >= B*9; joints_3d g_joints_3d_abs g_joints_3d >= B*63; hand_verts_3d g_hand_verts_3d_abs g_hand_verts_3d >= B*778*3; obj_verts_can g_obj_verts_3d_abs g_obj_verts_3d >= B*N*3; corners_can g_corners_3d_abs g_corners_3d >= B*24; g_root_joint g_obj_center >= B*3; g_joints_2d >= B*42; g_hand_verts_2d >= B*778*2; g_obj_verts_2d >= B*N*2; g_corners_2d >= B*16; bytes workspace >= ab_honet_recover_workspace(B,N)
  * @check ab_mesh_queries: table >= n_obj*n*3; obj_id >= B; obj_transf >= B*16; root_joint >= B*3; hand_verts hand_verts_3d >= B*778*3; bytes samples >= (B-1)*sample_pitch+pose_offset+64; obj_verts_can obj_verts_3d >= B*n*3
+ * @check ab_real_mesh_queries: table >= n_rows*n*3; row >= B; obj_map hand_map >= B*12; mano_verts hand_verts_3d >= B*778*3; obj_verts_can obj_verts_3d >= B*n*3
  * @check ab_honet_loss: joints_3d_abs joints_3d g_joints_3d_abs >= B*63; hand_verts_3d_abs hand_verts_3d g_hand_verts_3d_abs >= B*778*3; obj_verts_3d_abs obj_verts_3d g_obj_verts_3d_abs >= B*N*3; corners_3d_abs corners_3d >= B*24; mano_pca_pose g_mano_pca_pose >= B*(3+ncomps); mano_shape g_mano_shape >= B*10; root_joint >= B*3; weights7_host >= 7; sample_part >= B*8; losses >= 8; bytes workspace >= ab_honet_loss_workspace(B,N)
  * @check ab_mano_fit: quat >= B*64; pred_joints >= B*63; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; J_template >= 48; J_shapedirs >= 480; params adam_m adam_v grad >= B*59; verts >= B*778*3; joints >= B*63; loss >= B*n_iter
  * @check ab_draw_meshes: hand_verts >= B*778*3; hand_faces >= nhf*3; adj_off >= 779; adj_face >= nadj; obj_verts obj_normals >= nov*3; obj_faces >= nof*3; obj_vert_off obj_face_off >= n_obj+1; obj_id >= B; obj_rot >= B*9; obj_tsl >= B*3; corners >= B*24; cam_intr >= B*9; image >= B*3*H*W; out >= B*H*4*W*3; bytes workspace >= ab_draw_workspace_bytes(B,W,H,max_obj_verts)

@@ -1,5 +1,13 @@
 """Per-batch cost of the real-data half (realdata.RealBatcher) at HO3D frame size, frames already decoded in host memory:
-host GT assembly + upload + ab_augment_batch, and the mixed real/synthetic batch of MixedLoader."""
+host GT assembly + upload + ab_augment_batch, and the mixed real/synthetic batch of MixedLoader.
+
+  --mesh-queries N   (default 0: everything above, output unchanged)  instead: what the mesh queries of REAL frames cost (DESIGN.md
+                     section 22).  Alternating pairs in one process (N = 0, N, 0, N, ...; N = 0 is the batch without the argument):
+                       real_batch_ms   RealBatcher.batch of 40 decoded 640 x 480 frames, wall time per batch ending in a synchronise
+                       mixed_batch_ms  one MixedLoader batch (40 real + 24 synthetic, 224 x 224), both halves with / without the queries
+                     and, at N alone (HoNet cannot read a batch without them), honet_step_ms: the fused, graph-replayed HoNet step of
+                     config/ho3dv2_honet_mi355x_fused.yaml over those mixed batches behind ThreadedPrefetcher(depth=2).  Medians and ranges
+                     over --pairs pairs, one JSON line."""
 import os
 import sys
 import time
@@ -91,6 +99,88 @@ class PngFileSource(JpegFileSource):
             self.get_image_bytes = None
 
 
+class MeshMemorySource(MemorySource):
+    """MemorySource with seeded MANO annotations and four canonical meshes of 2000 vertices (realdata.HOdataSource.get_mesh_annots)."""
+
+    def __init__(self, n=256, seed=0):
+        super().__init__(n, seed)
+        rng = np.random.default_rng(seed + 1)
+        self.meshes = (rng.uniform(-1, 1, (4, 2000, 3)) * [0.04, 0.06, 0.09]).astype(np.float32)
+        self.mesh = [dict(hand_pose=rng.normal(0, 0.3, 48).astype(np.float32), hand_shape=rng.normal(0, 1, 10).astype(np.float32),
+                          hand_tsl=np.array([0.0, 0.0, -0.55], np.float32), table_row=i % 4) for i in range(n)]
+
+    def get_mesh_annots(self, idx):
+        return self.mesh[idx]
+
+    def mesh_vertex_table(self, n):
+        return self.meshes[:, (np.arange(n) * 2000) // n if n <= 2000 else np.arange(n) % 2000], {str(i): i for i in range(4)}
+
+
+def mesh_queries_ab(N, pairs=15, inner=5):
+    """--mesh-queries N: see the module docstring."""
+    import json
+    import random
+    import statistics
+    from artiboost_amd import registry as R
+    from artiboost_amd.criterions import Criterion
+    from artiboost_amd.models import Arch
+    from artiboost_amd.netutils import build_optimizer
+    from artiboost_amd.realdata import ThreadedPrefetcher
+    from artiboost_amd.train import TrainStep
+    import artiboost_amd.honet  # noqa: F401
+    cfg = yaml.safe_load(open(os.path.join(ROOT, "config", "ho3dv2_honet_mi355x_fused.yaml")))
+    preset = cfg["DATA_PRESET"]
+    B, assets = 64, SceneAssets("HO3D", seed=1)
+    src = MeshMemorySource(n=4096)
+    synth_len = int(0.6 * len(src))
+    n_synth = MixedLoader.n_synth_for(B, len(src), synth_len)
+
+    def mixed(n, cdt=torch.float32, **kw):
+        random.seed(5); torch.manual_seed(5); np.random.seed(5)
+        synth = ArtiBoostLoader.from_assets(assets, dict(cfg["MANAGER"], MESH_QUERIES=n), preset, n_synth, synth_len, compute_dtype=cdt)
+        synth.prepare()
+        return MixedLoader(RealBatcher(src, preset, compute_dtype=cdt, mesh_queries=n, mano=synth.mano if n else None), synth, B, **kw)
+
+    def wall(fn):
+        torch.cuda.synchronize(); t0 = time.time()
+        for _ in range(inner):
+            fn()
+        torch.cuda.synchronize()
+        return (time.time() - t0) / inner * 1e3
+
+    stat = lambda v: dict(median=round(statistics.median(v), 4), min=round(min(v), 4), max=round(max(v), 4))      # noqa: E731
+    mls = {n: mixed(n) for n in (0, N)}
+    idxs = list(range(mls[0].n_real))
+    its = {n: iter(ml) for n, ml in mls.items()}
+    real_ms, mixed_ms = {0: [], N: []}, {0: [], N: []}
+    for n in (0, N):                                      # warm-up: allocator, the vertex table upload
+        mls[n].real.batch(idxs); next(its[n])
+    for _ in range(pairs):
+        for n in (0, N):
+            real_ms[n].append(wall(lambda: mls[n].real.batch(idxs)))
+        for n in (0, N):
+            mixed_ms[n].append(wall(lambda: next(its[n])))
+    # the fused HoNet step over mixed batches with the queries
+    ml = mixed(N, cdt="u8n", want_chw=False, reuse_buffers=4)      # as train/train_artiboost.py builds it for a bf16x3 model
+    arch = dict(cfg["ARCH"], COMPUTE_DTYPE="bf16x3", DEVICE="cuda", INIT_SEED=3)
+    model = Arch({"ARCH": arch}, R.build_arch_model_list(arch, preset_cfg=preset))
+    crit = Criterion(cfg, R.build_criterion_loss_list(cfg["CRITERION"], preset_cfg=preset, LAMBDAS=cfg["LAMBDAS"]))
+    opt = build_optimizer(model.models_params, **cfg["TRAIN"])
+    opt.max_norm = cfg["TRAIN"]["GRAD_CLIP"]
+    model.train()
+    it = iter(ThreadedPrefetcher(ml, depth=2))
+    ts = TrainStep(model, crit, opt, {k: v.clone() for k, v in next(it).items()}, use_graph=True, renderer=None)
+    assert ts.fused is not None and ts.use_graph
+    for _ in range(3):
+        ts(next(it))
+    step_ms = [wall(lambda: ts(next(it))) for _ in range(pairs)]
+    it.close()
+    print(json.dumps({"bench": "real_mesh_queries", "N": N, "B": B, "n_real": mls[0].n_real, "n_synth": mls[0].n_synth, "pairs": pairs,
+                      "inner": inner, "real_batch_ms": {str(n): stat(v) for n, v in real_ms.items()},
+                      "mixed_batch_ms": {str(n): stat(v) for n, v in mixed_ms.items()}, "honet_step_ms": {str(N): stat(step_ms)},
+                      "final_loss": float(ts.fused.out["losses"][5])}))
+
+
 def jpeg_compare(cfg):
     """40 real frames per batch from .jpg files: decode on the device vs Pillow on this host (one thread, as one DataLoader worker)."""
     for dev_dec in (True, False):
@@ -170,6 +260,14 @@ def train_loop(cfg, steps=30, modes=("same stream", "same stream, frames of 4 ba
 
 
 def main():
+    import argparse
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mesh-queries", type=int, default=0)
+    ap.add_argument("--pairs", type=int, default=15)
+    ap.add_argument("--inner", type=int, default=5)
+    a = ap.parse_args()
+    if a.mesh_queries > 0:
+        return mesh_queries_ab(a.mesh_queries, a.pairs, a.inner)
     cfg = yaml.safe_load(open(os.path.join(ROOT, "config", "ho3dv2_clasbased_artiboost_mi355x.yaml")))
     cfg["DATA_PRESET"]["IMAGE_SIZE"] = [256, 256]
     src = MemorySource(n=1024)

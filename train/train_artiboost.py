@@ -173,10 +173,14 @@ def main():
                              compute_dtype=("u8n" if getattr(getattr(model.model_list[0], "net", None), "x3", False) and os.environ.get("AB_IMAGE_PLANE", "u8n") == "u8n"
                                             else getattr(getattr(model.model_list[0], "net", None), "dtype", torch.float32)))
     mixed = None
+    # MANAGER.MESH_QUERIES covers both halves: the real frames' OBJ_VERTS_CAN / OBJ_VERTS_3D / hand_verts_3d come from the dataset's own MANO
+    # and object annotation through the loader's MANO layer
+    mesh_kw = dict(mesh_queries=int(cfg["MANAGER"].get("MESH_QUERIES", 0) or 0), mano=loader.mano)
     if real_len > 0:
         tr = cfg["DATASET"]["TRAIN"]
         mixed = MixedLoader(RealBatcher(train_data, cfg["DATA_PRESET"], aug=bool(tr.get("AUG", False)), aug_param=tr.get("AUG_PARAM") or None, device=dev,
-                                        compute_dtype=("u8n" if loader.image_plane == "u8n" else loader.dtype), seed=seed, num_workers=int(arg.workers) or None),
+                                        compute_dtype=("u8n" if loader.image_plane == "u8n" else loader.dtype), seed=seed, num_workers=int(arg.workers) or None,
+                                        **mesh_kw),
                             loader, per_rank, seed=seed, rank=rank, world_size=world, want_chw=False, reuse_buffers=4)      # TrainStep copies a batch in
     epoch0 = 0
     if arg.resume:
@@ -199,7 +203,7 @@ def main():
                 from artiboost_amd.realdata import RealBatcher
                 if "real" not in test_state:
                     test_state["real"] = RealBatcher(test_data, cfg["DATA_PRESET"], aug=False, device=dev,
-                                                    compute_dtype=("u8n" if loader.image_plane == "u8n" else loader.dtype), seed=seed)
+                                                    compute_dtype=("u8n" if loader.image_plane == "u8n" else loader.dtype), seed=seed, **mesh_kw)
                 rb = test_state["real"]
                 # shuffle=True, drop_last=False (train_artiboost.py:113-121).  Every rank evaluates the WHOLE test set (the reference's
                 # DataParallel process does): no cross-rank reduction of the evaluator is needed and rank 0's record covers every frame;
