@@ -309,6 +309,11 @@ static int launch_reduce(const float* slabs, int ns, long slab_elems, int src_j,
     return e == hipSuccess ? 0 : (int)e;
 }
 
+// A launch that runs as two half-batches (conv_x3.hip, X3_WGRAD_MAX_M) must not record its reductions: both halves write the same
+// slab workspace and one descriptor holds one reduction.  It calls this first; each half then reduces at once, in stream order,
+// and the *_deferred caller's descriptor keeps nslices == 0 (nothing pending).
+void wgrad_reduce_now() { g_reduce_sink = nullptr; }
+
 // the fixed-order slab reduction for the weight-gradient kernels of other translation units (conv_x3.hip)
 int wgrad_launch_reduce(const float* slabs, int ns, long slab_elems, int src_j, int dst_j, float* dst, int accumulate,
                         int stem_mask, hipStream_t st) {

@@ -56,6 +56,7 @@ int gemm_rw_run(const void* a_hi, const void* a_lo, const void* w_hi, const void
                 int K, const GemmRwSam* sam, hipStream_t st);
 int wgrad_launch_reduce(const float* slabs, int ns, long slab_elems, int src_j, int dst_j, float* dst, int accumulate,
                            int stem_mask, hipStream_t st);      // conv_wgrad.hip
+void wgrad_reduce_now();                                        // conv_wgrad.hip: a *_deferred call in progress reduces immediately instead
 
 // ---------------------------------------------------------------- fp32 -> (hi, lo) bf16 planes
 __global__ __launch_bounds__(256) void split_f32_kernel(const float* __restrict__ src, long nvec, bf16_t* __restrict__ hi,
@@ -428,6 +429,7 @@ extern "C" int ab_conv2d_wgrad_x3(const void* x_hi, const void* x_lo, const void
         const long Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
         if ((long)N * Ho * Wo >= X3_WGRAD_MAX_M && N > 1) {
             const int n1 = N / 2;
+            wgrad_reduce_now();             // (the halves share the workspace: a deferred call cannot record two reductions over it)
             const long xo = (long)n1 * H * W * Cin, yo = (long)n1 * Ho * Wo * Cout;
             int rc = ab_conv2d_wgrad_x3(x_hi, x_lo, dy_hi, dy_lo, dw, n1, H, W, Cin, Cout, kh, kw, stride, pad, workspace, accumulate, stream);
             if (rc) return rc;
@@ -469,6 +471,7 @@ static int stem_wgrad_x3_impl(const bf16_t* xpad_hi, const bf16_t* xpad_lo, cons
                               int H, int W, int Cout, void* workspace, int accumulate, hipStream_t st) {
     if ((long)N * (H / 2) * (W / 2) >= X3_WGRAD_MAX_M && N > 1) {         // two half-batches (see X3_WGRAD_MAX_M)
         const int n1 = N / 2;
+        wgrad_reduce_now();
         const long xo = (long)n1 * (H + 6) * (W + 8) * 4, yo = (long)n1 * (H / 2) * (W / 2) * Cout;
         int rc = stem_wgrad_x3_impl(xpad_hi, xpad_lo, dy_hi, dy_lo, dw, n1, H, W, Cout, workspace, accumulate, st);
         if (rc) return rc;

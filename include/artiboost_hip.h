@@ -107,7 +107,9 @@ int ab_conv2d_wgrad(const void* x, const void* dy, float* dw, int dtype, int N, 
                     int kh, int kw, int stride, int pad, void* workspace, int accumulate, void* stream);
 /* Deferred slab reduction: the *_deferred variants run the slab kernel and record the fixed-order reduction they would
  * launch; ab_wgrad_reduce_batch runs the recorded reductions of many layers in one launch (bit-identical results).  The
- * workspace of a deferred call must stay untouched until its descriptor has been consumed.                          */
+ * workspace of a deferred call must stay untouched until its descriptor has been consumed.  A split-bf16 launch of 2^21 or
+ * more output pixels runs as two half-batches over one workspace: its *_x3_deferred call reduces both halves itself, in stream
+ * order, and returns pending->nslices == 0 (dw is then complete without ab_wgrad_reduce_batch).                      */
 #define AB_WGRAD_BATCH_MAX 48
 typedef struct ab_wgrad_reduce_desc {
     const float* slabs;    /* [nslices][slab_elems] partial weight gradients */

@@ -452,7 +452,7 @@ def test_wgrad_bf16_deferred_reduction_with_exact_workspace(case):
 
 def test_stem_wgrad_x3_beyond_2p21_pixels():
     """A stem weight gradient over more than 2^21 output pixels (batch 128 at 256 x 256 -- the reference YAML's TRAIN.BATCH_SIZE on
-    one GPU) runs as two half-batches; same result as the sum of the halves computed separately."""
+    one GPU) runs as two half-batches; same result as the sum of the halves computed separately, immediate and deferred."""
     from artiboost_amd import kernels as K
     N, H, W = 130, 256, 256
     g = torch.Generator().manual_seed(1)
@@ -465,6 +465,11 @@ def test_stem_wgrad_x3_beyond_2p21_pixels():
     b = K.conv2d_stem_wgrad_x3(xpad[:, h:].contiguous(), dy[:, h:].contiguous(), H, W)
     ref = a.double() + b.double()
     assert float((dw.double() - ref).abs().max()) <= 1e-5 * float(ref.abs().max())
+    # the deferred entry point on the same operands: the halves share one workspace, so it reduces both itself and records nothing
+    pend = K.PendingReductions()
+    deferred = K.conv2d_stem_wgrad_x3(xpad, dy, H, W, out=torch.full_like(dw, 7.0), defer=pend)
+    pend.flush()
+    assert torch.equal(deferred, dw)
 
 
 @pytest.mark.parametrize("case", [(16, 32, 32, 256, 704, 1, 1, 0),     # 256 x 256 tiles, partial last channel tile (704 = 2.75 x 256)
