@@ -4,6 +4,7 @@
 The ordinal losses draw from the same global RNGs in the same order as the reference (torch.rand for the virtual
 view vectors, random.shuffle for the pair subsets), so seeding `random` and `torch` identically reproduces the
 reference's loss values.  Tensors here are tiny ((B,21,3)-sized); the arithmetic runs as device torch ops."""
+import ctypes
 import os
 import random
 from itertools import combinations, product
@@ -84,10 +85,7 @@ class Criterion(TensorLoss):
         key = (tuple(link["inp_res"]), link["center_idx"])
         cache = self.__dict__.setdefault("_fused_cache", {})
         if key not in cache:
-            try:
-                cache[key] = FusedPoseCriterion(self, link["inp_res"], link["center_idx"])
-            except NotImplementedError:
-                cache[key] = None
+            cache[key] = fused_or_none(FusedPoseCriterion, self, link["inp_res"], link["center_idx"])
         return cache[key]
 
     def _compute_losses_fused(self, link, targs):
@@ -462,13 +460,52 @@ class _FusedLossFn(torch.autograd.Function):
         return gk * g_total, gb * g_total, None, None
 
 
-class FusedPoseCriterion:
+def fused_or_none(cls, *args):
+    """cls(*args), or None when the criterion holds a loss outside that kernel: the registry losses then run through autograd."""
+    try:
+        return cls(*args)
+    except NotImplementedError:
+        return None
+
+
+class _FusedCriterion:
+    """What the fused criteria share: each wraps a `Criterion` (self.crit), leaves its kernel's outputs in self.out and reports the
+    kernel's loss vector (LOSS_WIDTH floats) under the registry route's keys."""
+    LOSS_WIDTH = 8           # floats of the kernel's loss vector
+    _last = None             # the slots of the last call, where they depend on that call's targets
+
+    def draw(self, dev):
+        self.crit.draw(dev)
+
+    def _set_keys(self, key_slots):
+        """key_slots: key -> slot of the loss vector (None: the registry route reports None), in the registry's own update order.
+        LOSS_KEYS is the vector's layout: the dict key each slot is reported under (None: not an entry of the loss dict)."""
+        self.key_slots, by_slot = key_slots, {s: k for k, s in key_slots.items()}
+        self.LOSS_KEYS = tuple(by_slot.get(i) for i in range(self.LOSS_WIDTH))
+
+    def losses_dict(self):
+        """Host view of the loss scalars of the last call under the keys of Criterion.compute_losses (synchronises)."""
+        v = self.out["losses"].cpu()
+        return {k: (None if s is None else v[s]) for k, s in (self._last or self.key_slots).items()}
+
+    def _ordinal_args(self):
+        """The ordinal-draw arguments of ab_pose_loss_sym / ab_reg_pose_loss: hand views, nvh, j0, j1, count, p0, p1, count, scene
+        views, nvs, i0, i1, count (null / 0 without that loss)."""
+        from . import _lib as L
+        hb = self.hand.draws.bufs if self.hand is not None else {}
+        sb = self.scene.draws.bufs if self.scene is not None else {}
+        n = lambda b, k: L.i(b[k].numel() if b else 0)   # noqa: E731
+        return (L.ptr(hb.get("views")), L.i(hb["views"].shape[0] if hb else 0), L.ptr(hb.get("j0")), L.ptr(hb.get("j1")), n(hb, "j0"),
+                L.ptr(hb.get("p0")), L.ptr(hb.get("p1")), n(hb, "p0"),
+                L.ptr(sb.get("views")), L.i(sb["views"].shape[0] if sb else 0), L.ptr(sb.get("i0")), L.ptr(sb.get("i1")), n(sb, "i0"))
+
+
+class FusedPoseCriterion(_FusedCriterion):
     """Pose assembly + JointsLoss + HandOrdLoss + SceneOrdLoss + per-sample EPE + backward in ONE HIP kernel
     (csrc/pose_loss.hip).  Built from a `Criterion` whose loss list is [JointsLoss, HandOrdLoss, SceneOrdLoss] (any
     subset); uses that criterion's draw buffers so the RNG behaviour is the reference's."""
 
     def __init__(self, criterion: Criterion, inp_res, center_idx=0):
-        import ctypes
         self.crit = criterion
         self.inp_res = inp_res
         self.center_idx = center_idx
@@ -494,9 +531,6 @@ class FusedPoseCriterion:
         self.weights = (ctypes.c_float * 8)(*w)
         self.out = None
 
-    def draw(self, dev):
-        self.crit.draw(dev)
-
     def _alloc(self, B, dev):
         z = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)   # noqa: E731
         self.out = dict(joints_3d_abs=z(B, 21, 3), corners_3d_abs=z(B, 8, 3), box_rot_rotmat=z(B, 3, 3),
@@ -510,14 +544,9 @@ class FusedPoseCriterion:
         if self.out is None or self.out["g_kp3d"].shape[0] != B:
             self._alloc(B, dev)
         o = self.out
-        hb = self.hand.draws.bufs if self.hand is not None else {}
-        sb = self.scene.draws.bufs if self.scene is not None else {}
-        nvh = hb["views"].shape[0] if hb else 0
-        nvs = sb["views"].shape[0] if sb else 0
         t = lambda k: targs[k]   # noqa: E731
         symp = None
         if self.sym is not None and self.sym.lambda_sym_corners_3d:
-            import ctypes
             if self._sym_dev is None or self._sym_dev[0].device != dev:
                 self._sym_dev = (self.sym.R.to(dev).contiguous(), self.sym.t.to(dev).reshape(self.sym.t.shape[0], -1, 3).contiguous())
             Rd, td = self._sym_dev
@@ -530,10 +559,7 @@ class FusedPoseCriterion:
         L.check(L.lib().ab_pose_loss_sym(
             L.ptr(kp3d), L.ptr(box6d_buf), L.i(box_stride), L.ptr(t(Queries.ROOT_JOINT)), L.ptr(t(Queries.CAM_INTR)),
             L.ptr(t(Queries.CORNERS_CAN)), L.ptr(t(Queries.JOINTS_3D)), L.ptr(t(Queries.CORNERS_3D)),
-            L.ptr(t(Queries.JOINTS_VIS)), L.ptr(t(Queries.CORNERS_VIS)),
-            L.ptr(hb.get("views")), L.i(nvh), L.ptr(hb.get("j0")), L.ptr(hb.get("j1")), L.i(hb["j0"].numel() if hb else 0),
-            L.ptr(hb.get("p0")), L.ptr(hb.get("p1")), L.i(hb["p0"].numel() if hb else 0),
-            L.ptr(sb.get("views")), L.i(nvs), L.ptr(sb.get("i0")), L.ptr(sb.get("i1")), L.i(sb["i0"].numel() if sb else 0),
+            L.ptr(t(Queries.JOINTS_VIS)), L.ptr(t(Queries.CORNERS_VIS)), *self._ordinal_args(),
             L.i(B), L.i(self.center_idx), L.f(self.inp_res[0]), L.f(self.inp_res[1]), self.weights, symp,
             L.ptr(o["joints_3d_abs"]), L.ptr(o["corners_3d_abs"]), L.ptr(o["box_rot_rotmat"]), L.ptr(o["uvd2d"]),
             L.ptr(o["sample_part"]), L.ptr(o["losses"]), L.ptr(o["g_kp3d"] if backward else None),
@@ -541,17 +567,16 @@ class FusedPoseCriterion:
         return o
 
     LOSS_KEYS = ("joints_3d_loss", "corners_3d_loss", "joint_ord_loss", "part_ord_loss", "scene_ord_loss", "final_loss")
+    key_slots = {k: i for i, k in enumerate(LOSS_KEYS)}      # (the vector's last two slots are no entries of the loss dict)
 
     def losses_dict(self):
-        """Host view of the loss scalars of the last call (synchronises)."""
-        v = self.out["losses"].cpu()
-        d = {k: v[i] for i, k in enumerate(self.LOSS_KEYS)}
+        d = super().losses_dict()
         if self.sym is not None:
             d["sym_corners_3d_loss"] = self.out["sym_loss"].cpu()[0]
         return d
 
 
-class FusedRegCriterion:
+class FusedRegCriterion(_FusedCriterion):
     """The regression-based model's criterion in ONE HIP kernel (ab_reg_pose_loss, csrc/pose_loss.hip): HOPRegNet's assembly
     (hpregnet.mano_outputs / object_outputs: joints + the target's root, corners = R(transf[3:9]) can + root + transf[0:3]) +
     ManoLoss + JointsLoss + HandOrdLoss + SceneOrdLoss + per-sample EPE + backward down to MANO's joints, the PCA pose, the shape
@@ -562,7 +587,6 @@ class FusedRegCriterion:
     LOSS_WIDTH = 16          # floats of the kernel's loss vector
 
     def __init__(self, criterion: Criterion, ncomps, example_batch=None):
-        import ctypes
         self.crit = criterion
         self.ncomps = int(ncomps)
         w = [0.0] * 12
@@ -597,18 +621,9 @@ class FusedRegCriterion:
         if self.mano.lambda_hand_verts_3d and example_batch is not None and "hand_verts_3d" in example_batch:
             raise NotImplementedError("ManoLoss's hand-vertex term (a hand_verts_3d target with LAMBDA_HAND_VERTS_3D != 0)")
         d["final_loss"] = 5
-        self.key_slots = d
-        # the vector's layout: the dict key each slot is reported under (None: not an entry of the loss dict)
-        keys = [None] * self.LOSS_WIDTH
-        for k, s in d.items():
-            if s is not None:
-                keys[s] = k
-        self.LOSS_KEYS = tuple(keys)
+        self._set_keys(d)
         self.weights = (ctypes.c_float * 12)(*[float(x) for x in w])
         self.out = None
-
-    def draw(self, dev):
-        self.crit.draw(dev)
 
     def _alloc(self, B, dev):
         z = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)   # noqa: E731
@@ -632,41 +647,29 @@ class FusedRegCriterion:
         gt = g_transf if g_transf is not None else o["g_transf"]
         if backward and (gt.stride(0) != stride or transf.stride(1) != 1 or gt.stride(1) != 1):
             raise ValueError("g_transf must have transf's row pitch")
-        hb = self.hand.draws.bufs if self.hand is not None else {}
-        sb = self.scene.draws.bufs if self.scene is not None else {}
         t = lambda k: targs[k]   # noqa: E731
         L.check(L.lib().ab_reg_pose_loss(
             L.ptr(joints_3d), L.ptr(mano_pca_pose), L.ptr(mano_shape), L.view_ptr(transf), L.i(stride),
             L.ptr(t(Queries.ROOT_JOINT)), L.ptr(t(Queries.CAM_INTR)), L.ptr(t(Queries.CORNERS_CAN)), L.ptr(t(Queries.JOINTS_3D)),
-            L.ptr(t(Queries.CORNERS_3D)), L.ptr(t(Queries.JOINTS_VIS)), L.ptr(t(Queries.CORNERS_VIS)),
-            L.ptr(hb.get("views")), L.i(hb["views"].shape[0] if hb else 0), L.ptr(hb.get("j0")), L.ptr(hb.get("j1")),
-            L.i(hb["j0"].numel() if hb else 0), L.ptr(hb.get("p0")), L.ptr(hb.get("p1")), L.i(hb["p0"].numel() if hb else 0),
-            L.ptr(sb.get("views")), L.i(sb["views"].shape[0] if sb else 0), L.ptr(sb.get("i0")), L.ptr(sb.get("i1")),
-            L.i(sb["i0"].numel() if sb else 0), L.i(B), L.i(self.ncomps), self.weights,
+            L.ptr(t(Queries.CORNERS_3D)), L.ptr(t(Queries.JOINTS_VIS)), L.ptr(t(Queries.CORNERS_VIS)), *self._ordinal_args(),
+            L.i(B), L.i(self.ncomps), self.weights,
             L.ptr(o["joints_3d_abs"]), L.ptr(o["corners_3d_abs"]), L.ptr(o["box_rot_rotmat"]), L.ptr(o["sample_part"]), L.ptr(o["losses"]),
             L.ptr(o["g_joints"] if backward else None), L.ptr(o["g_pose"] if backward else None), L.ptr(o["g_shape"] if backward else None),
             L.view_ptr(gt if backward else None), L.stream()), "ab_reg_pose_loss")
         return o
 
-    def losses_dict(self):
-        """Host view of the loss scalars of the last call under the keys of Criterion.compute_losses (synchronises)."""
-        v = self.out["losses"].cpu()
-        return {k: (None if s is None else v[s]) for k, s in self.key_slots.items()}
 
-
-class FusedMeshCriterion:
+class FusedMeshCriterion(_FusedCriterion):
     """HoNet's criterion in ONE HIP kernel + a finalize pass (ab_honet_loss, csrc/honet_loss.hip): ManoLoss with all four terms -- the
     hand-vertex term included -- + ObjLoss + per-sample EPE + the gradient of final_loss wrt joints_3d_abs, hand_verts_3d_abs,
     obj_verts_3d_abs, mano_pca_pose and mano_shape.  Built from a `Criterion` whose list is [ManoLoss] or [ManoLoss, ObjLoss]; anything else
     raises NotImplementedError (the registry losses then run through autograd).  A term whose target the batch does not carry is dropped, as
     the registry classes drop it (`key in targs`); `example_batch` fixes which ones the loss record reports."""
 
-    LOSS_WIDTH = 8           # floats of the kernel's loss vector
     _SLOTS = ("mano_shape", "mano_pca_pose", "joints_3d_loss", "hand_verts_3d_loss", "obj_verts_3d_loss", "final_loss")
     _TARGET = {"joints_3d_loss": Queries.JOINTS_3D, "hand_verts_3d_loss": "hand_verts_3d", "obj_verts_3d_loss": Queries.OBJ_VERTS_3D}
 
     def __init__(self, criterion: Criterion, ncomps, example_batch=None):
-        import ctypes
         self.crit = criterion
         self.ncomps = int(ncomps)
         self.mano = self.obj = None
@@ -687,12 +690,7 @@ class FusedMeshCriterion:
             self._on["obj_verts_3d_loss"] = bool(self.obj.lambda_obj_verts_3d)
             w[4], w[6] = self.obj.lambda_obj_verts_3d, lam["ObjLoss"]
         self.weights = (ctypes.c_float * 7)(*[float(x) for x in w])
-        self.key_slots = self._slots_for(example_batch)
-        keys = [None] * self.LOSS_WIDTH
-        for k, s in self.key_slots.items():
-            if s is not None:
-                keys[s] = k
-        self.LOSS_KEYS = tuple(keys)
+        self._set_keys(self._slots_for(example_batch))
         self.out = None
 
     def _slots_for(self, targs):
@@ -742,11 +740,6 @@ class FusedMeshCriterion:
             L.ptr(g("g_obj_verts_3d_abs")), L.ptr(g("g_mano_pca_pose")), L.ptr(g("g_mano_shape")), L.ptr(o["workspace"]), L.stream()),
             "ab_honet_loss")
         return o
-
-    def losses_dict(self):
-        """Host view of the loss scalars of the last call under the keys of Criterion.compute_losses (synchronises)."""
-        v = self.out["losses"].cpu()
-        return {k: (None if s is None else v[s]) for k, s in self._last.items()}
 
 
 # ---- mesh-level losses (DESIGN.md section 19) --------------------------------------------------------------------------------------------

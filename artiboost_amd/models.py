@@ -389,6 +389,41 @@ class SimpleBaseline(HybridBaseline):
                 "corners_3d": corners_3d_abs - root_joint.unsqueeze(1), "2d_uvd": kp3d}
 
 
+class PoseRoute:
+    """TrainStep's route for HybridBaseline (a model with the MLP_O box head): the fused pose/loss kernel is its assembly.  The only
+    route whose backward can be captured in stages (HybridNet.BWD_STAGES) for the all-reduce overlap."""
+    splittable, pipelinable = True, True
+
+    @staticmethod
+    def criterion(ts, example_batch):
+        from .criterions import FusedPoseCriterion, fused_or_none
+        return fused_or_none(FusedPoseCriterion, ts.crit, ts.hb.inp_res, ts.hb.center_idx)
+
+    @staticmethod
+    def fwd_bwd(ts):
+        """HIP forward -> fused soft-argmax -> fused pose+criterion(+backward) -> HIP backward, no autograd."""
+        hb, net, st = ts.hb, ts.hb.net, ts.static
+        logits, _ = net.forward(image=st.get(Queries.IMAGE), xpad=st.get("image_nhwc4_padded"))
+        kp3d, conf, stat = net.head_fwd(logits)
+        o = ts.fused(kp3d, net.last["box_raw"], net.last["box_raw"].shape[-1], st)
+        dlogits = net.head_bwd(logits, kp3d, conf, stat, o["g_kp3d"])
+        net.backward(dlogits, o["g_box6d"], stage=0 if ts._capturing_split else None)
+        hb.flat_param.grad = hb.store.grad
+        return dict(o, kp3d=kp3d, kp3d_confd=conf), o["losses"], o
+
+    @staticmethod
+    def predictions(ts):
+        """The NINE keys HybridBaseline.forward returns (hybridbaseline.py:86-96).  The fused path keeps only what the criterion kernel writes;
+        the root-relative and box-root entries the evaluator's PCK / visual metrics read are derived here (small device ops, outside the graphs)."""
+        o, st, c = ts.fused.out, ts.static, ts.hb.center_idx
+        ja, ca, R = o["joints_3d_abs"], o["corners_3d_abs"], o["box_rot_rotmat"]
+        root = ja[:, c:c + 1]
+        can = st[Queries.CORNERS_CAN].to(ca.dtype)
+        boxroot = (ca - torch.matmul(R, can.permute(0, 2, 1)).permute(0, 2, 1)).mean(1, keepdim=True)
+        return {"joints_3d_abs": ja, "corners_3d_abs": ca, "joints_3d": ja - root, "corners_3d": ca - root, "2d_uvd": o["uvd2d"],
+                "boxroot_3d_abs": boxroot, "box_rot_rotmat": R, "kp3d": ts.out[0]["kp3d"], "kp3d_confd": ts.out[0]["kp3d_confd"]}
+
+
 class Arch(nn.Module):
     """anakin/models/arch.py:11-72: DAG of models keyed by TYPE with PREVIOUS edges."""
 

@@ -153,13 +153,18 @@ class HOPRegNetHIP(nn.Module):
     def _lin(self, x, name, relu=False):
         return K.linear_fwd(x, self._w(name), self.store.view(name + ".bias"), relu=relu)
 
-    def _run(self, image, xpad, save):
-        """-> (mano_pca_pose [N,3+ncomps], mano_shape [N,10], hand_verts_3d [N,778,3], joints_3d [N,21,3], mano_full_pose [N,48], transf [N,9])."""
-        fmean = self.net.forward(image=image, xpad=xpad)                    # res_layer4_mean [N, 512] f32
+    def _mano_heads(self, fmean):
+        """ManoBranch's heads on res_layer4_mean: -> (h1, h2, mano_pca_pose [N,3+ncomps], mano_shape [N,10])."""
         h1 = self._lin(fmean, HEADS[0], relu=True)
         h2 = self._lin(h1, HEADS[1], relu=True)
         pose = self._lin(h2, HEADS[2])[:, :self.P].contiguous()
         shape = self._lin(h2, HEADS[3])[:, :10].contiguous()
+        return h1, h2, pose, shape
+
+    def _run(self, image, xpad, save):
+        """-> (mano_pca_pose [N,3+ncomps], mano_shape [N,10], hand_verts_3d [N,778,3], joints_3d [N,21,3], mano_full_pose [N,48], transf [N,9])."""
+        fmean = self.net.forward(image=image, xpad=xpad)                    # res_layer4_mean [N, 512] f32
+        h1, h2, pose, shape = self._mano_heads(fmean)
         d1 = self._lin(fmean, HEADS[4], relu=True)
         transf = self._lin(d1, HEADS[5])[:, :9].contiguous()
         verts, joints, full = K.mano_pca_fwd(pose, shape, self.mano, self.center_idx)
@@ -213,11 +218,15 @@ class HOPRegNetHIP(nn.Module):
         K.linear_wgrad(gd, S["fmean"], self._gv(dec), self._gb(dec))
         return gd
 
-    def _backward(self, g_pose, g_shape, g_verts, g_joints, g_full, g_transf):
-        S = self._saved
+    def _take_saved(self):
+        """The activations of the last grad-mode forward, handed over once."""
+        S, self._saved = self._saved, None
         if S is None:
             raise RuntimeError("backward without a grad-mode training forward")
-        self._saved = None
+        return S
+
+    def _backward(self, g_pose, g_shape, g_verts, g_joints, g_full, g_transf):
+        S = self._take_saved()
         N = S["fmean"].shape[0]
         c = lambda t: None if t is None else t.contiguous().float()      # noqa: E731
         gt = self._padded(HEADS[5], N, c(g_transf))
@@ -253,6 +262,34 @@ class HOPRegNetHIP(nn.Module):
                 pose, shape, verts, joints, full, transf = self._run(image, xpad, save=False)
         mano = {"hand_verts_3d": verts, "joints_3d": joints, "mano_shape": shape, "mano_pca_pose": pose, "mano_full_pose": full}
         return combine_outputs(mano_outputs(mano, inputs, dev), object_outputs(transf, inputs, dev))
+
+
+class RegRoute:
+    """TrainStep's route for a model that declares FUSED_STEP (HOPRegNet built with ARCH.FUSED_STEP): its own fused criterion and two linear
+    graphs; the trunk-only layout has no staged backward, so with a process group the all-reduce runs between the two graphs, unsplit."""
+    splittable, pipelinable = False, True
+
+    @staticmethod
+    def criterion(ts, example_batch):
+        from .criterions import FusedRegCriterion, fused_or_none
+        return fused_or_none(FusedRegCriterion, ts.crit, ts.hb.ncomps, example_batch)      # (None also for a hand_verts_3d target)
+
+    @staticmethod
+    def fwd_bwd(ts):
+        """Trunk + heads + MANO -> fused regbased criterion (+backward) -> MANO / heads / trunk backward, no autograd."""
+        hb, st = ts.hb, ts.static
+        pose, shape, verts, joints, full, transf = hb._run(st.get(Queries.IMAGE), st.get("image_nhwc4_padded"), save=True)
+        o = ts.fused(joints, pose, shape, transf, st)
+        hb._backward(o["g_pose"], o["g_shape"], None, o["g_joints"], None, o["g_transf"])
+        hb.flat_param.grad = hb.store.grad
+        bridge = {"hand_verts_3d": verts, "joints_3d": joints, "mano_shape": shape, "mano_pca_pose": pose, "mano_full_pose": full, "transf": transf}
+        return bridge, o["losses"], o
+
+    @staticmethod
+    def predictions(ts):
+        """HOPRegNet's 18 keys from the bridge outputs (the camera projections stay torch ops, as in its forward)."""
+        mano = {k: v for k, v in ts.out[0].items() if k != "transf"}
+        return combine_outputs(mano_outputs(mano, ts.static, ts.dev), object_outputs(ts.out[0]["transf"], ts.static, ts.dev))
 
 
 # ------------------------------------------------------------------------------------------------ HoNet
@@ -312,10 +349,7 @@ class HoNetHIP(HOPRegNetHIP):
         """-> (mano_pca_pose, mano_shape, hand_verts_3d, joints_3d, mano_full_pose, hand_st [N,3], obj_st [N,6], *HONET_GEO)."""
         cam_intr, can, ccan = geo
         fmean = self.net.forward(image=image, xpad=xpad)                    # res_layer4_mean [N, 512] f32
-        h1 = self._lin(fmean, HEADS[0], relu=True)
-        h2 = self._lin(h1, HEADS[1], relu=True)
-        pose = self._lin(h2, HEADS[2])[:, :self.P].contiguous()
-        shape = self._lin(h2, HEADS[3])[:, :10].contiguous()
+        h1, h2, pose, shape = self._mano_heads(fmean)
         m1 = self._lin(fmean, HONET_TRANS[0], relu=True)
         hst = self._lin(m1, HONET_TRANS[1])[:, :3]                          # rows of the padded output: the kernels take the pitch
         o1 = self._lin(fmean, HONET_TRANS[2], relu=True)
@@ -327,10 +361,7 @@ class HoNetHIP(HOPRegNetHIP):
         return (pose, shape, verts, joints, full, hst, ost) + tuple(o[k] for k in HONET_GEO)
 
     def _backward(self, g_pose, g_shape, g_verts, g_joints, g_full, g_hst, g_ost, *g_geo):
-        S = self._saved
-        if S is None:
-            raise RuntimeError("backward without a grad-mode training forward")
-        self._saved = None
+        S = self._take_saved()
         N = S["fmean"].shape[0]
         c = lambda t: None if t is None else t.contiguous().float()      # noqa: E731
         cam_intr, can, ccan = S["geo"]
@@ -377,3 +408,38 @@ class HoNetHIP(HOPRegNetHIP):
                    obj_rot=ost[:, 3:], obj_scale=o_scale.reshape(B, 1, 1) * self.obj_scale_factor,
                    obj_trans=o_trans.unsqueeze(1) * self.obj_trans_factor, boxroot_3d_abs=res["obj_center"])
         return res
+
+
+class MeshRoute:
+    """TrainStep's route for a model that declares FUSED_MESH_STEP (HoNet built with ARCH.FUSED_MESH_STEP): the fused mesh criterion
+    (ab_honet_loss) on the recovery outputs and the same two linear graphs as RegRoute.  Its mesh queries are made from the render inputs
+    of the batch being learned, which the pipelined modes hold one batch ahead: the step renders and learns in order."""
+    splittable, pipelinable = False, False
+
+    @staticmethod
+    def criterion(ts, example_batch):
+        """A loader with MANAGER.MESH_QUERIES writes the three mesh queries inside the captured region (one ab_mesh_queries launch after
+        the render) into tensors allocated here, before the criterion looks at the batch and before any capture."""
+        from .criterions import FusedMeshCriterion, fused_or_none
+        if getattr(ts.renderer, "mesh_queries", 0) and hasattr(ts.renderer, "mesh_queries_into"):
+            ts.renderer.mesh_queries_into(ts.static)
+            ts.mesh_queries = True
+        return fused_or_none(FusedMeshCriterion, ts.crit, ts.hb.ncomps, ts.static)
+
+    @staticmethod
+    def fwd_bwd(ts):
+        """Trunk + heads + MANO + recovery -> fused mesh criterion (+backward) -> recovery / MANO / heads / trunk backward, no autograd.
+        The recovery stage reads the static batch's own tensors (cam_intr, obj_verts_can, corners_can): fixed addresses."""
+        hb, st = ts.hb, ts.static
+        out = hb._run(st.get(Queries.IMAGE), st.get("image_nhwc4_padded"), True, hb._geo_of(st))
+        rec = dict(zip(HONET_GEO, out[7:]))
+        o = ts.fused(rec["joints_3d_abs"], rec["hand_verts_3d_abs"], rec["obj_verts_3d_abs"], rec["corners_3d_abs"], out[0], out[1], st)
+        # the five gradients; the TransHead rows (g_hst / g_ost) and the untouched recovery outputs get none
+        hb._backward(o["g_mano_pca_pose"], o["g_mano_shape"], None, None, None, None, None, *(o.get("g_" + k) for k in HONET_GEO))
+        hb.flat_param.grad = hb.store.grad
+        return out, o["losses"], o
+
+    @staticmethod
+    def predictions(ts):
+        """HoNet's dict from the bridge outputs, as HoNetHIP.forward assembles it."""
+        return ts.hb._assemble(ts.out[0])

@@ -8,9 +8,13 @@ Adam bias corrections, CCV sample descriptors) go through small pinned -> device
 With world_size > 1 the backward is captured as three graphs; the RCCL all-reduce of each finished range of the flat
 gradient buffer runs on a side stream while the next stage computes."""
 import os
+import random
 
+import numpy as np
 import torch
 
+from .models import PoseRoute
+from .regnet import MeshRoute, RegRoute
 from .registry import IMAGE_PLANE_KEY, Queries, SynthQueries, image_plane_of, tag_image_plane
 
 
@@ -45,7 +49,31 @@ def rccl_env_defaults():
     os.environ.setdefault("NCCL_ALGO", "Ring")
 
 
+class PlainRoute:
+    """No fused criterion (SimpleBaseline, HOPRegNet / HoNet without their FUSED_* key, a loss outside the model's kernel): forward, registry losses, autograd."""
+    splittable, pipelinable = False, True
+    criterion = staticmethod(lambda ts, example_batch: None)
+    predictions = staticmethod(lambda ts: ts.out[0])
+
+    @staticmethod
+    def fwd_bwd(ts):
+        preds = ts.model(ts.static)[ts.model_key]
+        total, losses = ts.crit.compute_losses(preds, ts.static)
+        ts.opt.zero_grad(set_to_none=True)
+        total.backward()
+        return preds, total, losses
+
+
+def route_of(hb):
+    """The route table: what the model declares -> who builds the fused criterion, runs one forward + backward on the static batch and names
+    the predictions (`criterion`, `fwd_bwd`, `predictions`), and whether the step may be split / pipelined.  A route lives with its model."""
+    return (MeshRoute if getattr(hb, "FUSED_MESH_STEP", False) else RegRoute if getattr(hb, "FUSED_STEP", False) else
+            PoseRoute if getattr(hb, "HAS_BOX_HEAD", True) else PlainRoute)      # (SimpleBaseline: the pose kernel is HybridBaseline's assembly)
+
+
 class TrainStep:
+    _capturing_split = False          # True while the first of the split backward graphs is captured (PoseRoute stops after stage 0)
+
     def __init__(self, arch_model, criterion, optimizer, example_batch, use_graph=True, dist_group=None,
                  renderer=None, fused_criterion=True, pipeline_render=False):
         self.model = arch_model
@@ -60,9 +88,7 @@ class TrainStep:
         # ("__flat_*" are the loader's packed staging buffers; clones would not alias their typed views)
         self.static = {k: (v.to(self.dev).clone() if torch.is_tensor(v) else v) for k, v in example_batch.items()
                        if not k.startswith("__flat_")}
-        self.out = None
-        self.g_fwd_bwd = None
-        self.g_opt = None
+        self.out = self.g_fwd_bwd = self.g_opt = self.g_render = None
         self._fake_comm = os.environ.get("AB_FAKE_COMM") == "1"     # timing probe: the DDP stream choreography without RCCL
         # AB_DDP_SINGLE_RANK=1 with a process group of ONE rank: the whole multi-rank schedule (three backward graphs, bucketed
         # SUM all-reduces + 1 / world on the comm stream, post-all-reduce clip) with the real collective -- what a 1-GPU box can execute
@@ -70,14 +96,6 @@ class TrainStep:
         self.comm = self.world > 1 or (dist_group is not None and os.environ.get("AB_DDP_SINGLE_RANK") == "1")
         self.comm_stream = torch.cuda.Stream(device=self.dev) if (self.comm or self._fake_comm) else None
         self.steps = 0
-        # DDP overlap: the backward is captured as three graphs (heads + layer4 | layer3 | layer2 .. stem).  The first
-        # stage produces 68 % of the gradient bytes, the second 27 %; each range is all-reduced on the comm stream while
-        # the next stage computes, so only the last 5 MB are exposed.  AB_DDP_SPLIT=1 forces the split on one GPU
-        # (tests), =0 disables it.
-        env = os.environ.get("AB_DDP_SPLIT", "")
-        self.split = bool(use_graph and fused_criterion and (self.comm or env == "1") and env != "0")   # (cleared below
-        #                                                                                            if the criterion is not fusable)
-        self.g_bwd_rest = []
         # Render/learn pipelining (the reference overlaps them through DataLoader worker processes,
         # artiboost_loader.py:195-260): the batch for step i+1 is rendered on a side stream while step i trains.
         # `rstatic` holds the render inputs of the NEXT batch and its own image buffer; the image is handed over by one
@@ -86,14 +104,11 @@ class TrainStep:
         # run; it is written straight into the learn buffer, which step i no longer reads by then -- no second image, no
         # copy.  Measured on one MI355X: 9505 vs 9890 samples/s without it -- like the other two-stream variants (see
         # DESIGN.md section 5) concurrency across streams costs more here than it hides; opt-in only.
-        # HoNet built with ARCH.FUSED_MESH_STEP (below): its mesh queries are made from the render inputs of the batch being learned, which
-        # the pipelined modes hold one batch ahead -- the step renders and learns in order instead
-        self.mesh = bool(getattr(self.hb, "FUSED_MESH_STEP", False))
-        if self.mesh:
-            pipeline_render = False
-        self.pipeline_opt = bool(pipeline_render == "opt" and renderer is not None)
-        self.g_render = None
-        self.pipeline = bool(pipeline_render and not self.pipeline_opt and renderer is not None)
+        route = route_of(self.hb)                                    # the one place the model family is looked at
+        self.reg, self.mesh = route is RegRoute, route is MeshRoute
+        # None | "copy" (pipeline_render=True) | "opt", decided once; `pipeline` / `pipeline_opt` are its public spellings
+        self.render_mode = ("opt" if pipeline_render == "opt" else "copy") if pipeline_render and renderer is not None and route.pipelinable else None
+        self.pipeline, self.pipeline_opt = self.render_mode == "copy", self.render_mode == "opt"
         # the padded image's plane comes from the tag its loader wrote (registry.tag_image_plane / the batch's IMAGE_PLANE_KEY), carried over
         # to the static clone; HybridBaseline._plane_of refuses an untagged bfloat16 image on a bf16x3 model
         pad0 = self.static.get("image_nhwc4_padded") if isinstance(self.static, dict) else None
@@ -104,69 +119,37 @@ class TrainStep:
                 tag_image_plane(pad0, plane)
                 self.static[IMAGE_PLANE_KEY] = plane
             net0.image_plane = self._plane = self.hb._plane_of(self.static, pad0)
-        self.rstatic = None
-        self.render_stream = None
-        if self.pipeline_opt:
+        self.rstatic = self.render_stream = None
+        if self.render_mode:
             self.rstatic = {k: v.clone() for k, v in self.static.items() if torch.is_tensor(v) and k.startswith("_") and not k.startswith("__flat_")}
+            if self.render_mode == "copy":
+                self.rstatic["image_nhwc4_padded"] = torch.zeros_like(self.static["image_nhwc4_padded"])
             self.render_stream = torch.cuda.Stream(device=self.dev)
-        if self.pipeline:
-            self.rstatic = {k: v.clone() for k, v in self.static.items() if torch.is_tensor(v) and k.startswith("_") and not k.startswith("__flat_")}
-            self.rstatic["image_nhwc4_padded"] = torch.zeros_like(self.static["image_nhwc4_padded"])
-            self.render_stream = torch.cuda.Stream(device=self.dev)
-        self.fused = None
         self.mesh_queries = False
         # the key of this model's outputs in Arch's result dict: its config TYPE (the class name can differ: HOPRegNet on the HIP kernels)
         self.model_key = next((t for t, v in getattr(arch_model, "models", {}).items() if v["id"] == 0), type(self.hb).__name__)
-        # HOPRegNet built with ARCH.FUSED_STEP: its own fused criterion (ab_reg_pose_loss) and two linear graphs; the trunk-only layout has no
-        # staged backward, so with a process group the unsplit schedule applies (all-reduce between the two graphs)
-        self.reg = bool(getattr(self.hb, "FUSED_STEP", False))
-        if self.reg:
-            self.split = False
-            if fused_criterion:
-                from .criterions import FusedRegCriterion
-                try:
-                    self.fused = FusedRegCriterion(criterion, self.hb.ncomps, example_batch)
-                except NotImplementedError:   # a loss outside the kernel, or a hand_verts_3d target: the registry losses through autograd
-                    self.fused = None
-            if self.fused is None:
-                self.use_graph = False
-            fused_criterion = False
-        elif self.mesh:
-            # HoNet built with ARCH.FUSED_MESH_STEP: the fused mesh criterion (ab_honet_loss) on the recovery outputs and the same two linear
-            # graphs.  A loader with MANAGER.MESH_QUERIES writes the three mesh queries inside the captured region (one ab_mesh_queries
-            # launch after the render) into tensors allocated here, before the criterion looks at the batch and before any capture
-            self.split = False
-            if fused_criterion:
-                from .criterions import FusedMeshCriterion
-                if getattr(renderer, "mesh_queries", 0) and hasattr(renderer, "mesh_queries_into"):
-                    renderer.mesh_queries_into(self.static)
-                    self.mesh_queries = True
-                try:
-                    self.fused = FusedMeshCriterion(criterion, self.hb.ncomps, self.static)
-                except NotImplementedError:   # a loss outside the kernel: the registry losses through autograd, eagerly
-                    self.fused = None
-            if self.fused is None:
-                self.use_graph = False
-                self.mesh_queries = False     # (the eager loop calls loader.add_mesh_queries itself)
-            fused_criterion = False
-        elif not getattr(self.hb, "HAS_BOX_HEAD", True):             # SimpleBaseline: the fused pose/loss kernel is HybridBaseline's assembly
-            fused_criterion = False
-            self.split = False
-            self.use_graph = False
-        if fused_criterion:
-            from .criterions import FusedPoseCriterion
-            try:
-                self.fused = FusedPoseCriterion(criterion, self.hb.inp_res, self.hb.center_idx)
-            except NotImplementedError:       # a loss outside the fused kernel (e.g. SymCornerLoss): autograd criterion
-                self.fused = None
-                self.split = False
-                self.use_graph = False        # the registry losses index with host lists / move constants: not capturable
+        self.fused = route.criterion(self, example_batch) if fused_criterion else None
+        if self.fused is None:
+            # the registry losses index with host lists / move constants: not capturable.  Only a caller that turns HybridBaseline's fused
+            # criterion off itself (fused_criterion=False) is taken at its word on use_graph
+            self.use_graph = bool(use_graph and route is PoseRoute and not fused_criterion)
+            self.mesh_queries = False         # (the eager loop calls loader.add_mesh_queries itself)
+            route = PlainRoute
+        self.route = route
+        self._draws = self.fused if self.fused is not None else self.crit      # whose per-step host draws (the mesh criterion has none)
+        # DDP overlap: the backward is captured as three graphs (heads + layer4 | layer3 | layer2 .. stem).  The first
+        # stage produces 68 % of the gradient bytes, the second 27 %; each range is all-reduced on the comm stream while
+        # the next stage computes, so only the last 5 MB are exposed.  AB_DDP_SPLIT=1 forces the split on one GPU
+        # (tests), =0 disables it.
+        env = os.environ.get("AB_DDP_SPLIT", "")
+        self.split = bool(self.use_graph and route.splittable and (self.comm or env == "1") and env != "0")
+        self.g_bwd_rest = []
         if self.use_graph:
             self.opt.use_device_hyper(self.dev)
 
     # ------------------------------------------------------------------ pieces
     def _fwd_bwd(self):
-        if self.pipeline:
+        if self.render_mode == "copy":
             cur = torch.cuda.current_stream(self.dev)
             self.render_stream.wait_stream(cur)
             with torch.cuda.stream(self.render_stream):
@@ -175,20 +158,19 @@ class TrainStep:
             cur.wait_stream(self.render_stream)
             self.static["image_nhwc4_padded"].copy_(self.rstatic["image_nhwc4_padded"])
             return out
-        if self.renderer is not None and not self.pipeline_opt:
+        if self.renderer is not None and self.render_mode != "opt":
             self.renderer.render_into(self.static)
             if self.mesh_queries:
                 self.renderer.mesh_queries_into(self.static)
         return self._learn()
 
     def _launch_render_next(self):
-        """pipeline_opt: the learn graphs are enqueued -- once they have run the image buffer is free; start the render of
-        the next batch on the side stream (it overlaps the all-reduce and the optimizer graph)."""
-        if not self.pipeline_opt:
-            return
-        self.render_stream.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(self.render_stream):
-            self.g_render.replay()
+        """pipeline_opt: the learn work is enqueued -- once it has run the image buffer is free; start the render of the next
+        batch (its graph, or eagerly) on the side stream: it overlaps the all-reduce and the optimizer."""
+        if self.render_mode == "opt":
+            self.render_stream.wait_stream(torch.cuda.current_stream(self.dev))
+            with torch.cuda.stream(self.render_stream):
+                self.g_render.replay() if self.use_graph else self._render_next()
 
     def _render_next(self):
         """pipeline_opt: render the batch staged in `rstatic` into the learn image buffer."""
@@ -196,83 +178,18 @@ class TrainStep:
         self.renderer.render_into(self.rstatic)
 
     def _learn(self):
+        """One forward + backward on the static batch: the route's.  A fused one (autograd-free) runs on the trunk in training mode."""
         if self.fused is not None:
-            return self._fwd_bwd_fused()
-        preds = self.model(self.static)[self.model_key]
-        total, losses = self.crit.compute_losses(preds, self.static)
-        self.opt.zero_grad(set_to_none=True)
-        total.backward()
-        return preds, total, losses
-
-    def _fwd_bwd_fused(self):
-        """Autograd-free path: HIP forward -> fused soft-argmax -> fused pose+criterion(+backward) -> HIP backward."""
-        hb, net, st = self.hb, self.hb.net, self.static
-        net.training = True
-        if not net._packed:
-            net.pack_weights()
-        net.image_plane = getattr(self, "_plane", "f32") if st.get("image_nhwc4_padded") is not None else "f32"
-        if self.reg:
-            return self._fwd_bwd_reg()
-        if self.mesh:
-            return self._fwd_bwd_mesh()
-        logits, _ = net.forward(image=st.get(Queries.IMAGE), xpad=st.get("image_nhwc4_padded"))
-        kp3d, conf, stat = net.head_fwd(logits)
-        o = self.fused(kp3d, net.last["box_raw"], net.last["box_raw"].shape[-1], st)
-        dlogits = net.head_bwd(logits, kp3d, conf, stat, o["g_kp3d"])
-        net.backward(dlogits, o["g_box6d"], stage=0 if self._capturing_split else None)
-        hb.flat_param.grad = hb.store.grad
-        preds = dict(o, kp3d=kp3d, kp3d_confd=conf)
-        return preds, o["losses"], o
-
-    def _fwd_bwd_reg(self):
-        """HOPRegNet: trunk + heads + MANO -> fused regbased criterion (+backward) -> MANO / heads / trunk backward, no autograd."""
-        hb, st = self.hb, self.static
-        pose, shape, verts, joints, full, transf = hb._run(st.get(Queries.IMAGE), st.get("image_nhwc4_padded"), save=True)
-        o = self.fused(joints, pose, shape, transf, st)
-        hb._backward(o["g_pose"], o["g_shape"], None, o["g_joints"], None, o["g_transf"])
-        hb.flat_param.grad = hb.store.grad
-        bridge = {"hand_verts_3d": verts, "joints_3d": joints, "mano_shape": shape, "mano_pca_pose": pose, "mano_full_pose": full, "transf": transf}
-        return bridge, o["losses"], o
-
-    def _fwd_bwd_mesh(self):
-        """HoNet: trunk + heads + MANO + recovery -> fused mesh criterion (+backward) -> recovery / MANO / heads / trunk backward, no
-        autograd.  The recovery stage reads the static batch's own tensors (cam_intr, obj_verts_can, corners_can): fixed addresses."""
-        from .regnet import HONET_GEO
-        hb, st = self.hb, self.static
-        geo = hb._geo_of(st)
-        out = hb._run(st.get(Queries.IMAGE), st.get("image_nhwc4_padded"), True, geo)
-        rec = dict(zip(HONET_GEO, out[7:]))
-        o = self.fused(rec["joints_3d_abs"], rec["hand_verts_3d_abs"], rec["obj_verts_3d_abs"], rec["corners_3d_abs"], out[0], out[1], st)
-        # the five gradients; the TransHead rows (g_hst / g_ost) and the untouched recovery outputs get none
-        hb._backward(o["g_mano_pca_pose"], o["g_mano_shape"], None, None, None, None, None, *(o.get("g_" + k) for k in HONET_GEO))
-        hb.flat_param.grad = hb.store.grad
-        return out, o["losses"], o
-
-    def _draw(self):
-        """Per-step host draws of the losses into their device buffers (outside the graphs); the mesh criterion has none."""
-        (self.fused if self.mesh and self.fused is not None else self.crit).draw(self.dev)
-
-    _capturing_split = False
+            net, st = self.hb.net, self.static
+            net.training = True
+            if not net._packed:
+                net.pack_weights()
+            net.image_plane = getattr(self, "_plane", "f32") if st.get("image_nhwc4_padded") is not None else "f32"
+        return self.route.fwd_bwd(self)
 
     def predictions(self):
-        """The step's predictions under the NINE keys HybridBaseline.forward returns (hybridbaseline.py:86-96).  The fused path keeps
-        only what the criterion kernel writes; the root-relative and box-root entries the evaluator's PCK / visual metrics read are
-        derived here (a few small device ops, outside the graphs)."""
-        if self.fused is None:
-            return self.out[0]
-        if self.mesh:     # HoNet's dict from the bridge outputs, as HoNetHIP.forward assembles it
-            return self.hb._assemble(self.out[0])
-        if self.reg:      # HOPRegNet's 18 keys from the bridge outputs (the camera projections stay torch ops, as in its forward)
-            from .hpregnet import combine_outputs, mano_outputs, object_outputs
-            mano = {k: v for k, v in self.out[0].items() if k != "transf"}
-            return combine_outputs(mano_outputs(mano, self.static, self.dev), object_outputs(self.out[0]["transf"], self.static, self.dev))
-        o, st = self.fused.out, self.static
-        ja, ca, R = o["joints_3d_abs"], o["corners_3d_abs"], o["box_rot_rotmat"]
-        root = ja[:, self.hb.center_idx:self.hb.center_idx + 1]
-        can = st[Queries.CORNERS_CAN].to(ca.dtype)
-        boxroot = (ca - torch.matmul(R, can.permute(0, 2, 1)).permute(0, 2, 1)).mean(1, keepdim=True)
-        return {"joints_3d_abs": ja, "corners_3d_abs": ca, "joints_3d": ja - root, "corners_3d": ca - root, "2d_uvd": o["uvd2d"],
-                "boxroot_3d_abs": boxroot, "box_rot_rotmat": R, "kp3d": self.out[0]["kp3d"], "kp3d_confd": self.out[0]["kp3d_confd"]}
+        """The step's predictions under the keys the model's forward returns."""
+        return self.route.predictions(self)
 
     def _optim(self):
         self.opt.step()
@@ -301,20 +218,16 @@ class TrainStep:
     def _snapshot(self):
         """Everything the capture warm-up step modifies: weights, BatchNorm running statistics, Adam moments and step counts,
         and the host RNG streams the loss draws consume."""
-        import random
-        import numpy as np
         store = self.hb.store
         snap = dict(flat=store.flat.detach().clone(), stats=store.stats.clone(), nbt=store.num_batches_tracked,
                     graph_steps=self.opt.graph_steps, rng=(random.getstate(), np.random.get_state(), torch.get_rng_state()), opt={})
         for p, st in self.opt.state.items():
             snap["opt"][p] = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in st.items()}
-        if self.pipeline:       # the pipelined warm-up ends by handing the NEXT batch's image to the learn buffer: undo that too
+        if self.render_mode == "copy":       # the pipelined warm-up ends by handing the NEXT batch's image to the learn buffer: undo that too
             snap["image"] = self.static["image_nhwc4_padded"].clone()
         return snap
 
     def _restore(self, snap):
-        import random
-        import numpy as np
         store = self.hb.store
         with torch.no_grad():
             store.flat.copy_(snap["flat"])
@@ -339,7 +252,7 @@ class TrainStep:
         # afterwards, so a graph-replayed run is the same sequence of updates as the eager one, bit for bit, and a
         # checkpoint can be loaded before the first step.
         snap = self._snapshot()
-        self._draw()
+        self._draws.draw(self.dev)
         self.opt.advance_hyper()
         self.opt.graph_steps = 0
         torch.cuda.synchronize(self.dev)
@@ -373,7 +286,7 @@ class TrainStep:
         self.g_opt = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_opt, pool=self.g_fwd_bwd.pool(), capture_error_mode=CAPTURE_MODE):
             self._optim()
-        if self.pipeline_opt:
+        if self.render_mode == "opt":
             self.g_render = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.g_render, pool=self.g_fwd_bwd.pool(), capture_error_mode=CAPTURE_MODE):
                 self._render_next()
@@ -383,7 +296,7 @@ class TrainStep:
     def stage(self, loader, batch_idx):
         """Gather the inputs of step `batch_idx` from the loader's planned epoch: ground truth of this batch and, when
         pipelined, the render inputs of the next one (whose image this step produces)."""
-        if not (self.pipeline or self.pipeline_opt):
+        if not self.render_mode:
             loader.load_batch(self.static, batch_idx)
             return
         loader.load_batch(self.static, batch_idx, which="gt")
@@ -391,13 +304,12 @@ class TrainStep:
 
     def prime(self, loader, batch_idx):
         """Pipelined mode: render batch `batch_idx` eagerly so that the first step has an image to learn from."""
-        if self.pipeline_opt:
-            loader.load_batch(self.rstatic, batch_idx, which="render")
-            self._render_next()
-            return
-        if not self.pipeline:
+        if not self.render_mode:
             return
         loader.load_batch(self.rstatic, batch_idx, which="render")
+        if self.render_mode == "opt":
+            self._render_next()
+            return
         self.renderer.render_into(self.rstatic)
         self.static["image_nhwc4_padded"].copy_(self.rstatic["image_nhwc4_padded"])
 
@@ -412,22 +324,16 @@ class TrainStep:
             self.load_batch(batch)
         if not self.use_graph:
             if self.fused is not None:
-                self._draw()
+                self.fused.draw(self.dev)
             self.out = self._fwd_bwd()
-            if self.pipeline_opt:
-                cur = torch.cuda.current_stream(self.dev)
-                self.render_stream.wait_stream(cur)
-                with torch.cuda.stream(self.render_stream):
-                    self._render_next()
+            self._launch_render_next()
             if self.comm:
                 self._allreduce()
             self._optim()
-            if self.pipeline_opt:
-                torch.cuda.current_stream(self.dev).wait_stream(self.render_stream)
         else:
             if self.g_fwd_bwd is None:
                 self._capture()
-            self._draw()
+            self._draws.draw(self.dev)
             self.opt.advance_hyper()
             self.g_fwd_bwd.replay()
             self.hb.store.num_batches_tracked += 1           # the replayed forward is a training-mode BatchNorm forward
@@ -448,8 +354,8 @@ class TrainStep:
                 if self.comm:
                     self._allreduce()
             self.g_opt.replay()
-            if self.pipeline_opt:
-                torch.cuda.current_stream(self.dev).wait_stream(self.render_stream)
+        if self.render_mode == "opt":
+            torch.cuda.current_stream(self.dev).wait_stream(self.render_stream)
         self.steps += 1
         return self.out
 
@@ -469,7 +375,7 @@ class DeferredEpochMetrics:
         self.direct = [m for m in (evaluator.metrics_list if evaluator is not None else []) if not self._deferrable(m)]
         B, dev = ts.static[Queries.ROOT_JOINT].shape[0], ts.dev
         self.epe = torch.zeros((capacity, B, 2), dtype=torch.float32, device=dev)         # (joints, corners) mm
-        self.losses = torch.zeros((capacity, getattr(ts.fused, "LOSS_WIDTH", 8)), dtype=torch.float32, device=dev)     # the criterion's loss vector
+        self.losses = torch.zeros((capacity, ts.fused.LOSS_WIDTH), dtype=torch.float32, device=dev)     # the criterion's loss vector
         self.ids = torch.zeros((capacity, B, 4), dtype=torch.int64, device=dev)           # obj, persp, grasp, is_synth
 
     @staticmethod
