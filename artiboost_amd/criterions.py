@@ -743,11 +743,44 @@ class FusedMeshCriterion(_FusedCriterion):
 
 
 # ---- mesh-level losses --------------------------------------------------------------------------------------------
-def _refuse_device(name, dev):
-    """No HIP kernel backs these two losses yet, and eager device torch ops are not a route of this build (a brute-force [N,M] distance
-    matrix per sample; a batched 3x3 torch.svd with a host synchronisation per step): a HIP tensor is an error, not a silent fallback."""
-    if dev.type == "cuda":
-        raise RuntimeError(f"{name} has no HIP kernel in this build: it runs on CPU tensors only (DESIGN.md section 19)")
+class _ChamferRigidFn(torch.autograd.Function):
+    """ab_chamfer_rigid (csrc/mesh_align.hip): ONE call in forward leaves the loss and its gradient with respect to the rotation entries and
+    the translation; backward scales the kept buffers by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, rot, tsl, can, targ, root, corners_vis):
+        from . import kernels as K
+        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        o = K.chamfer_rigid(can, rot, tsl, targ, root, corners_vis, want_grad=want)
+        ctx.shapes = (rot.shape, tsl.shape)
+        if want:
+            ctx.save_for_backward(o["g_rot"], o["g_tsl"])
+        return o["loss"].reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        g_rot, g_tsl = ctx.saved_tensors
+        return (g_rot * g).reshape(ctx.shapes[0]), (g_tsl * g).reshape(ctx.shapes[1]), None, None, None, None
+
+
+class _ProcrustesLossFn(torch.autograd.Function):
+    """ab_procrustes_loss (csrc/mesh_align.hip): ONE call in forward leaves the loss and its gradient with respect to the predicted joints."""
+
+    @staticmethod
+    def forward(ctx, pred, targ, root):
+        from . import kernels as K
+        o = K.procrustes_loss(pred, targ, root, want_grad=ctx.needs_input_grad[0])
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(o["g_pred"])
+        return o["loss"].reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.saved_tensors[0] * g, None, None
+
+
+def _dev_f32(t, dev):
+    return t.to(device=dev, dtype=torch.float32).contiguous()
 
 
 def chamfer_distance_torch(x, y):
@@ -768,7 +801,8 @@ def chamfer_distance_torch(x, y):
 class ChamferLoss(TensorLoss):
     """anakin/criterions/chamferloss.py:11-52.  The predicted cloud is R_pred can + boxroot, the target obj_verts_3d + root_joint (the
     reference's padded [B,N,3] batch, datasets.ho_collate); both are multiplied by any(corners_vis) and compared by the two-way squared
-    nearest-neighbour distance.  Torch ops over chamfer_distance_torch, CPU tensors only."""
+    nearest-neighbour distance.  CPU tensors: torch ops over chamfer_distance_torch.  HIP tensors: ab_chamfer_rigid (csrc/mesh_align.hip),
+    loss and rigid gradient in one call; the eager route only (TrainStep refuses to capture a step that holds this loss)."""
 
     def __init__(self, **cfg):
         super().__init__()
@@ -779,25 +813,35 @@ class ChamferLoss(TensorLoss):
         chamfer_loss = None
         if self.lambda_chamfer:
             dev = final_loss.device
-            _refuse_device("ChamferLoss", dev)
             rot, tsl = preds["box_rot_rotmat"], preds["boxroot_3d_abs"]
-            keep = torch.any(targs[Queries.CORNERS_VIS].to(dev) != 0, dim=1).to(rot.dtype)
-            can = targs[Queries.OBJ_VERTS_CAN].to(dev)
-            v3d, root = targs[Queries.OBJ_VERTS_3D].to(dev), targs[Queries.ROOT_JOINT].to(dev)
-            pred = torch.matmul(rot, can.permute(0, 2, 1)).permute(0, 2, 1) + tsl
-            pred = torch.einsum("bij,b->bij", pred, keep)
-            targ = torch.einsum("bij,b->bij", v3d + root.unsqueeze(1), keep)
-            dist_xy, dist_yx, _, _ = chamfer_distance_torch(pred, targ)
-            chamfer_loss = torch.mean(dist_xy) + torch.mean(dist_yx)
+            if dev.type == "cuda":      # one ab_chamfer_rigid call; the mask is formed in the kernel (eager only)
+                t = lambda k: _dev_f32(targs[k], dev)   # noqa: E731
+                chamfer_loss = _ChamferRigidFn.apply(_dev_f32(rot, dev), _dev_f32(tsl, dev), t(Queries.OBJ_VERTS_CAN), t(Queries.OBJ_VERTS_3D),
+                                                     t(Queries.ROOT_JOINT), t(Queries.CORNERS_VIS))
+            else:
+                chamfer_loss = self.torch_expression(rot, tsl, targs, dev)
             final_loss = final_loss + self.lambda_chamfer * chamfer_loss
         losses["chamfer_loss"] = chamfer_loss
         losses[self.output_key] = final_loss
         return final_loss, losses
 
+    @staticmethod
+    def torch_expression(rot, tsl, targs, dev):
+        """The route of CPU tensors: the reference's torch ops (tools/bench_mesh_losses.py times the same expression on device tensors)."""
+        keep = torch.any(targs[Queries.CORNERS_VIS].to(dev) != 0, dim=1).to(rot.dtype)
+        can = targs[Queries.OBJ_VERTS_CAN].to(dev)
+        v3d, root = targs[Queries.OBJ_VERTS_3D].to(dev), targs[Queries.ROOT_JOINT].to(dev)
+        pred = torch.matmul(rot, can.permute(0, 2, 1)).permute(0, 2, 1) + tsl
+        pred = torch.einsum("bij,b->bij", pred, keep)
+        targ = torch.einsum("bij,b->bij", v3d + root.unsqueeze(1), keep)
+        dist_xy, dist_yx, _, _ = chamfer_distance_torch(pred, targ)
+        return torch.mean(dist_xy) + torch.mean(dist_yx)
+
 
 @LOSS.register_module
 class AlignLoss(TensorLoss):
-    """anakin/criterions/alignloss.py:12-80: the reference's torch ops (batched torch.svd under autograd), CPU tensors only."""
+    """anakin/criterions/alignloss.py:12-80.  CPU tensors: the reference's torch ops (batched torch.svd under autograd).  HIP tensors:
+    ab_procrustes_loss (csrc/mesh_align.hip), one wave per sample, analytic backward; the eager route only, as for ChamferLoss."""
 
     def __init__(self, **cfg):
         super().__init__()
@@ -810,9 +854,11 @@ class AlignLoss(TensorLoss):
         pred = preds["joints_3d_abs"]
         loss = None
         if self.lambda_procrustes_align:
-            _refuse_device("AlignLoss", dev)
-            xyz = (targs[Queries.JOINTS_3D] + targs[Queries.ROOT_JOINT].unsqueeze(1)).to(dev)
-            loss = F.mse_loss(self.procrustes_align(xyz, pred), xyz)
+            if dev.type == "cuda":      # one ab_procrustes_loss call, analytic backward (eager only)
+                loss = _ProcrustesLossFn.apply(_dev_f32(pred, dev), _dev_f32(targs[Queries.JOINTS_3D], dev), _dev_f32(targs[Queries.ROOT_JOINT], dev))
+            else:
+                xyz = (targs[Queries.JOINTS_3D] + targs[Queries.ROOT_JOINT].unsqueeze(1)).to(dev)
+                loss = F.mse_loss(self.procrustes_align(xyz, pred), xyz)
             final_loss = final_loss + self.lambda_procrustes_align * loss
         losses["procrustes_aligned_loss"] = loss
         if self.lambda_st_align:

@@ -1026,6 +1026,50 @@ def mssd(can, obj_transf, obj_idx, sym_R, sym_t, sym_count, pred_R=None, pred_t=
     return out
 
 
+def _f32_of(op, what, t, numel):
+    if t.dtype != torch.float32 or t.numel() != numel:
+        raise ValueError(f"{op}: {what} must be fp32 with {numel} elements, got {t.dtype} {tuple(t.shape)}")
+    return L.ptr(t)
+
+
+def chamfer_rigid(can, rot, tsl, targ, root, corners_vis, want_grad=True, want_dist=False):
+    """ab_chamfer_rigid (eager only, never under graph capture): the two-way squared nearest-neighbour distance between keep (R can + t) and
+    keep (targ + root), keep = any(corners_vis != 0) formed in the kernel.  can [B,N,3], rot [B,3,3] / [B,9], tsl [B,(1,)3], targ [B,M,3],
+    root [B,3], corners_vis [B,8], all fp32.  -> dict: loss [1]; with want_grad g_rot [B,3,3] and g_tsl [B,3] (the gradient of loss);
+    with want_dist dist_xy [B,N], dist_yx [B,M] and the int32 indices idx_xy, idx_yx."""
+    B, N, M = can.shape[0], can.shape[1], targ.shape[1]
+    ins = [_f32_of("chamfer_rigid", w, t, n) for w, t, n in (("can", can, B * N * 3), ("rot", rot, B * 9), ("tsl", tsl, B * 3), ("targ", targ, B * M * 3),
+                                                            ("root", root, B * 3), ("corners_vis", corners_vis, B * 8))]
+    dev = can.device
+    o = {"loss": torch.empty((1,), dtype=torch.float32, device=dev)}
+    if want_grad:
+        o["g_rot"], o["g_tsl"] = torch.empty((B, 3, 3), dtype=torch.float32, device=dev), torch.empty((B, 3), dtype=torch.float32, device=dev)
+    if want_dist:
+        o["dist_xy"], o["dist_yx"] = torch.empty((B, N), dtype=torch.float32, device=dev), torch.empty((B, M), dtype=torch.float32, device=dev)
+        o["idx_xy"], o["idx_yx"] = torch.empty((B, N), dtype=torch.int32, device=dev), torch.empty((B, M), dtype=torch.int32, device=dev)
+    ws = _workspace(L.lib().ab_chamfer_rigid_workspace(L.i(B), L.i(N), L.i(M)), dev)
+    L.check(L.lib().ab_chamfer_rigid(*ins, L.i(B), L.i(N), L.i(M), o["loss"], o.get("dist_xy"), o.get("dist_yx"), o.get("idx_xy"), o.get("idx_yx"),
+                                     o.get("g_rot"), o.get("g_tsl"), L.ptr(ws), L.stream()), "ab_chamfer_rigid")
+    return o
+
+
+def procrustes_loss(pred, targ, root, want_grad=True, want_aligned=False):
+    """ab_procrustes_loss (eager only, never under graph capture): the MSE between targ + root and pred aligned to it by the optimal
+    similarity (rotation or reflection, scale, translation).  pred, targ [B,n,3], root [B,3], fp32, n >= 3.  -> dict: loss [1],
+    sample_loss [B]; with want_grad g_pred [B,n,3] (the gradient of loss); with want_aligned aligned [B,n,3]."""
+    B, n = pred.shape[0], pred.shape[1]
+    ins = [_f32_of("procrustes_loss", w, t, k) for w, t, k in (("pred", pred, B * n * 3), ("targ", targ, B * n * 3), ("root", root, B * 3))]
+    dev = pred.device
+    o = {"loss": torch.empty((1,), dtype=torch.float32, device=dev), "sample_loss": torch.empty((B,), dtype=torch.float32, device=dev)}
+    if want_grad:
+        o["g_pred"] = torch.empty((B, n, 3), dtype=torch.float32, device=dev)
+    if want_aligned:
+        o["aligned"] = torch.empty((B, n, 3), dtype=torch.float32, device=dev)
+    L.check(L.lib().ab_procrustes_loss(*ins, L.i(B), L.i(n), o["sample_loss"], o["loss"], o.get("aligned"), o.get("g_pred"), L.stream()),
+            "ab_procrustes_loss")
+    return o
+
+
 FIT_NP = 59             # parameters per hand of ab_mano_fit: so3 48 | beta 10 | bone 1
 
 

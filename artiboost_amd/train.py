@@ -248,6 +248,11 @@ class TrainStep:
         torch.cuda.synchronize(self.dev)
 
     def _capture(self):
+        # ab_chamfer_rigid / ab_procrustes_loss are never captured: refused before anything of the device is touched
+        from .criterions import AlignLoss, ChamferLoss
+        if any(isinstance(l, (ChamferLoss, AlignLoss)) for l in self.crit.loss_list):
+            raise NotImplementedError("ChamferLoss / AlignLoss run on the eager route only: a step that holds either is not captured in a "
+                                      "hipGraph (DESIGN.md section 19); build the TrainStep with use_graph=False")
         # The capture needs one real step first (allocator warm-up, lazily created optimizer state).  Its effects are undone
         # afterwards, so a graph-replayed run is the same sequence of updates as the eager one, bit for bit, and a
         # checkpoint can be loaded before the first step.

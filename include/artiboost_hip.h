@@ -718,6 +718,43 @@ int ab_mssd(const float* can, const float* obj_transf, const int64_t* obj_idx, c
             const int32_t* sym_count, int n_obj, int Kmax, const float* pred_R, const float* pred_t, const float* pred_pts,
             const float* center, int B, int V, float* mssd, void* workspace, void* stream);
 
+/* ---- Mesh-level registry losses, eager route only (csrc/mesh_align.hip) --------------------------------------------
+ * ab_chamfer_rigid: anakin/criterions/chamferloss.py:11-52 over the brute-force nearest neighbour of criterions.chamfer_distance_torch.
+ * can [B,N,3], rot [B,9] row-major (box_rot_rotmat), tsl [B,3] (boxroot_3d_abs), targ [B,M,3] (obj_verts_3d), root [B,3] (root_joint, added
+ * to targ), corners_vis [B,8] fp32: keep = any(corners_vis != 0) is formed in the kernel.  Per sample
+ *   x_i = keep (R can_i + t),  y_j = keep (targ_j + root),  dist_xy[i] = min_j |x_i - y_j|^2,  dist_yx[j] = min_i |x_i - y_j|^2
+ * as sums of squared differences (never |x|^2 + |y|^2 - 2 x.y: that form cancels at 0.5 m depth and millimetre distances); the first
+ * minimum wins on ties, as in argmin and ab_nearest_dist.
+ *   loss[1] = sum dist_xy / (B N) + sum dist_yx / (B M)
+ * dist_xy [B,N], dist_yx [B,M], idx_xy int32 [B,N] (into y), idx_yx int32 [B,M] (into x): each optional (NULL).  g_rot [B,9] and g_tsl [B,3]
+ * (both or neither): the gradient of loss, the nine rotation entries free variables as autograd treats them,
+ *   g_i = (2 / (B N)) (x_i - y_i*) + sum over j with j* = i of (2 / (B M)) (x_i - y_j),   g_tsl = keep sum g_i,   g_rot = keep sum g_i can_i^T,
+ * each target's term folded straight into the two sums: no [B,N,3] and no [N,M] is materialised.  A masked sample (keep = 0) writes zero
+ * distances, zero indices and zero gradients without scanning and still counts in both means (the reference's behaviour, kept on purpose).
+ * Meshes padded by repetition hold exact duplicates; which duplicate wins a tie does not change g_rot or g_tsl: duplicates share can_i.
+ * workspace: ab_chamfer_rigid_workspace(B, N, M) bytes (16 floats per sample and chunk of 256 query points of either cloud).  No atomics:
+ * partial sums are added in a fixed order by a second small launch, so two calls give the same bits, and a sample's distances, indices
+ * and B-fold gradients (B a power of two) do not depend on the batch around it.  1 <= B <= 65535, N, M >= 1.
+ *
+ * ab_procrustes_loss: anakin/criterions/alignloss.py:52-80 plus the MSE; one wave per sample, one launch for the batch and a small one for
+ * the mean.  pred [B,n,3] (joints_3d_abs), targ [B,n,3] (joints_3d), root [B,3] (added to targ), n >= 3 (the model: 21).  With Xh, Ph the
+ * centred clouds over (their Frobenius norm + 1e-8), c the target's norm term, M = Xh^T Ph = u w v^T, R = u v^T (NO determinant correction:
+ * a mirrored hand aligns by a reflection, as in the reference) and s = sum w:
+ *   aligned [B,n,3] (optional) = s c R Ph_i + centroid(targ + root);   sample_loss [B] = c^2 sum_i |s R Ph_i - Xh_i|^2 / (3 n), computed from
+ *   the residual (1 - s^2 loses its digits for a near-perfect prediction);   loss[1] = mean of sample_loss, summed in a fixed order;
+ *   g_pred [B,n,3] (optional) = d loss / d pred: R is the optimum, so d loss / d M = -2 c^2 s R / (3 n B) without an SVD backward, then
+ *   through Ph = Pc / p and the centring.
+ * A rank-deficient M (coplanar or collinear joints) gives finite numbers everywhere; the gradient there is unspecified (the reference's
+ * torch.svd backward is not finite there either).  Deterministic; sample_loss, aligned and B-fold g_pred (B a power of two) do not depend
+ * on the batch around the sample.  B >= 1, 3 <= n <= 2^24.
+ * Neither entry point is captured in a hipGraph anywhere in this project: TrainStep refuses such a step.          */
+long ab_chamfer_rigid_workspace(int B, int N, int M);
+int ab_chamfer_rigid(const float* can, const float* rot, const float* tsl, const float* targ, const float* root, const float* corners_vis,
+                     int B, int N, int M, float* loss, float* dist_xy, float* dist_yx, int32_t* idx_xy, int32_t* idx_yx, float* g_rot,
+                     float* g_tsl, void* workspace, void* stream);
+int ab_procrustes_loss(const float* pred, const float* targ, const float* root, int B, int n, float* sample_loss, float* loss,
+                       float* aligned, float* g_pred, void* stream);
+
 /* ---- Argument contracts of the dispatcher ops (torch.ops.artiboost_hip.*, libartiboost_torch.so) ------------------------------------------
  * The C entry points above take raw pointers and trust their caller.  Their PyTorch-dispatcher form (ops that "validate
  * with TORCH_CHECK") is generated from this header by artiboost_amd/gen_torch_ops.py and checks, before the C call, for EVERY op:
@@ -791,6 +828,8 @@ int ab_mssd(const float* can, const float* obj_transf, const int64_t* obj_idx, c
  * @check ab_mano_fit: quat >= B*64; pred_joints >= B*63; v_template >= 778*3; shapedirs >= 778*3*10; posedirs >= 778*3*135; J_regressor >= 16*778; weights >= 778*16; J_template >= 48; J_shapedirs >= 480; params adam_m adam_v grad >= B*59; verts >= B*778*3; joints >= B*63; loss >= B*n_iter
  * @check ab_draw_meshes: hand_verts >= B*778*3; hand_faces >= nhf*3; adj_off >= 779; adj_face >= nadj; obj_verts obj_normals >= nov*3; obj_faces >= nof*3; obj_vert_off obj_face_off >= n_obj+1; obj_id >= B; obj_rot >= B*9; obj_tsl >= B*3; corners >= B*24; cam_intr >= B*9; image >= B*3*H*W; out >= B*H*4*W*3; bytes workspace >= ab_draw_workspace_bytes(B,W,H,max_obj_verts)
  * @check ab_mssd: can pred_pts >= B*V*3; obj_transf >= B*16; obj_idx mssd >= B; sym_R >= n_obj*Kmax*9; sym_t >= n_obj*Kmax*3; sym_count >= n_obj; pred_R >= B*9; pred_t center >= B*3; bytes workspace >= ab_mssd_workspace(B,Kmax,V)
+ * @check ab_chamfer_rigid: can >= B*N*3; rot g_rot >= B*9; tsl root g_tsl >= B*3; targ >= B*M*3; corners_vis >= B*8; loss >= 1; dist_xy idx_xy >= B*N; dist_yx idx_yx >= B*M; bytes workspace >= ab_chamfer_rigid_workspace(B,N,M)
+ * @check ab_procrustes_loss: pred targ aligned g_pred >= B*n*3; root >= B*3; sample_loss >= B; loss >= 1
  */
 
 #ifdef __cplusplus
