@@ -1070,6 +1070,32 @@ def procrustes_loss(pred, targ, root, want_grad=True, want_aligned=False):
     return o
 
 
+MM_PAIRED, MM_PROCRUSTES, MM_NN = 1, 2, 4      # AB_MM_* flags of ab_mesh_metrics
+MM_ROW = {"epe": 0, "ra_epe": 1, "pa_epe": 2, "scale": 3, "mean_pg": 4, "mean_gp": 5, "pa_mean_pg": 6, "pa_mean_gp": 7, "f": 8, "pa_f": 12}
+MM_MAX_THRESHOLDS = 4
+
+
+def mesh_metrics(pred, targ, root=None, center_idx=-1, thresholds=(), flags=MM_PAIRED | MM_PROCRUSTES | MM_NN, want_dist=False):
+    """ab_mesh_metrics (eager only, never under graph capture): per-sample paired / Procrustes-aligned errors and the two-way
+    nearest-neighbour distances, means (mean_gp is ADD-S) and F-score counts of pred [B,N,3] against targ [B,M,3] + root [B,3] (None:
+    zero), all fp32.  thresholds: up to 4 distances in metres (host numbers).  flags: MM_PAIRED | MM_PROCRUSTES | MM_NN; the first two
+    need N == M.  -> dict: rows [B,16] (columns MM_ROW; NaN where a group was not asked for), counts int32 [B,T,4] (pg, gp, pa_pg, pa_gp);
+    want_dist: True for all of d_pg [B,N], d_gp [B,M], pa_d_pg, pa_d_gp, or the names wanted."""
+    B, N, M = pred.shape[0], pred.shape[1], targ.shape[1]
+    ins = [_f32_of("mesh_metrics", "pred", pred, B * N * 3), _f32_of("mesh_metrics", "targ", targ, B * M * 3),
+           None if root is None else _f32_of("mesh_metrics", "root", root, B * 3)]
+    thr = torch.tensor([float(t) for t in thresholds], dtype=torch.float32)
+    T, dev = thr.numel(), pred.device
+    o = {"rows": torch.empty((B, 16), dtype=torch.float32, device=dev), "counts": torch.empty((B, T, 4), dtype=torch.int32, device=dev)}
+    names = ("d_pg", "d_gp", "pa_d_pg", "pa_d_gp") if want_dist is True else tuple(want_dist or ())
+    for k in names:
+        o[k] = torch.empty((B, N if k.endswith("pg") else M), dtype=torch.float32, device=dev)
+    ws = _workspace(L.lib().ab_mesh_metrics_workspace(L.i(B), L.i(N), L.i(M)), dev)
+    L.check(L.lib().ab_mesh_metrics(*ins, L.i(B), L.i(N), L.i(M), L.i(center_idx), thr, L.i(T), L.i(flags), o["rows"], o["counts"], o.get("d_pg"),
+                                    o.get("d_gp"), o.get("pa_d_pg"), o.get("pa_d_gp"), L.ptr(ws), L.stream()), "ab_mesh_metrics")
+    return o
+
+
 FIT_NP = 59             # parameters per hand of ab_mano_fit: so3 48 | beta 10 | bone 1
 
 

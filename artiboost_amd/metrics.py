@@ -248,7 +248,7 @@ class Evaluator:
                 m.feed(preds, targs, losses=losses) if isinstance(m, LossesMetric) else m.feed(preds, targs)
                 continue
             tensors, extra = res if isinstance(res, tuple) else (res, None)
-            if not all(torch.is_tensor(t) and t.is_cuda for t in tensors):      # host tensors / numbers: nothing to wait for
+            if not tensors or not all(torch.is_tensor(t) and t.is_cuda for t in tensors):      # host tensors / numbers / nothing: nothing to wait for
                 m.feed_host([t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in tensors], extra=extra)
                 continue
             lay = []
@@ -648,3 +648,209 @@ class ValMetricAR2(Metric):
 
     def __str__(self):
         return ""
+
+
+# ============================================================================ leaderboard mesh metrics
+MESH_F_THRESHOLDS_MM = (5.0, 15.0)       # the thresholds HO3D / FreiHAND publish F-scores at
+
+
+def mesh_values_torch(pred, targ, root=None, center_idx=-1, thresholds=(), flags=7, want_dist=False):
+    """The definitions of ab_mesh_metrics (include/artiboost_hip.h) as torch ops, in the tensors' dtype: the route of CPU tensors, and what
+    tools/bench_mesh_metrics.py times on device tensors.  Same arguments and the same dict as kernels.mesh_metrics: rows [B,16] (columns
+    kernels.MM_ROW, NaN where a group was not asked for), counts int32 [B,T,4] and, with want_dist, the four per-point distance arrays.
+    The nearest-neighbour scan is one [N,M] matrix of squared direct differences per sample (not torch.cdist: on the HIP build this project
+    runs on, its batched no-matmul form returned distances 0.2 m off for every sample but the first at B = 64, N = M = 778; DESIGN.md
+    section 23)."""
+    from .kernels import MM_NN, MM_PAIRED, MM_PROCRUSTES, MM_ROW as C
+    P = pred.detach()
+    G = targ.to(P.device) if root is None else targ.to(P.device) + root.to(P.device).unsqueeze(1)
+    B, N, M, T = P.shape[0], P.shape[1], G.shape[1], len(thresholds)
+    if flags & (MM_PAIRED | MM_PROCRUSTES) and N != M:
+        raise ValueError(f"mesh_values_torch: paired and aligned errors need N == M, got {N} and {M}")
+    if flags & MM_PROCRUSTES and N < 3:
+        raise ValueError("mesh_values_torch: the alignment needs N >= 3")
+    rows = torch.full((B, 16), float("nan"), dtype=P.dtype, device=P.device)
+    counts = torch.zeros((B, T, 4), dtype=torch.int32, device=P.device)
+    out = {"rows": rows, "counts": counts}
+    if flags & MM_PAIRED:
+        rows[:, C["epe"]] = torch.norm(P - G, dim=2).mean(1)
+        if center_idx >= 0:
+            c = slice(center_idx, center_idx + 1)
+            rows[:, C["ra_epe"]] = torch.norm((P - P[:, c]) - (G - G[:, c]), dim=2).mean(1)
+    Pa = None
+    if flags & MM_PROCRUSTES:         # AlignLoss.procrustes_align, keeping the scale: R = u v^T of Gh^T Ph, no determinant correction
+        mg, mp = G.mean(1, keepdim=True), P.mean(1, keepdim=True)
+        c = torch.norm(G - mg, dim=(1, 2), keepdim=True) + 1e-8
+        p = torch.norm(P - mp, dim=(1, 2), keepdim=True) + 1e-8
+        Ph = (P - mp) / p
+        u, w, vh = torch.linalg.svd(((G - mg) / c).transpose(1, 2) @ Ph)
+        s = w.sum(1).reshape(B, 1, 1)
+        Pa = (Ph @ (u @ vh).transpose(1, 2)) * (s * c) + mg
+        rows[:, C["pa_epe"]] = torch.norm(Pa - G, dim=2).mean(1)
+        rows[:, C["scale"]] = (s * c / p).reshape(B)
+    if flags & MM_NN:
+        thr = torch.as_tensor([float(t) for t in thresholds], dtype=P.dtype, device=P.device)
+        for k, (Q, pre) in enumerate(((P, ""), (Pa, "pa_"))):
+            if Q is None:
+                continue
+            d_pg, d_gp = [], []
+            for qb, gb in zip(Q, G):      # one sample at a time, as criterions.chamfer_distance_torch: one [N,M] matrix of direct differences
+                d2 = ((qb[:, None, :] - gb[None, :, :]) ** 2).sum(-1)
+                d_pg.append(d2.min(1)[0]); d_gp.append(d2.min(0)[0])
+            d_pg, d_gp = torch.stack(d_pg).sqrt(), torch.stack(d_gp).sqrt()
+            rows[:, C[pre + "mean_pg"]], rows[:, C[pre + "mean_gp"]] = d_pg.mean(1), d_gp.mean(1)
+            if T:
+                n_pg, n_gp = (d_pg.unsqueeze(1) < thr[None, :, None]).sum(2), (d_gp.unsqueeze(1) < thr[None, :, None]).sum(2)   # [B,T], strict <
+                counts[:, :, 2 * k], counts[:, :, 2 * k + 1] = n_pg.to(torch.int32), n_gp.to(torch.int32)
+                pr, rc = n_pg.to(P.dtype) / N, n_gp.to(P.dtype) / M
+                rows[:, C[pre + "f"]:C[pre + "f"] + T] = torch.where(pr + rc > 0, 2 * pr * rc / (pr + rc).clamp_min(1e-30), torch.zeros_like(pr))
+            if want_dist:
+                out[pre + "d_pg"], out[pre + "d_gp"] = d_pg, d_gp
+    return out
+
+
+def _mesh_values(preds, targs, key, memo=None, center_idx=-1, thresholds=None):
+    """rows / counts (the dict of kernels.mesh_metrics) of `key`, or None when the batch lacks the prediction or its target.  ONE call per
+    key per feed_all: every mesh metric asks for the same thing -- all the groups the shapes allow (N == M >= 3: paired, aligned and
+    nearest-neighbour; otherwise nearest-neighbour only), the centre on 21-joint arrays only, thresholds None = the published 5 / 15 mm --
+    so the `memo` of Evaluator.feed_all serves the second and third metric over a key.  Keys resolve as in _epe_mm: a `*_abs` key is
+    compared against targs[key without _abs] + root_joint.  HIP tensors: ab_mesh_metrics; CPU tensors: mesh_values_torch."""
+    thr = tuple(float(t) for t in (thresholds if thresholds is not None else [t / 1000.0 for t in MESH_F_THRESHOLDS_MM]))
+    tkey = key.replace("_abs", "") if "_abs" in key else key
+    if preds.get(key) is None or targs.get(tkey) is None or ("_abs" in key and targs.get(Queries.ROOT_JOINT) is None):
+        return None
+    pred = preds[key].detach()
+    N, M = pred.shape[1], targs[tkey].shape[1]
+    center = int(center_idx) if N == CONST.NUM_JOINTS and N == M else -1
+    mk = ("mesh", key, center, thr)
+    if memo is not None and mk in memo:
+        return memo[mk]
+    from . import kernels as K
+    flags = (K.MM_PAIRED | K.MM_PROCRUSTES | K.MM_NN) if N == M and N >= 3 else K.MM_NN
+    f = lambda t: t.to(device=pred.device, dtype=torch.float32).contiguous()      # noqa: E731
+    root = f(targs[Queries.ROOT_JOINT]) if "_abs" in key else None
+    fn = K.mesh_metrics if pred.is_cuda else mesh_values_torch
+    val = dict(fn(f(pred), f(targs[tkey]), root, center_idx=center, thresholds=thr, flags=flags), n_points=(N, M))
+    if memo is not None:
+        memo[mk] = val
+    return val
+
+
+class _MeshMetric(Metric):
+    """Shared bookkeeping of the three mesh metrics: per measure one [sum over samples, count] pair from feed_device (nothing there reads
+    the device), averaged over samples on the host -- the mean over samples of the per-sample value, as the scoring scripts average.
+    A key whose prediction or target a batch lacks is skipped for that batch and logged once (HO3D's evaluation split has no hand
+    annotation).  --filter_unseen_obj_idxs is NOT honoured by these classes."""
+
+    def __init__(self, **cfg):
+        self.val_keys_list: List[str] = list(cfg["VAL_KEYS"])
+        self.to_millimeters = cfg.get("MILLIMETERS", False)
+        self.center_idx = int(cfg.get("CENTER_IDX", (cfg.get("DATA_PRESET") or {}).get("CENTER_IDX", 0)))
+        self.thresholds = None
+        self.avg_meters: Dict[str, AverageMeter] = {}
+        self._skipped = set()
+
+    def reset(self):
+        for m in self.avg_meters.values():
+            m.reset()
+
+    def _measures(self, key, val):
+        """[(measure name, (B,) tensor)] of one key."""
+        raise NotImplementedError()
+
+    def _col(self, val, name, k=0):
+        from .kernels import MM_ROW
+        d = val["rows"][:, MM_ROW[name] + k]
+        return d * 1000.0 if self.to_millimeters and name not in ("f", "pa_f") else d
+
+    def feed_device(self, preds, targs, memo=None, **kwargs):
+        names, out = [], []
+        for key in self.val_keys_list:
+            val = _mesh_values(preds, targs, key, memo, self.center_idx, self.thresholds)
+            if val is None:
+                if key not in self._skipped:
+                    self._skipped.add(key)
+                    import logging
+                    logging.getLogger("anakin").warning(f"{type(self).__name__}: batch without '{key}' or its target; the key is skipped for such batches")
+                continue
+            for name, d in self._measures(key, val):
+                n = torch.full((), float(d.shape[0]), dtype=torch.float32, device=d.device)
+                names.append(name)
+                out.append(torch.stack([d.sum().to(torch.float32), n]))
+        return out, names
+
+    def feed_host(self, arrays, extra=None, **kwargs):
+        for name, a in zip(extra or [], arrays):
+            self.avg_meters.setdefault(name, AverageMeter()).update(float(a[0]), n=int(a[1]))
+
+    def feed(self, preds, targs, **kwargs):
+        out, names = self.feed_device(preds, targs)
+        self.feed_host([t.cpu().numpy() for t in out], extra=names)
+
+    def get_measures(self, **kwargs):
+        return {k: m.avg for k, m in self.avg_meters.items()}
+
+    def __str__(self):
+        return " | ".join(f"{k}: {m.avg:6.4f}" for k, m in self.avg_meters.items())
+
+
+@METRIC.register_module
+class MeanAlignedEPE(_MeshMetric):
+    """PA-MPJPE / PA-MPVPE and the root-relative error: `{key}_pa_mepe` (after the similarity alignment of the prediction onto the target:
+    rotation or reflection, scale, translation) and `{key}_ra_mepe` (both clouds relative to their CENTER_IDX point).  ALIGN: a subset of
+    {root, procrustes}, default [procrustes]; `root` is defined for 21-joint arrays only.  CENTER_IDX defaults to DATA_PRESET.CENTER_IDX."""
+
+    def __init__(self, **cfg):
+        super().__init__(**cfg)
+        self.align = list(cfg.get("ALIGN", ["procrustes"]))
+        if not self.align or set(self.align) - {"root", "procrustes"}:
+            raise ValueError(f"MeanAlignedEPE: ALIGN must be a non-empty subset of [root, procrustes], got {self.align}")
+
+    def _measures(self, key, val):
+        out = []
+        N = val["n_points"]
+        if N[0] != N[1] or N[0] < 3:
+            raise ValueError(f"MeanAlignedEPE: '{key}' pairs {N[0]} predicted with {N[1]} target points; an aligned error needs N == M >= 3")
+        if "procrustes" in self.align:
+            out.append((f"{key}_pa_mepe", self._col(val, "pa_epe")))
+        if "root" in self.align:
+            if N[0] != CONST.NUM_JOINTS:
+                raise ValueError(f"MeanAlignedEPE: ALIGN root needs a {CONST.NUM_JOINTS}-joint array, '{key}' has {N[0]} points")
+            out.append((f"{key}_ra_mepe", self._col(val, "ra_epe")))
+        return out
+
+
+@METRIC.register_module
+class MeshFScore(_MeshMetric):
+    """Mesh F-scores: per sample the harmonic mean of precision #{d_pg < t} / N and recall #{d_gp < t} / M over the two-way nearest
+    distances, `{key}_f{t}` unaligned and `{key}_pa_f{t}` after the similarity alignment (t in mm, printed with %g: f5, f15).
+    THRESHOLDS_MM default [5, 15] (at most 4); ALIGN: a subset of {none, procrustes}, default both."""
+
+    def __init__(self, **cfg):
+        super().__init__(**cfg)
+        self.thresholds_mm = [float(t) for t in cfg.get("THRESHOLDS_MM", MESH_F_THRESHOLDS_MM)]
+        self.align = list(cfg.get("ALIGN", ["none", "procrustes"]))
+        if not self.align or set(self.align) - {"none", "procrustes"}:
+            raise ValueError(f"MeshFScore: ALIGN must be a non-empty subset of [none, procrustes], got {self.align}")
+        if not 1 <= len(self.thresholds_mm) <= 4:
+            raise ValueError(f"MeshFScore: 1 to 4 THRESHOLDS_MM, got {self.thresholds_mm}")
+        self.thresholds = [t / 1000.0 for t in self.thresholds_mm]
+
+    def _measures(self, key, val):
+        out = []
+        N = val["n_points"]
+        if "procrustes" in self.align and (N[0] != N[1] or N[0] < 3):
+            raise ValueError(f"MeshFScore: '{key}' pairs {N[0]} predicted with {N[1]} target points; ALIGN procrustes needs N == M >= 3")
+        for pre, col in (("none", "f"), ("procrustes", "pa_f")):
+            if pre in self.align:
+                out += [(f"{key}_{col}{t:g}", self._col(val, col, k)) for k, t in enumerate(self.thresholds_mm)]
+        return out
+
+
+@METRIC.register_module
+class MeanSurfaceDist(_MeshMetric):
+    """ADD-S of an object mesh: `{key}_adds`, the mean over the points of the posed ground-truth model of the distance to the nearest
+    predicted point, unaligned; the two clouds need not have the same number of points."""
+
+    def _measures(self, key, val):
+        return [(f"{key}_adds", self._col(val, "mean_gp"))]

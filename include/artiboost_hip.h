@@ -755,6 +755,53 @@ int ab_chamfer_rigid(const float* can, const float* rot, const float* tsl, const
 int ab_procrustes_loss(const float* pred, const float* targ, const float* root, int B, int n, float* sample_loss, float* loss,
                        float* aligned, float* g_pred, void* stream);
 
+/* ---- Leaderboard mesh metrics of the evaluator, eager only (csrc/mesh_metrics.hip) ----------------------------------
+ * What HO3D / DexYCB results are published in: the Procrustes-aligned and root-relative errors, the mesh F-scores and ADD-S.
+ * pred [B,N,3], targ [B,M,3] fp32; root [B,3] or NULL (zero), added to targ; center_idx: the centre point of the root-relative error, or
+ * < 0 (none); thresholds_host: T <= AB_MM_MAX_THRESHOLDS F-score thresholds in metres, a HOST array read during the call; flags: which
+ * groups to compute.  AB_MM_PAIRED and AB_MM_PROCRUSTES need N == M, AB_MM_PROCRUSTES N >= 3, center_idx < N: AB_EINVAL otherwise.
+ * Per sample, with P = pred[b] and G = targ[b] + root[b]:
+ *   AB_MM_PAIRED      epe = mean_i |P_i - G_i|;  ra_epe = mean_i |(P_i - P_c) - (G_i - G_c)|, c = center_idx (NaN when center_idx < 0)
+ *   AB_MM_PROCRUSTES  the similarity of ab_procrustes_loss, formed as that entry point forms `aligned` (same normalisation by the Frobenius
+ *                     norms + 1e-8, same one-sided Jacobi, finite numbers for rank-deficient clouds): with Pc, Gc the centred clouds and
+ *                     K = Gc^T Pc = U S V^T,  R = U V^T with NO determinant correction (a mirrored prediction aligns by a reflection, as
+ *                     in AlignLoss and the public FreiHAND / HO3D scoring scripts),  s = tr S / |Pc|^2,  P'_i = s R Pc_i + centroid(G);
+ *                     pa_epe = mean_i |P'_i - G_i|,  scale = s.  The two entry points agree on P' to rounding.
+ *   AB_MM_NN          for Q = P and, with AB_MM_PROCRUSTES, Q = P':  d_pg[i] = min_j |Q_i - G_j|,  d_gp[j] = min_i |Q_i - G_j|  as sums of
+ *                     squared differences (never |x|^2 + |y|^2 - 2 x.y), squared lengths compared, one square root per point;
+ *                     mean_pg, mean_gp their means (mean_gp is ADD-S: the mean over the posed ground-truth points of the distance to the
+ *                     nearest predicted point);  per threshold t:  precision = #{d_pg < t} / N,  recall = #{d_gp < t} / M  (strict <; the
+ *                     points of a cloud padded by repetition each count),  F = 2 p r / (p + r), 0 when p + r = 0.
+ * rows [B, AB_MM_ROW] fp32, written in full: the AB_MM_* slots below; a group that was not asked for, ra_epe without a centre and the
+ * F slots at or past T are NaN.  counts int32 [B, T, 4]: per threshold #{d_pg < t}, #{d_gp < t}, then the same two of the aligned scan
+ * (zero where the scan was not asked for).  d_pg [B,N], d_gp [B,M], pa_d_pg [B,N], pa_d_gp [B,M]: the per-point distances in metres,
+ * each optional (NULL).  workspace: ab_mesh_metrics_workspace(B, N, M) bytes (the similarity of each sample, one partial per sample, scan
+ * and chunk of 256 query points).  Three launches: one wave per sample for the paired sums and the similarity; one workgroup per (sample,
+ * scan, direction, chunk), applying the similarity as it stages or forms the points, so no aligned [B,N,3] is written; one thread per
+ * sample adding its chunks in turn.  No atomics: two calls give the same bits, and a sample's row, counts and distances do not depend on
+ * the batch around it.  1 <= B <= 65535, 1 <= N, M <= 2^24.
+ * Like the two mesh losses above, this entry point is not captured in a hipGraph anywhere in this project (DESIGN.md sections 19 and 23):
+ * the evaluator is fed outside the replayed graphs.                                                                                      */
+#define AB_MM_PAIRED 1
+#define AB_MM_PROCRUSTES 2
+#define AB_MM_NN 4
+#define AB_MM_MAX_THRESHOLDS 4
+#define AB_MM_ROW 16           /* floats per sample row: */
+#define AB_MM_EPE 0
+#define AB_MM_RA_EPE 1
+#define AB_MM_PA_EPE 2
+#define AB_MM_SCALE 3
+#define AB_MM_MEAN_PG 4
+#define AB_MM_MEAN_GP 5        /* ADD-S */
+#define AB_MM_PA_MEAN_PG 6
+#define AB_MM_PA_MEAN_GP 7
+#define AB_MM_F 8              /* [AB_MM_MAX_THRESHOLDS] */
+#define AB_MM_PA_F 12          /* [AB_MM_MAX_THRESHOLDS] */
+long ab_mesh_metrics_workspace(int B, int N, int M);
+int ab_mesh_metrics(const float* pred, const float* targ, const float* root, int B, int N, int M, int center_idx,
+                    const float* thresholds_host, int T, int flags, float* rows, int32_t* counts, float* d_pg, float* d_gp, float* pa_d_pg,
+                    float* pa_d_gp, void* workspace, void* stream);
+
 /* ---- Argument contracts of the dispatcher ops (torch.ops.artiboost_hip.*, libartiboost_torch.so) ------------------------------------------
  * The C entry points above take raw pointers and trust their caller.  Their PyTorch-dispatcher form (ops that "validate
  * with TORCH_CHECK") is generated from this header by artiboost_amd/gen_torch_ops.py and checks, before the C call, for EVERY op:
@@ -830,6 +877,7 @@ int ab_procrustes_loss(const float* pred, const float* targ, const float* root, 
  * @check ab_mssd: can pred_pts >= B*V*3; obj_transf >= B*16; obj_idx mssd >= B; sym_R >= n_obj*Kmax*9; sym_t >= n_obj*Kmax*3; sym_count >= n_obj; pred_R >= B*9; pred_t center >= B*3; bytes workspace >= ab_mssd_workspace(B,Kmax,V)
  * @check ab_chamfer_rigid: can >= B*N*3; rot g_rot >= B*9; tsl root g_tsl >= B*3; targ >= B*M*3; corners_vis >= B*8; loss >= 1; dist_xy idx_xy >= B*N; dist_yx idx_yx >= B*M; bytes workspace >= ab_chamfer_rigid_workspace(B,N,M)
  * @check ab_procrustes_loss: pred targ aligned g_pred >= B*n*3; root >= B*3; sample_loss >= B; loss >= 1
+ * @check ab_mesh_metrics: pred >= B*N*3; targ >= B*M*3; root >= B*3; thresholds_host >= T; rows >= B*AB_MM_ROW; counts >= B*T*4; d_pg pa_d_pg >= B*N; d_gp pa_d_gp >= B*M; bytes workspace >= ab_mesh_metrics_workspace(B,N,M)
  */
 
 #ifdef __cplusplus
