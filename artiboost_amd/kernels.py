@@ -1096,6 +1096,38 @@ def mesh_metrics(pred, targ, root=None, center_idx=-1, thresholds=(), flags=MM_P
     return o
 
 
+IA_VERTS, IA_VOLUME = 1, 2                     # AB_IA_* flags of ab_interaction
+IA_ROW = {"pen_max": 0, "pen_mean": 1, "min_dist": 2, "inside_frac": 3, "contact": 4, "volume": 5}      # slots 6, 7 reserved (NaN)
+IA_COUNTS = {"n_inside": 0, "n_lattice": 1, "n_both": 2, "capped": 3}
+
+
+def interaction(hand_verts, hand_faces, hand_orient, obj_verts, obj_faces, vert_off, face_off, obj_orient, obj_row, rot, tsl,
+                contact_thr=0.005, voxel=0.005, max_voxels=262144, flags=IA_VERTS | IA_VOLUME, want_sdf=False):
+    """ab_interaction (eager only, never under graph capture): hand vertices [B,Nh,3] against the object rot[b] can + tsl[b] of the packed
+    table (obj_verts [*,3] fp32, obj_faces int32 [*,3] local indices, vert_off / face_off int32 [n_obj+1], obj_orient fp32 [n_obj] of +-1,
+    obj_row int64 [B]) and the lattice intersection volume with the hand mesh (hand_faces int32 [Fh,3], hand_orient +-1).  Distances in
+    metres.  -> dict: rows [B,8] (columns IA_ROW; NaN where a group was not asked for), counts int32 [B,4] (IA_COUNTS); with want_sdf
+    sdf [B,Nh] (-d inside, +d outside) and wind [B,Nh] (orientation x winding number)."""
+    B, Nh, Fh, n_obj = hand_verts.shape[0], hand_verts.shape[1], hand_faces.shape[0], obj_orient.numel()
+    for what, t, dt, numel in (("hand_faces", hand_faces, torch.int32, Fh * 3), ("obj_faces", obj_faces, torch.int32, None),
+                               ("vert_off", vert_off, torch.int32, n_obj + 1), ("face_off", face_off, torch.int32, n_obj + 1),
+                               ("obj_row", obj_row, torch.int64, B), ("obj_verts", obj_verts, torch.float32, None)):
+        if t.dtype != dt or (t.numel() != numel if numel is not None else t.numel() < 3):
+            raise ValueError(f"interaction: {what} must be {dt} with {numel if numel is not None else 'at least 3'} elements, got {t.dtype} {tuple(t.shape)}")
+    ins = {"hand_verts": _f32_of("interaction", "hand_verts", hand_verts, B * Nh * 3), "obj_orient": _f32_of("interaction", "obj_orient", obj_orient, n_obj),
+           "rot": _f32_of("interaction", "rot", rot, B * 9), "tsl": _f32_of("interaction", "tsl", tsl, B * 3)}
+    dev = hand_verts.device
+    o = {"rows": torch.empty((B, 8), dtype=torch.float32, device=dev), "counts": torch.empty((B, 4), dtype=torch.int32, device=dev)}
+    if want_sdf:
+        o["sdf"], o["wind"] = torch.empty((B, Nh), dtype=torch.float32, device=dev), torch.empty((B, Nh), dtype=torch.float32, device=dev)
+    ws = _workspace(L.lib().ab_interaction_workspace(L.i(B), L.i(Nh), L.i(max_voxels)), dev)
+    L.check(L.lib().ab_interaction(ins["hand_verts"], L.ptr(hand_faces), L.i(Nh), L.i(Fh), L.f(hand_orient), L.ptr(obj_verts), L.ptr(obj_faces),
+                                   L.ptr(vert_off), L.ptr(face_off), ins["obj_orient"], L.i(n_obj), L.ptr(obj_row), ins["rot"], ins["tsl"], L.i(B),
+                                   L.f(contact_thr), L.f(voxel), L.i(max_voxels), L.i(flags), o["rows"], o["counts"], o.get("sdf"), o.get("wind"),
+                                   L.ptr(ws), L.stream()), "ab_interaction")
+    return o
+
+
 FIT_NP = 59             # parameters per hand of ab_mano_fit: so3 48 | beta 10 | bone 1
 
 

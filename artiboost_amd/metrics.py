@@ -854,3 +854,328 @@ class MeanSurfaceDist(_MeshMetric):
 
     def _measures(self, key, val):
         return [(f"{key}_adds", self._col(val, "mean_gp"))]
+
+
+# ============================================================================ hand-object interaction
+def drop_repeated_faces(faces):
+    """The faces whose three indices differ (the stand-in hand pads to 1 538 faces with fans that repeat an index)."""
+    f = np.asarray(faces).reshape(-1, 3)
+    return np.ascontiguousarray(f[(f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0])]).astype(np.int32)
+
+
+def mesh_orientation(verts, faces):
+    """o = sign(sum_f a . (b x c)) in float64: the sign of the mesh's signed volume (+1 for a mesh without volume)."""
+    v, f = np.asarray(verts, np.float64), np.asarray(faces).reshape(-1, 3)
+    vol = np.einsum("ij,ij->", v[f[:, 0]], np.cross(v[f[:, 1]], v[f[:, 2]]))
+    return -1.0 if vol < 0 else 1.0
+
+
+def _triangle_scan(q, tri, want_dist):
+    """q [Q,3] against tri [F,3,3] as [Q,F] blocks (at most 2^20 pairs at a time) -> (w [Q] = sum_f Omega_f / (4 pi), the smallest squared
+    distance [Q] or None), by the definitions of ab_interaction in the tensors' dtype."""
+    import math
+    Q, F = q.shape[0], tri.shape[0]
+    e1, e2 = (tri[:, 1] - tri[:, 0])[None], (tri[:, 2] - tri[:, 0])[None]
+    dot = lambda x, y: (x * y).sum(-1)      # noqa: E731
+    ws, ds = [], []
+    step = max(1, (1 << 20) // max(F, 1))
+    for s in range(0, Q, step):
+        qq = q[s:s + step, None]
+        A, B, C = tri[None, :, 0] - qq, tri[None, :, 1] - qq, tri[None, :, 2] - qq
+        la, lb, lc = dot(A, A).sqrt(), dot(B, B).sqrt(), dot(C, C).sqrt()
+        num = dot(A, torch.cross(B, C, dim=-1))
+        den = la * lb * lc + dot(A, B) * lc + dot(B, C) * la + dot(C, A) * lb
+        om = torch.where((num == 0) & (den == 0), torch.zeros_like(num), 2.0 * torch.atan2(num, den))
+        ws.append(om.sum(1) / (4.0 * math.pi))
+        if not want_dist:
+            continue
+        d1, d2, d3, d4, d5, d6 = -dot(e1, A), -dot(e2, A), -dot(e1, B), -dot(e2, B), -dot(e1, C), -dot(e2, C)
+        vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
+        e43, e56 = d4 - d3, d5 - d6
+        zero, one = torch.zeros_like(va), torch.ones_like(va)
+        nv, nw, dn = vb, vc, (va + vb) + vc                                        # interior; then the regions, the first of the list winning last
+        for cond, a, b, c in (((va <= 0) & (e43 >= 0) & (e56 >= 0), e56, e43, e43 + e56),       # edge bc
+                              ((vb <= 0) & (d2 >= 0) & (d6 <= 0), zero, d2, d2 - d6),           # edge ac
+                              ((d6 >= 0) & (d5 <= d6), zero, one, one),                         # vertex c
+                              ((vc <= 0) & (d1 >= 0) & (d3 <= 0), d1, zero, d1 - d3),           # edge ab
+                              ((d3 >= 0) & (d4 <= d3), one, zero, one),                         # vertex b
+                              ((d1 <= 0) & (d2 <= 0), zero, zero, one)):                        # vertex a
+            nv, nw, dn = torch.where(cond, a, nv), torch.where(cond, b, nw), torch.where(cond, c, dn)
+        ok = dn != 0
+        safe = torch.where(ok, dn, one)
+        v, w = torch.where(ok, nv / safe, zero), torch.where(ok, nw / safe, zero)  # a zero denominator gives parameter 0
+        r = A + v[..., None] * e1 + w[..., None] * e2
+        ds.append(dot(r, r).min(1)[0])
+    return torch.cat(ws), (torch.cat(ds) if want_dist else None)
+
+
+def interaction_values_torch(hand_verts, hand_faces, hand_orient, obj_verts, obj_faces, vert_off, face_off, obj_orient, obj_row, rot, tsl,
+                             contact_thr=0.005, voxel=0.005, max_voxels=262144, flags=3, want_sdf=False, want_lattice=False):
+    """The definitions of ab_interaction (include/artiboost_hip.h) as torch ops in hand_verts' dtype: the route of CPU tensors, in float64
+    the reference of the tests, and what tools/bench_interaction.py times on device tensors.  Same arguments and the same dict as
+    kernels.interaction: rows [B,8] (columns kernels.IA_ROW; NaN where a group was not asked for), counts int32 [B,4] and, with want_sdf,
+    sdf and wind [B,Nh].  Like the kernel it takes a query into the object's canonical frame, q' = R^T (q - t), and scans the canonical
+    triangles, one [Q,F] block per sample; the lattice points of the volume are scanned against the object and, those inside it, against
+    the hand mesh of the camera frame.  want_lattice (this route only): also `lattice`, per sample None or (points [n,3], o w of the object [n],
+    o w of the hand [n], NaN where the point is outside the object and the hand was not scanned)."""
+    from .kernels import IA_ROW as C, IA_VERTS, IA_VOLUME
+    hv = hand_verts.detach()
+    dt, dev = hv.dtype, hv.device
+    B, Nh = hv.shape[0], hv.shape[1]
+    n_obj = int(obj_orient.numel())
+    rows = torch.full((B, 8), float("nan"), dtype=dt, device=dev)
+    counts = torch.zeros((B, 4), dtype=torch.int32, device=dev)
+    out = {"rows": rows, "counts": counts}
+    if want_sdf:
+        out["sdf"], out["wind"] = torch.full((B, Nh), float("nan"), dtype=dt, device=dev), torch.full((B, Nh), float("nan"), dtype=dt, device=dev)
+    if want_lattice:
+        out["lattice"] = [None] * B
+    vo, fo = [int(x) for x in vert_off.cpu()], [int(x) for x in face_off.cpu()]
+    orow = [min(max(int(r), 0), n_obj - 1) for r in obj_row.cpu()]
+    orient = [float(x) for x in obj_orient.cpu()]
+    hf = hand_faces.to(dev).long().reshape(-1, 3)
+    R_all, t_all = rot.detach().to(device=dev, dtype=dt).reshape(B, 3, 3), tsl.detach().to(device=dev, dtype=dt).reshape(B, 3)
+    for b in range(B):
+        r = orow[b]
+        can = obj_verts[vo[r]:vo[r + 1]].to(device=dev, dtype=dt)
+        tri = can[obj_faces[fo[r]:fo[r + 1]].to(dev).long().reshape(-1, 3)]
+        R, t = R_all[b], t_all[b]
+        if flags & IA_VERTS:
+            w, d2 = _triangle_scan((hv[b] - t) @ R, tri, True)
+            w, d = orient[r] * w, d2.sqrt()
+            inside = w > 0.5
+            n_in = inside.sum()
+            din = torch.where(inside, d, torch.zeros_like(d))
+            rows[b, C["pen_max"]], rows[b, C["pen_mean"]] = din.max(), din.sum() / n_in.clamp_min(1).to(dt)
+            rows[b, C["min_dist"]], rows[b, C["inside_frac"]] = d.min(), n_in.to(dt) / Nh
+            rows[b, C["contact"]] = ((n_in > 0) | (d.min() <= contact_thr)).to(dt)
+            counts[b, 0] = n_in.to(torch.int32)
+            if want_sdf:
+                out["sdf"][b], out["wind"][b] = torch.where(inside, -d, d), w
+        if flags & IA_VOLUME:
+            posed = can @ R.T + t
+            lo = torch.maximum(hv[b].min(0)[0], posed.min(0)[0])
+            hi = torch.minimum(hv[b].max(0)[0], posed.max(0)[0])
+            first = torch.ceil(lo / voxel - 0.5).clamp(-1e9, 1e9).cpu().tolist()      # h (i + 1/2) in [lo, hi]
+            last = torch.floor(hi / voxel - 0.5).clamp(-1e9, 1e9).cpu().tolist()
+            n = [int(l) - int(f) + 1 if l >= f else 0 for f, l in zip(first, last)]
+            nl = n[0] * n[1] * n[2]
+            counts[b, 1] = min(nl, 2 ** 31 - 1)
+            if nl > max_voxels:
+                counts[b, 3] = 1
+                continue
+            n_both = 0
+            if nl:
+                ax = [voxel * (torch.arange(int(f), int(f) + k, dtype=dt, device=dev) + 0.5) for f, k in zip(first, n)]
+                p = torch.stack(torch.meshgrid(ax[2], ax[1], ax[0], indexing="ij"), -1).reshape(-1, 3).flip(-1)      # x fastest, as the kernel's index
+                w_obj = orient[r] * _triangle_scan((p - t) @ R, tri, False)[0]
+                in_obj = w_obj > 0.5
+                w_hand = torch.full_like(w_obj, float("nan"))
+                if bool(in_obj.any()):
+                    w_hand[in_obj] = hand_orient * _triangle_scan(p[in_obj], hv[b][hf], False)[0]
+                    n_both = int((w_hand[in_obj] > 0.5).sum())
+                if want_lattice:
+                    out["lattice"][b] = (p, w_obj, w_hand)
+            counts[b, 2] = n_both
+            rows[b, C["volume"]] = n_both * float(voxel) ** 3
+    return out
+
+
+class ObjectMeshTable:
+    """The object meshes of the interaction measures as one packed table (the layout of assets.SceneAssets: verts [*,3] fp32, faces int32
+    [*,3] with indices local to the object, vert_off / face_off int32 [n_obj + 1]), each mesh's orientation (the sign of its signed volume,
+    float64 on the host) and the map from a batch's `obj_idx` (YCB class id) to a table row.  Faces with a repeated index are dropped here.
+    Uploaded once per device (`on`).  The hand's faces and orientation travel with it (`set_hand`)."""
+
+    def __init__(self, meshes, obj_ids, hand_model=None):
+        """meshes: [(verts [V,3], faces [F,3])] in the canonical frame the poses act on (that of `corners_can`); obj_ids: their class ids."""
+        vs, fs, vo, fo, orient = [], [], [0], [0], []
+        for v, f in meshes:
+            v, f = np.asarray(v, np.float32).reshape(-1, 3), drop_repeated_faces(f)
+            if len(f) < 1 or f.min() < 0 or f.max() >= len(v):
+                raise ValueError("ObjectMeshTable: every object needs at least one face, with indices inside its vertex list")
+            vs.append(v); fs.append(f); vo.append(vo[-1] + len(v)); fo.append(fo[-1] + len(f)); orient.append(mesh_orientation(v, f))
+        self.verts, self.faces = np.concatenate(vs), np.concatenate(fs)
+        self.vert_off, self.face_off = np.asarray(vo, np.int32), np.asarray(fo, np.int32)
+        self.orient = np.asarray(orient, np.float32)
+        self.obj_ids = [int(i) for i in obj_ids]
+        self.row_of = {i: r for r, i in enumerate(self.obj_ids)}
+        lut = np.full(max(self.obj_ids + [0]) + 1, -1, np.int64)      # an id the table lacks maps to -1 (the kernel clamps it to row 0)
+        lut[self.obj_ids] = np.arange(len(self.obj_ids))
+        self._lut = lut
+        self.hand_faces, self.hand_orient = None, 1.0
+        self._dev = {}
+        if hand_model is not None:
+            self.set_hand(hand_model)
+
+    @property
+    def n_obj(self):
+        return len(self.obj_ids)
+
+    def set_hand(self, hand_model):
+        """Hand faces from draw.hand_model_faces, the orientation from the rest-pose template."""
+        from .draw import hand_model_faces
+        self.hand_faces = drop_repeated_faces(hand_model_faces(hand_model))
+        self.hand_orient = mesh_orientation(hand_model["v_template"], self.hand_faces)
+        self._dev = {}
+        return self
+
+    @classmethod
+    def from_assets(cls, assets, hand_model=None):
+        """From a SceneAssets: obj_verts / obj_faces / obj_vert_off / obj_face_off / obj_idx, and its hand model."""
+        vo, fo = assets.obj_vert_off, assets.obj_face_off
+        meshes = [(assets.obj_verts[vo[k]:vo[k + 1]], assets.obj_faces[fo[k]:fo[k + 1]]) for k in range(len(vo) - 1)]
+        return cls(meshes, list(assets.obj_idx), hand_model if hand_model is not None else assets.hand)
+
+    @classmethod
+    def from_dataset(cls, ds, hand_model=None):
+        """From a dataset reader with `_verts_can` / `get_obj_faces` (datasets.HO3D): the objects its frames hold, by name, each in the
+        canonical frame of `corners_can`."""
+        first = {}
+        for idx, i in enumerate(ds.sample_idxs):
+            first.setdefault(ds.ann["obj_name"][i], idx)
+        names = sorted(first)
+        return cls([(ds._verts_can(o), ds.get_obj_faces(first[o])) for o in names], [ds.name2id[o] for o in names], hand_model)
+
+    def on(self, device):
+        """The table's tensors on `device`, uploaded once."""
+        key = str(device)
+        if key not in self._dev:
+            if self.hand_faces is None:
+                raise RuntimeError("ObjectMeshTable: no hand faces (set_hand)")
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)      # noqa: E731
+            self._dev[key] = dict(obj_verts=t(self.verts), obj_faces=t(self.faces), vert_off=t(self.vert_off), face_off=t(self.face_off),
+                                  obj_orient=t(self.orient), hand_faces=t(self.hand_faces), lut=t(self._lut))
+        return self._dev[key]
+
+    def rows(self, obj_idx):
+        """int64 [B] table rows of a batch's class ids, on their device, without a host read."""
+        lut = self.on(obj_idx.device)["lut"]
+        i = obj_idx.reshape(-1).long()
+        return torch.where((i >= 0) & (i < lut.numel()), lut[i.clamp(0, lut.numel() - 1)], torch.full_like(i, -1))
+
+
+IA_MEASURES = ("pen_depth_mm", "pen_mean_mm", "min_dist_mm", "inside_frac", "contact_ratio", "inter_vol_cm3", "capped")
+
+
+@METRIC.register_module
+class InteractionMetric(Metric):
+    """Hand-object interaction of a prediction: means over samples of the maximum penetration depth of the hand vertices into the object
+    (`pen_depth_mm`), their mean depth (`pen_mean_mm`), the smallest hand-object distance (`min_dist_mm`), the fraction of hand vertices
+    inside (`inside_frac`), the fraction of samples in contact (`contact_ratio`: a vertex inside or within CONTACT_MM) and, with VOLUME, the
+    intersection volume of the two meshes at VOXEL_MM voxels (`inter_vol_cm3`, over the samples whose lattice stayed within MAX_VOXELS;
+    `capped` counts the others).  The hand is preds[HAND_KEY] with the hand model's faces, the object its canonical mesh under
+    preds[ROT_KEY] / preds[TSL_KEY] (the rule of corners_3d_abs and MSSD), chosen by targs[obj_idx].  REPORT_GT adds the same measures of
+    the annotation with a `gt_` prefix (targs: hand_verts_3d + root_joint, obj_transf).  OBJ_MESHES {SOURCE: assets, DATASET: HO3D} builds
+    the stand-in table as synth.py builds its assets; `set_obj_meshes(table)` is for callers that hold the real meshes.  HIP tensors: one
+    ab_interaction call per batch and group (through the evaluator's memo), nothing read back in feed_device; CPU tensors:
+    interaction_values_torch in their dtype.  A batch that lacks a key is skipped and logged once."""
+
+    def __init__(self, **cfg):
+        self.hand_key = cfg.get("HAND_KEY", "hand_verts_3d_abs")
+        self.rot_key, self.tsl_key = cfg.get("ROT_KEY", "box_rot_rotmat"), cfg.get("TSL_KEY", "boxroot_3d_abs")
+        self.contact_thr, self.voxel = float(cfg.get("CONTACT_MM", 5.0)) / 1000.0, float(cfg.get("VOXEL_MM", 5.0)) / 1000.0
+        self.max_voxels, self.volume, self.report_gt = int(cfg.get("MAX_VOXELS", 262144)), bool(cfg.get("VOLUME", True)), bool(cfg.get("REPORT_GT", False))
+        if self.voxel <= 0 or self.contact_thr < 0 or not 1 <= self.max_voxels <= 1 << 24:
+            raise ValueError("InteractionMetric: VOXEL_MM > 0, CONTACT_MM >= 0 and 1 <= MAX_VOXELS <= 2^24")
+        self.table = None
+        src = cfg.get("OBJ_MESHES")
+        if src:
+            if str(src.get("SOURCE", "assets")) != "assets":
+                raise ValueError(f"InteractionMetric: OBJ_MESHES.SOURCE must be 'assets' (or call set_obj_meshes), got {src.get('SOURCE')!r}")
+            from .assets import SceneAssets
+            self.table = ObjectMeshTable.from_assets(SceneAssets(src.get("DATASET", "HO3D"), seed=1))
+        self._skipped = set()
+        self.reset()
+
+    def set_obj_meshes(self, table):
+        if table.hand_faces is None:
+            from .hpregnet import load_hand_model
+            table.set_hand(load_hand_model("assets/mano_v1_2"))
+        self.table = table
+        return self
+
+    def reset(self):
+        self.sums = {}       # prefix -> float64 [9]: sums of the six row slots | samples not capped | capped | samples
+
+    def _inputs(self, preds, targs, prefix):
+        """(hand [B,Nh,3], rot [B,3,3], tsl [B,3], obj_idx [B]) of a group, or the name of the key the batch lacks."""
+        if targs.get(Queries.OBJ_IDX) is None:
+            return Queries.OBJ_IDX
+        if prefix == "":
+            for k in (self.hand_key, self.rot_key, self.tsl_key):
+                if preds.get(k) is None:
+                    return k
+            hand, rot, tsl = preds[self.hand_key].detach(), preds[self.rot_key].detach(), preds[self.tsl_key].detach()
+        else:
+            for k in ("hand_verts_3d", Queries.ROOT_JOINT, Queries.OBJ_TRANSF):
+                if targs.get(k) is None:
+                    return k
+            T = targs[Queries.OBJ_TRANSF]
+            hand, rot, tsl = targs["hand_verts_3d"] + targs[Queries.ROOT_JOINT].to(targs["hand_verts_3d"].device).unsqueeze(1), T[:, :3, :3], T[:, :3, 3]
+        B = hand.shape[0]
+        return hand, rot.reshape(B, 3, 3), tsl.reshape(B, 3), targs[Queries.OBJ_IDX]
+
+    def values(self, hand, rot, tsl, obj_idx):
+        """The dict of kernels.interaction for one batch: HIP tensors through ab_interaction (fp32), CPU tensors through the torch route."""
+        if self.table is None:
+            raise RuntimeError("InteractionMetric: no object meshes (OBJ_MESHES in the config, or set_obj_meshes)")
+        from . import kernels as K
+        dev = hand.device
+        tb = self.table.on(dev)
+        flags = K.IA_VERTS | (K.IA_VOLUME if self.volume else 0)
+        dt = torch.float32 if hand.is_cuda else hand.dtype
+        f = lambda t: t.to(device=dev, dtype=dt).contiguous()      # noqa: E731
+        fn = K.interaction if hand.is_cuda else interaction_values_torch
+        return fn(f(hand), tb["hand_faces"], self.table.hand_orient, tb["obj_verts"], tb["obj_faces"], tb["vert_off"], tb["face_off"], tb["obj_orient"],
+                  self.table.rows(obj_idx.to(dev)), f(rot), f(tsl), contact_thr=self.contact_thr, voxel=self.voxel, max_voxels=self.max_voxels,
+                  flags=flags)
+
+    def feed_device(self, preds, targs, memo=None, **kwargs):
+        names, out = [], []
+        for prefix in ("", "gt_") if self.report_gt else ("",):
+            got = self._inputs(preds, targs, prefix)
+            if isinstance(got, str):
+                if (prefix, got) not in self._skipped:
+                    self._skipped.add((prefix, got))
+                    import logging
+                    logging.getLogger("anakin").warning(f"InteractionMetric: batch without '{got}'; its {prefix or 'prediction '}measures are skipped for such batches")
+                continue
+            mk = ("interaction", prefix, self.hand_key, self.rot_key, self.tsl_key, self.contact_thr, self.voxel, self.max_voxels, self.volume, id(self.table))
+            val = memo.get(mk) if memo is not None else None
+            if val is None:
+                val = self.values(*got)
+                if memo is not None:
+                    memo[mk] = val
+            rows, cnt = val["rows"].double(), val["counts"]
+            capped = cnt[:, 3] > 0
+            vol = torch.where(capped | rows[:, 5].isnan(), torch.zeros_like(rows[:, 5]), rows[:, 5])
+            n = torch.full((), float(rows.shape[0]), dtype=torch.float64, device=rows.device)
+            names.append(prefix)
+            out.append(torch.stack([rows[:, 0].sum(), rows[:, 1].sum(), rows[:, 2].sum(), rows[:, 3].sum(), rows[:, 4].sum(), vol.sum(),
+                                    (~capped).sum().double(), capped.sum().double(), n]))
+        return out, names
+
+    def feed_host(self, arrays, extra=None, **kwargs):
+        for prefix, a in zip(extra or [], arrays):
+            self.sums[prefix] = self.sums.get(prefix, np.zeros(9)) + np.asarray(a, np.float64)
+
+    def feed(self, preds, targs, **kwargs):
+        out, names = self.feed_device(preds, targs)
+        self.feed_host([t.cpu().numpy() for t in out], extra=names)
+
+    def get_measures(self, **kwargs):
+        out = {}
+        for prefix, s in self.sums.items():
+            n = s[8]
+            if n <= 0:
+                continue
+            out.update({prefix + "pen_depth_mm": 1000.0 * s[0] / n, prefix + "pen_mean_mm": 1000.0 * s[1] / n, prefix + "min_dist_mm": 1000.0 * s[2] / n,
+                        prefix + "inside_frac": s[3] / n, prefix + "contact_ratio": s[4] / n})
+            if self.volume:
+                out[prefix + "inter_vol_cm3"] = 1.0e6 * s[5] / s[6] if s[6] > 0 else float("nan")
+                out[prefix + "capped"] = int(s[7])
+        return out
+
+    def __str__(self):
+        return " | ".join(f"{k}: {v:6.4f}" for k, v in self.get_measures().items())

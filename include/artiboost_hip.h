@@ -802,6 +802,54 @@ int ab_mesh_metrics(const float* pred, const float* targ, const float* root, int
                     const float* thresholds_host, int T, int flags, float* rows, int32_t* counts, float* d_pg, float* d_gp, float* pa_d_pg,
                     float* pa_d_gp, void* workspace, void* stream);
 
+/* ---- Hand-object interaction measures of the evaluator, eager only (csrc/interact.hip) ------------------------------
+ * Whether the predicted hand is inside the predicted object or never touches it: maximum / mean penetration depth, smallest distance,
+ * contact, and the intersection volume of the two meshes on a lattice.  Definitions, for a mesh of triangles (a, b, c) and a query q, with
+ * A = a - q, B = b - q, C = c - q:
+ *   solid angle     num = A . (B x C),  den = |A||B||C| + (A.B)|C| + (B.C)|A| + (C.A)|B|,  Omega = 2 atan2(num, den), 0 when both are 0
+ *   winding number  w(q) = sum_f Omega_f / (4 pi)
+ *   orientation     o = sign(sum_f a . (b x c)), the sign of the mesh's signed volume, computed by the HOST per mesh in float64 and passed
+ *                   in (hand_orient, obj_orient [n_obj], each +-1); the kernel assumes no sign
+ *   inside          o w(q) > 0.5 (the meshes need not be watertight: the winding number degrades gracefully where a ray parity is undefined)
+ *   distance        d(q) = min_f |q - cp_f(q)|, cp_f the closest point of triangle f by the region form, every division guarded (a zero
+ *                   denominator gives parameter 0); sums of squared differences, squared lengths compared, one square root per query
+ * Faces with a repeated index are dropped by the host when it builds the face tables.
+ * hand_verts [B,Nh,3] fp32; hand_faces int32 [Fh,3] (needed with AB_IA_VOLUME only).  The objects are one packed table: obj_verts [*,3],
+ * obj_faces int32 [*,3] with indices LOCAL to the object, vert_off / face_off int32 [n_obj + 1]; obj_row int64 [B] selects the object
+ * (clamped into the table); rot [B,3,3], tsl [B,3]: the object mesh of sample b is rot[b] can + tsl[b].  A query is taken into the
+ * canonical frame once, q' = rot[b]^T (q - tsl[b]), and the canonical triangles are scanned from the table; no posed face list is written.
+ *   AB_IA_VERTS    hand vertex i against the object: inside_i, d_i;  pen_max = max over inside vertices of d_i (0 when none), pen_mean their
+ *                  mean (0 when none), min_dist = min_i d_i, inside_frac = n_inside / Nh, contact = 1 when n_inside > 0 or
+ *                  min_dist <= contact_thr, else 0.  sdf [B,Nh]: -d_i inside, +d_i outside; wind [B,Nh]: o w; each optional (NULL).
+ *   AB_IA_VOLUME   the lattice points p = voxel (i + 1/2, j + 1/2, k + 1/2), integer i, j, k, of the CAMERA frame (so a sample's value does
+ *                  not depend on the batch around it) inside the intersection of the axis-aligned boxes of the hand vertices and of the
+ *                  posed object vertices: n_lattice of them; n_both are inside the object AND inside the hand mesh (hand_orient);
+ *                  volume = n_both voxel^3.  More than max_voxels lattice points: nothing is scanned, volume NaN, capped = 1.
+ * rows [B, AB_IA_ROW] fp32, written in full: the slots below, metres and cubic metres; a group that was not asked for and the two
+ * reserved slots are NaN.  counts int32 [B,4]: n_inside, n_lattice, n_both, capped (zero where not asked for).  workspace:
+ * ab_interaction_workspace(B, Nh, max_voxels) bytes.  Launches: one workgroup of 256 threads per (sample, chunk of 256 hand vertices), the
+ * triangles through LDS in SoA tiles; one workgroup per sample for the boxes and index ranges; a FIXED grid of ceil(max_voxels / 256)
+ * chunks per sample whose workgroups leave at once past n_lattice or when the sample is capped (the host reads nothing back between the
+ * launches); one thread per sample adding its chunks in turn.  No atomics: two calls give the same bits, and a sample's row, counts, sdf
+ * and wind do not depend on the batch around it.  1 <= B <= 65535, 1 <= Nh, Fh <= 2^24, 1 <= max_voxels <= 2^24, voxel > 0,
+ * contact_thr >= 0, every object >= 1 face: AB_EINVAL otherwise (the tables' contents are trusted; indices are clamped into their mesh).
+ * Like the three mesh entry points above, this one is not captured in a hipGraph anywhere in this project (DESIGN.md sections 19, 23, 24):
+ * the evaluator is fed outside the replayed graphs.                                                                                      */
+#define AB_IA_VERTS 1
+#define AB_IA_VOLUME 2
+#define AB_IA_ROW 8            /* floats per sample row: */
+#define AB_IA_PEN_MAX 0
+#define AB_IA_PEN_MEAN 1
+#define AB_IA_MIN_DIST 2
+#define AB_IA_INSIDE_FRAC 3
+#define AB_IA_CONTACT 4
+#define AB_IA_VOL 5            /* m^3; slots 6, 7 reserved (NaN) */
+long ab_interaction_workspace(int B, int Nh, int max_voxels);
+int ab_interaction(const float* hand_verts, const int32_t* hand_faces, int Nh, int Fh, float hand_orient, const float* obj_verts,
+                   const int32_t* obj_faces, const int32_t* vert_off, const int32_t* face_off, const float* obj_orient, int n_obj,
+                   const int64_t* obj_row, const float* rot, const float* tsl, int B, float contact_thr, float voxel, int max_voxels, int flags,
+                   float* rows, int32_t* counts, float* sdf, float* wind, void* workspace, void* stream);
+
 /* ---- Argument contracts of the dispatcher ops (torch.ops.artiboost_hip.*, libartiboost_torch.so) ------------------------------------------
  * The C entry points above take raw pointers and trust their caller.  Their PyTorch-dispatcher form (ops that "validate
  * with TORCH_CHECK") is generated from this header by artiboost_amd/gen_torch_ops.py and checks, before the C call, for EVERY op:
@@ -878,6 +926,7 @@ int ab_mesh_metrics(const float* pred, const float* targ, const float* root, int
  * @check ab_chamfer_rigid: can >= B*N*3; rot g_rot >= B*9; tsl root g_tsl >= B*3; targ >= B*M*3; corners_vis >= B*8; loss >= 1; dist_xy idx_xy >= B*N; dist_yx idx_yx >= B*M; bytes workspace >= ab_chamfer_rigid_workspace(B,N,M)
  * @check ab_procrustes_loss: pred targ aligned g_pred >= B*n*3; root >= B*3; sample_loss >= B; loss >= 1
  * @check ab_mesh_metrics: pred >= B*N*3; targ >= B*M*3; root >= B*3; thresholds_host >= T; rows >= B*AB_MM_ROW; counts >= B*T*4; d_pg pa_d_pg >= B*N; d_gp pa_d_gp >= B*M; bytes workspace >= ab_mesh_metrics_workspace(B,N,M)
+ * @check ab_interaction: hand_verts >= B*Nh*3; hand_faces >= Fh*3; vert_off face_off >= n_obj+1; obj_verts >= 3; obj_faces >= 3; obj_orient >= n_obj; obj_row >= B; rot >= B*9; tsl >= B*3; rows >= B*AB_IA_ROW; counts >= B*4; sdf wind >= B*Nh; bytes workspace >= ab_interaction_workspace(B,Nh,max_voxels)
  */
 
 #ifdef __cplusplus
