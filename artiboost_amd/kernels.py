@@ -1032,6 +1032,72 @@ def _f32_of(op, what, t, numel):
     return L.ptr(t)
 
 
+def mspd(can, obj_transf, obj_idx, sym_R, sym_t, sym_count, cam_intr, pred_R=None, pred_t=None, pred_pts=None, out=None):
+    """ab_mspd (eager only): per-sample maximum symmetry-aware projection distance in pixels, min over the object's TRUE symmetry set of the
+    max over the points of || proj(pred) - proj(sym(gt)) ||.  The arguments of `mssd` (same table, same sym_count semantics) plus cam_intr
+    [B,3,3]; no centre.  A point at or behind the camera (Z <= 0) in either pose makes the sample +inf.  -> mspd [B] f32 (`out` when given)."""
+    B, V = can.shape[0], can.shape[1]
+    n_obj, Kmax = sym_R.shape[0], sym_R.shape[1]
+    if obj_idx.dtype != torch.int64 or sym_count.dtype != torch.int32:
+        raise ValueError(f"mspd: obj_idx must be int64 and sym_count int32, got {obj_idx.dtype} / {sym_count.dtype}")
+    if (pred_pts is None) == (pred_R is None) or (pred_R is None) != (pred_t is None):
+        raise ValueError("mspd: pass either pred_R and pred_t (rigid mode) or pred_pts (points mode)")
+    for t, numel, what in ((can, B * V * 3, "can"), (obj_transf, B * 16, "obj_transf"), (obj_idx, B, "obj_idx"), (sym_R, n_obj * Kmax * 9, "sym_R"),
+                           (sym_t, n_obj * Kmax * 3, "sym_t"), (sym_count, n_obj, "sym_count"), (pred_R, B * 9, "pred_R"), (pred_t, B * 3, "pred_t"),
+                           (pred_pts, B * V * 3, "pred_pts"), (cam_intr, B * 9, "cam_intr")):
+        if t is not None and (t.numel() != numel or (t.dtype != torch.float32 and what not in ("obj_idx", "sym_count"))):
+            raise ValueError(f"mspd: {what} must hold {numel} elements (fp32 but for the indices), got {t.dtype} {tuple(t.shape)}")
+    if out is None:
+        out = torch.empty((B,), dtype=torch.float32, device=can.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B,):
+        raise ValueError(f"mspd: out must be fp32 [{B}]")
+    ins = [L.ptr(t) for t in (can, obj_transf, obj_idx, sym_R, sym_t, sym_count, pred_R, pred_t, pred_pts, cam_intr)]
+    ws = _workspace(L.lib().ab_mspd_workspace(L.i(B), L.i(Kmax), L.i(V)), can.device)
+    L.check(L.lib().ab_mspd(*ins[:6], L.i(n_obj), L.i(Kmax), *ins[6:], L.i(B), L.i(V), L.ptr(out), L.ptr(ws), L.stream()), "ab_mspd")
+    return out
+
+
+VSD_MAX_TAUS = 16                               # AB_VSD_MAX_TAUS
+VSD_NEAR, VSD_RANGE = 0.01, 1 << 22             # AB_VSD_NEAR (metres), AB_VSD_RANGE (1/256 px)
+
+
+def vsd(obj_verts, obj_faces, vert_off, face_off, max_obj_verts, rows, rot_est, tsl_est, rot_gt, tsl_gt, cam_intr, W, H, delta, taus, diameter,
+        normalized_by_diameter=True, depth_test=None, occ_verts=None, occ_faces=None, want_depth=False):
+    """ab_vsd (eager only): Visible Surface Discrepancy of a batch, the three depth images kept in LDS.  The packed object table of
+    `interaction` (obj_verts [*,3] fp32, obj_faces int32 [*,3] local indices, vert_off / face_off int32 [n_obj+1]; max_obj_verts: the largest
+    vertex count, a host number), rows int64 [B]; rot_est / rot_gt [B,3,3], tsl_est / tsl_gt [B,3], cam_intr [B,3,3] fp32; depth_test
+    [B,H,W] fp32 or None (no measurement anywhere); the occluder occ_verts [B,Nv,3] (camera frame) with occ_faces int32 [Nf,3], or neither;
+    delta and taus (up to 16 host numbers) and diameter fp32 [n_obj], all in the unit of the meshes.  -> dict: counts int32 [B,2+T]
+    (union, complement, cost per tau), err [B,T] fp32 and, with want_depth, depth [B,3,H,W] (est, gt, test)."""
+    B, n_obj = rows.shape[0], vert_off.numel() - 1
+    for what, t, dt, numel in (("obj_faces", obj_faces, torch.int32, None), ("vert_off", vert_off, torch.int32, n_obj + 1),
+                               ("face_off", face_off, torch.int32, n_obj + 1), ("rows", rows, torch.int64, B), ("obj_verts", obj_verts, torch.float32, None)):
+        if t.dtype != dt or (t.numel() != numel if numel is not None else t.numel() < 3):
+            raise ValueError(f"vsd: {what} must be {dt} with {numel if numel is not None else 'at least 3'} elements, got {t.dtype} {tuple(t.shape)}")
+    if (occ_verts is None) != (occ_faces is None):
+        raise ValueError("vsd: pass occ_verts and occ_faces together, or neither")
+    Nv, Nf = (occ_verts.shape[1], occ_faces.shape[0]) if occ_verts is not None else (0, 0)
+    if occ_faces is not None and (occ_faces.dtype != torch.int32 or occ_faces.numel() != Nf * 3):
+        raise ValueError(f"vsd: occ_faces must be int32 [Nf,3], got {occ_faces.dtype} {tuple(occ_faces.shape)}")
+    ins = [_f32_of("vsd", w, t, n) for w, t, n in (("rot_est", rot_est, B * 9), ("tsl_est", tsl_est, B * 3), ("rot_gt", rot_gt, B * 9), ("tsl_gt", tsl_gt, B * 3),
+                                                   ("cam_intr", cam_intr, B * 9))]
+    dtest = None if depth_test is None else _f32_of("vsd", "depth_test", depth_test, B * H * W)
+    occ = None if occ_verts is None else _f32_of("vsd", "occ_verts", occ_verts, B * Nv * 3)
+    diam = _f32_of("vsd", "diameter", diameter, n_obj)
+    tau = torch.tensor([float(t) for t in taus], dtype=torch.float32)
+    T, dev = tau.numel(), rows.device
+    if not 1 <= T <= VSD_MAX_TAUS:
+        raise ValueError(f"vsd: 1 to {VSD_MAX_TAUS} taus, got {T}")
+    o = {"counts": torch.empty((B, 2 + T), dtype=torch.int32, device=dev), "err": torch.empty((B, T), dtype=torch.float32, device=dev)}
+    if want_depth:
+        o["depth"] = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+    ws = _workspace(L.lib().ab_vsd_workspace(L.i(B), L.i(max_obj_verts), L.i(Nv), L.i(W), L.i(H), L.i(T)), dev)
+    L.check(L.lib().ab_vsd(L.ptr(obj_verts), L.ptr(obj_faces), L.ptr(vert_off), L.ptr(face_off), L.i(n_obj), L.i(max_obj_verts), L.ptr(rows), *ins,
+                           L.i(B), L.i(W), L.i(H), dtest, occ, L.ptr(occ_faces), L.i(Nv), L.i(Nf), L.f(delta), tau, L.i(T), diam,
+                           L.i(1 if normalized_by_diameter else 0), o["counts"], o["err"], o.get("depth"), L.ptr(ws), L.stream()), "ab_vsd")
+    return o
+
+
 def chamfer_rigid(can, rot, tsl, targ, root, corners_vis, want_grad=True, want_dist=False):
     """ab_chamfer_rigid (eager only, never under graph capture): the two-way squared nearest-neighbour distance between keep (R can + t) and
     keep (targ + root), keep = any(corners_vis != 0) formed in the kernel.  can [B,N,3], rot [B,3,3] / [B,9], tsl [B,(1,)3], targ [B,M,3],

@@ -556,7 +556,8 @@ class _MSSDBase:
 
 @METRIC.register_module
 class AR(Metric):
-    """anakin/metrics/bopAR.py:15-61 with USE_MSSD (VSD / MSPD raise NotImplementedError in the reference too)."""
+    """anakin/metrics/bopAR.py:15-61 with USE_MSSD: a mean MSSD in millimetres.  USE_VSD / USE_MSPD raise NotImplementedError, as in the
+    reference, whose VSD and MSPD are stubs; the BOP average recall over VSD, MSSD and MSPD is the metric type BOPRecall (below)."""
 
     def __init__(self, **cfg):
         if cfg.get("USE_VSD", False) or cfg.get("USE_MSPD", False):
@@ -1179,3 +1180,366 @@ class InteractionMetric(Metric):
 
     def __str__(self):
         return " | ".join(f"{k}: {v:6.4f}" for k, v in self.get_measures().items())
+
+
+# ============================================================================ BOP average recall
+def calc_pts_diameter(pts, block=512):
+    """The largest distance between two of the points (bop_toolkit's misc.calc_pts_diameter), float64 on the host, in blocks of rows."""
+    p = np.asarray(pts, np.float64).reshape(-1, 3)
+    best = -1.0
+    for s in range(0, len(p), block):
+        d = p[s:s + block, None, :] - p[None, s:, :]
+        best = max(best, float((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]).max()))
+    return float(np.sqrt(best))
+
+
+def _vsd_snap(P, K):
+    """Stage A of ab_vsd on camera points P [V,3] fp32 with K [9] fp32 -> (snapped x, snapped y as python ints, Z float64 of the fp32 value, valid)."""
+    from .kernels import VSD_NEAR, VSD_RANGE
+    f32 = np.float32
+    X, Y, Z = P[:, 0], P[:, 1], P[:, 2]
+    with np.errstate(all="ignore"):
+        su = np.floor((K[0] * (X / Z) + K[2]) * f32(256.0) + f32(0.5))
+        sv = np.floor((K[4] * (Y / Z) + K[5]) * f32(256.0) + f32(0.5))
+        valid = (Z > f32(VSD_NEAR)) & (np.abs(su) <= f32(VSD_RANGE)) & (np.abs(sv) <= f32(VSD_RANGE))
+    assert su.dtype == f32 and Z.dtype == f32
+    return np.where(valid, su, 0).astype(np.int64).tolist(), np.where(valid, sv, 0).astype(np.int64).tolist(), Z.astype(np.float64).tolist(), valid.tolist()
+
+
+def _vsd_pose(R, t, v):
+    """((r0 x + r1 y) + r2 z) + t per row, fp32."""
+    x, y, z = v[:, 0], v[:, 1], v[:, 2]
+    return np.stack([((R[i, 0] * x + R[i, 1] * y) + R[i, 2] * z) + t[i] for i in range(3)], 1)
+
+
+def _vsd_raster(zbufs, snapped, faces, W, H):
+    """Stages B and C of ab_vsd: every face of `faces` into each [H,W] fp32 z-buffer of `zbufs` (empty = +inf), one pixel block per face."""
+    sx, sy, Z, ok = snapped
+    for a, b, c in np.asarray(faces).reshape(-1, 3).tolist():
+        if not (ok[a] and ok[b] and ok[c]):
+            continue
+        area = (sx[b] - sx[a]) * (sy[c] - sy[a]) - (sy[b] - sy[a]) * (sx[c] - sx[a])
+        if area == 0:
+            continue
+        if area < 0:
+            b, c, area = c, b, -area
+        xs3, ys3 = (sx[a], sx[b], sx[c]), (sy[a], sy[b], sy[c])
+        x0, x1 = max((min(xs3) + 255) >> 8, 0), min(max(xs3) >> 8, W - 1)
+        y0, y1 = max((min(ys3) + 255) >> 8, 0), min(max(ys3) >> 8, H - 1)
+        if x0 > x1 or y0 > y1:
+            continue
+        px, py = np.arange(x0, x1 + 1, dtype=np.int64)[None, :] * 256, np.arange(y0, y1 + 1, dtype=np.int64)[:, None] * 256
+        cov, es = True, []
+        for p, q in ((b, c), (c, a), (a, b)):
+            dx, dy = sx[q] - sx[p], sy[q] - sy[p]
+            e = dx * (py - sy[p]) - dy * (px - sx[p])
+            cov = cov & ((e > 0) | ((e == 0) & (dy > 0 or (dy == 0 and dx < 0))))
+            es.append(e)
+        if not cov.any():
+            continue
+        A = np.float64(area)
+        with np.errstate(all="ignore"):
+            l0, l1, l2 = es[0].astype(np.float64) / A, es[1].astype(np.float64) / A, es[2].astype(np.float64) / A
+            z = np.where(cov, (1.0 / ((l0 / Z[a] + l1 / Z[b]) + l2 / Z[c])).astype(np.float32), np.float32(np.inf))
+        for zb in zbufs:
+            sub = zb[y0:y1 + 1, x0:x1 + 1]
+            np.minimum(sub, z, out=sub)
+
+
+def _vsd_stage_d(de, dg, dt, K, delta, taus, diam, normalized):
+    """Stage D of ab_vsd on three fp32 depth images -> [union, complement, cost per tau] as python ints."""
+    f32, f64 = np.float32, np.float64
+    H, W = de.shape
+    xs, ys = np.meshgrid(np.arange(W), np.arange(H))
+    pX, pY = (xs - f64(K[2])) / f64(K[0]), (ys - f64(K[5])) / f64(K[4])
+    dist = lambda d: np.sqrt((pX * d) ** 2 + (pY * d) ** 2 + d.astype(f64) ** 2)      # noqa: E731
+    Le, Lg, Lt = dist(de), dist(dg), dist(dt)
+    vis = lambda L: ((L.astype(f32) - Lt.astype(f32) <= f32(delta)) | (Lt == 0)) & (L > 0)      # noqa: E731
+    vg = vis(Lg)
+    ve = vis(Le) | (vg & (Le > 0))
+    inter, uni = vg & ve, vg | ve
+    dd = np.abs(Lg[inter] - Le[inter])
+    if normalized:
+        dd = dd / f64(diam)
+    n_uni = int(uni.sum())
+    return [n_uni, n_uni - int(inter.sum())] + [int((dd >= f64(f32(t))).sum()) for t in taus]
+
+
+def vsd_values_numpy(obj_verts, obj_faces, vert_off, face_off, max_obj_verts, rows, rot_est, tsl_est, rot_gt, tsl_gt, cam_intr, W, H, delta, taus, diameter,
+                     normalized_by_diameter=True, depth_test=None, occ_verts=None, occ_faces=None, want_depth=False):
+    """The stages of ab_vsd (include/artiboost_hip.h) in numpy -- A in fp32 in the stated order, B in integers, C and D in float64 --: the route
+    of CPU tensors.  Same arguments (CPU tensors or arrays) and the same dict as kernels.vsd, as CPU tensors."""
+    def n(a, dt=None):
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        return a.astype(dt) if dt is not None else a
+    f32 = np.float32
+    verts, faces, vo, fo = n(obj_verts, f32).reshape(-1, 3), n(obj_faces).reshape(-1, 3), n(vert_off).tolist(), n(face_off).tolist()
+    rows = n(rows).reshape(-1).tolist()
+    B, n_obj, T = len(rows), len(vo) - 1, len(taus)
+    Re, te, Rg, tg, K = n(rot_est, f32).reshape(B, 3, 3), n(tsl_est, f32).reshape(B, 3), n(rot_gt, f32).reshape(B, 3, 3), n(tsl_gt, f32).reshape(B, 3), n(cam_intr, f32).reshape(B, 9)
+    diam = n(diameter, f32).reshape(-1)
+    dtest = None if depth_test is None else n(depth_test, f32).reshape(B, H, W)
+    occ = None if occ_verts is None else n(occ_verts, f32).reshape(B, -1, 3)
+    of = None if occ_faces is None else n(occ_faces).reshape(-1, 3)
+    counts, err = np.zeros((B, 2 + T), np.int32), np.ones((B, T), f32)
+    depth = np.zeros((B, 3, H, W), f32)
+    for b in range(B):
+        r = min(max(int(rows[b]), 0), n_obj - 1)
+        nv = min(vo[r + 1] - vo[r], int(max_obj_verts))
+        v = verts[vo[r]:vo[r] + nv]
+        f = faces[fo[r]:fo[r + 1]]
+        f = f[((f >= 0) & (f < nv)).all(1)]
+        zb = np.full((3, H, W), np.inf, f32)
+        _vsd_raster([zb[0]], _vsd_snap(_vsd_pose(Re[b], te[b], v), K[b]), f, W, H)
+        _vsd_raster([zb[1], zb[2]] if occ is not None else [zb[1]], _vsd_snap(_vsd_pose(Rg[b], tg[b], v), K[b]), f, W, H)
+        zb[~np.isfinite(zb)] = 0.0
+        dm = dtest[b] if dtest is not None else np.zeros((H, W), f32)
+        if occ is not None:
+            zt = np.full((H, W), np.inf, f32)
+            _vsd_raster([zt], _vsd_snap(occ[b], K[b]), of[((of >= 0) & (of < occ.shape[1])).all(1)], W, H)
+            zt[~np.isfinite(zt)] = 0.0
+            dt = np.where((zb[2] > 0) & ((zt == 0) | (zb[2] < zt)), zb[2], zt)
+            dt = np.where((dm > 0) & ((dt == 0) | (dm < dt)), dm, dt)
+        else:
+            dt = dm
+        depth[b, 0], depth[b, 1], depth[b, 2] = zb[0], zb[1], dt
+        c = _vsd_stage_d(zb[0], zb[1], dt, K[b], delta, taus, diam[r], normalized_by_diameter)
+        counts[b] = c
+        if c[0] > 0:
+            err[b] = (np.asarray(c[2:], np.float64) + c[1]) / np.float64(c[0])
+    out = {"counts": torch.from_numpy(counts), "err": torch.from_numpy(err)}
+    if want_depth:
+        out["depth"] = torch.from_numpy(depth)
+    return out
+
+
+def mspd_values_torch(can, obj_transf, obj_idx, sym_R, sym_t, sym_count, cam_intr, pred_R=None, pred_t=None, pred_pts=None):
+    """The definition of ab_mspd as torch ops in `can`'s dtype (the route of CPU tensors; in float64 the tests' reference): per sample the
+    minimum over the object's TRUE symmetry set of the maximum projection distance in pixels; +inf when a point has Z <= 0 in either pose."""
+    dt, dev = can.dtype, can.device
+    B, n_obj = can.shape[0], sym_R.shape[0]
+    t = lambda a: a.detach().to(device=dev, dtype=dt)      # noqa: E731
+    T, K = t(obj_transf).reshape(B, 4, 4), t(cam_intr).reshape(B, 3, 3)
+    SR, St = t(sym_R).reshape(n_obj, -1, 3, 3), t(sym_t).reshape(n_obj, -1, 3)
+    cnt, oi = sym_count.cpu().tolist(), (obj_idx.cpu() - 1).clamp(0, n_obj - 1).tolist()
+
+    def proj(P, k):
+        return torch.stack([k[0, 0] * P[..., 0] / P[..., 2] + k[0, 2], k[1, 1] * P[..., 1] / P[..., 2] + k[1, 2]], -1)
+    out = torch.full((B,), float("inf"), dtype=dt, device=dev)
+    for b in range(B):
+        c = min(max(int(cnt[oi[b]]), 0), SR.shape[1])
+        if c < 1:
+            continue
+        pred = t(pred_pts)[b] if pred_pts is not None else can[b] @ t(pred_R).reshape(B, 3, 3)[b].T + t(pred_t).reshape(B, 3)[b]
+        Rk = T[b, :3, :3] @ SR[oi[b], :c]                                                  # [c,3,3]
+        tk = St[oi[b], :c] @ T[b, :3, :3].T + T[b, :3, 3]                                  # [c,3]
+        gt = torch.einsum("kij,vj->kvi", Rk, can[b]) + tk[:, None]
+        if bool((pred[:, 2] <= 0).any()):
+            continue
+        d = torch.norm(proj(gt, K[b]) - proj(pred, K[b])[None], dim=-1)
+        d = torch.where(gt[..., 2] > 0, d, torch.full_like(d, float("inf")))
+        out[b] = d.max(1)[0].min()
+    return out
+
+
+BOP19_STEPS = np.arange(0.05, 0.51, 0.05)      # bop_toolkit's BOP19 settings: the VSD taus and every measure's ten correctness thresholds
+
+
+@METRIC.register_module
+class BOPRecall(Metric):
+    """The BOP average recall of an object-pose prediction, AR = mean(AR_VSD, AR_MSSD, AR_MSPD) (Hodan et al., BOP Challenge 2019/2020): a
+    sample is a hit of a measure at a threshold when its error is strictly below it, a measure's recall is the mean hit rate over its
+    thresholds (and, for VSD, over the taus).  Defaults are the BOP19 protocol, each overridable:
+      VSD    VSD_DELTA_MM 15, VSD_TAUS 0.05 .. 0.5 (normalised by the diameter: VSD_NORMALIZED), VSD_THRESHOLDS 0.05 .. 0.5
+      MSSD   MSSD_THRESHOLDS 0.05 .. 0.5 x diameter
+      MSPD   MSPD_THRESHOLDS 5 r .. 50 r pixels, r = IMAGE_SIZE[0] / 640
+    The prediction is preds[ROT_KEY] / preds[TSL_KEY] (the rule of corners_3d_abs and MSSD), the annotation targs[obj_transf], the camera
+    targs[cam_intr], images of DATA_PRESET.IMAGE_SIZE.  The symmetry table and MSSD are _MSSDBase's (MODEL_INFO / MODEL_INFO_PATH,
+    MAX_SYM_DISC_STEP, MSSD_USE_CORNERS), MSPD runs over the same points; the meshes VSD renders are an ObjectMeshTable: OBJ_MESHES
+    {SOURCE: assets, DATASET: HO3D} or set_obj_meshes(table).  Diameters: MODEL_INFO[i]["diameter"] (mm) when present, otherwise the largest
+    distance between two vertices of the table's mesh (bop_toolkit's calc_pts_diameter), computed once on the host.
+    DEPTH_TEST: `none` (no measurement: the pure est-against-gt discrepancy), `key` (targs["depth"] [B,H,W] in metres) or `hand` (the
+    annotated hand targs[hand_verts_3d] + root_joint occludes, with the table's hand faces).
+    HIP tensors: ab_vsd, ab_mssd and ab_mspd, once per batch through the evaluator's memo; feed_device reads nothing back: the hits are
+    integer index_add_ into a device tensor [n_obj, 3, T, 10] (MSSD and MSPD use tau slot 0).  CPU tensors: vsd_values_numpy,
+    the torch expression of MSSD and mspd_values_torch.  A batch that lacks a key is skipped and logged once.
+    get_measures: AR, AR_VSD, AR_MSSD, AR_MSPD over all samples, `{i}.ar` per object id, and recall_vsd / recall_mssd / recall_mspd, the
+    recall per threshold, as lists."""
+
+    def __init__(self, **cfg):
+        self.base = _MSSDBase(**cfg)
+        self.n_obj = self.base.n_obj
+        self.rot_key, self.tsl_key = cfg.get("ROT_KEY", "box_rot_rotmat"), cfg.get("TSL_KEY", "boxroot_3d_abs")
+        self.image_size = [int(s) for s in cfg["DATA_PRESET"]["IMAGE_SIZE"]]
+        self.delta = float(cfg.get("VSD_DELTA_MM", 15.0)) / 1000.0
+        self.taus = [float(t) for t in cfg.get("VSD_TAUS", BOP19_STEPS)]
+        self.normalized = bool(cfg.get("VSD_NORMALIZED", True))
+        r = self.image_size[0] / 640.0
+        self.thresholds = np.stack([np.asarray(cfg.get("VSD_THRESHOLDS", BOP19_STEPS), np.float64), np.asarray(cfg.get("MSSD_THRESHOLDS", BOP19_STEPS), np.float64),
+                                    np.asarray(cfg.get("MSPD_THRESHOLDS", [r * k for k in range(5, 51, 5)]), np.float64)])      # [3, n_thr]
+        self.depth_test = str(cfg.get("DEPTH_TEST", "none"))
+        from .kernels import VSD_MAX_TAUS
+        if self.depth_test not in ("none", "key", "hand") or not 1 <= len(self.taus) <= VSD_MAX_TAUS or self.delta < 0:
+            raise ValueError("BOPRecall: DEPTH_TEST is one of none / key / hand, 1 to 16 VSD_TAUS, VSD_DELTA_MM >= 0")
+        import json
+        info = cfg.get("MODEL_INFO") or json.load(open(cfg["MODEL_INFO_PATH"], "r"))
+        self._info_diam = [info[str(i)].get("diameter") for i in range(1, self.n_obj + 1)]
+        self.table, self._diam, self._tens = None, None, {}
+        src = cfg.get("OBJ_MESHES")
+        if src:
+            if str(src.get("SOURCE", "assets")) != "assets":
+                raise ValueError(f"BOPRecall: OBJ_MESHES.SOURCE must be 'assets' (or call set_obj_meshes), got {src.get('SOURCE')!r}")
+            from .assets import SceneAssets
+            self.set_obj_meshes(ObjectMeshTable.from_assets(SceneAssets(src.get("DATASET", "HO3D"), seed=1)))
+        self._skipped = set()
+        self.reset()
+
+    def set_obj_meshes(self, table):
+        if table.hand_faces is None and self.depth_test == "hand":
+            from .hpregnet import load_hand_model
+            table.set_hand(load_hand_model("assets/mano_v1_2"))
+        self.table = table
+        d = np.full(self.n_obj, np.nan)                                               # metres, by 1-based object id
+        for i in range(1, self.n_obj + 1):
+            if self._info_diam[i - 1] is not None:
+                d[i - 1] = float(self._info_diam[i - 1]) / 1000.0
+            elif i in table.row_of:
+                r = table.row_of[i]
+                d[i - 1] = calc_pts_diameter(table.verts[table.vert_off[r]:table.vert_off[r + 1]])
+        self._diam = d
+        self._row_diam = np.asarray([d[i - 1] if 1 <= i <= self.n_obj else np.nan for i in table.obj_ids], np.float32)
+        self.max_obj_verts = int((table.vert_off[1:] - table.vert_off[:-1]).max())
+        self._tens = {}
+        return self
+
+    def reset(self):
+        self._hits = self._cnt = None
+        self.count = 0
+
+    def _on(self, dev):
+        """The metric's own small tensors on `dev`, uploaded once (the mesh table keeps its own cache, without the hand faces when it has none)."""
+        key = str(dev)
+        if key not in self._tens:
+            tb, t = self.table, lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+            lut = torch.from_numpy(tb._lut).to(dev)
+            self._tens[key] = dict(obj_verts=t(tb.verts), obj_faces=t(tb.faces), vert_off=t(tb.vert_off), face_off=t(tb.face_off), lut=lut,
+                                   hand_faces=None if tb.hand_faces is None else t(tb.hand_faces), row_diam=t(self._row_diam), diam=t(self._diam),
+                                   thr=t(self.thresholds))
+        return self._tens[key]
+
+    def _missing(self, preds, targs):
+        need_t = [Queries.OBJ_IDX, Queries.OBJ_TRANSF, Queries.CAM_INTR, Queries.CORNERS_CAN if self.base.mssd_use_corners else "obj_verts_can"]
+        need_p = [self.rot_key, self.tsl_key] + (["corners_3d_abs"] if self.base.mssd_use_corners else [])
+        need_p += ["joints_3d_abs"] if self.base.center_idx is not None else []
+        need_t += [Queries.ROOT_JOINT] if self.base.center_idx is not None else []
+        need_t += {"none": [], "key": ["depth"], "hand": ["hand_verts_3d", Queries.ROOT_JOINT]}[self.depth_test]
+        for k in need_p:
+            if preds.get(k) is None:
+                return k
+        for k in need_t:
+            if targs.get(k) is None:
+                return k
+        return None
+
+    def values(self, preds, targs):
+        """One batch -> dict: obj_idx int64 [B] (1-based), vsd_counts int32 [B,2+T], mssd [B] (metres), mspd [B] (pixels), on the predictions' device."""
+        if self.table is None:
+            raise RuntimeError("BOPRecall: no object meshes (OBJ_MESHES in the config, or set_obj_meshes)")
+        from . import kernels as K
+        rot = preds[self.rot_key].detach()
+        dev, B = rot.device, rot.shape[0]
+        tn = self._on(dev)
+        hip = rot.is_cuda
+        dt = torch.float32 if hip else rot.dtype
+        f = lambda x: x.detach().to(device=dev, dtype=torch.float32).contiguous()      # noqa: E731
+        obj_idx = targs[Queries.OBJ_IDX].to(dev).long().reshape(-1)
+        lut = tn["lut"]
+        rows = torch.where((obj_idx >= 0) & (obj_idx < lut.numel()), lut[obj_idx.clamp(0, lut.numel() - 1)], torch.full_like(obj_idx, -1))
+        T = targs[Queries.OBJ_TRANSF].to(dev)
+        W, H = self.image_size
+        kw = dict(depth_test=None, occ_verts=None, occ_faces=None)
+        if self.depth_test == "key":
+            kw["depth_test"] = f(targs["depth"]).reshape(B, H, W)
+        elif self.depth_test == "hand":
+            kw["occ_verts"] = f(targs["hand_verts_3d"].to(dev) + targs[Queries.ROOT_JOINT].to(dev).unsqueeze(1))
+            kw["occ_faces"] = tn["hand_faces"]
+        fn = K.vsd if hip else vsd_values_numpy
+        v = fn(tn["obj_verts"], tn["obj_faces"], tn["vert_off"], tn["face_off"], self.max_obj_verts, rows.contiguous(), f(rot).reshape(B, 3, 3),
+               f(preds[self.tsl_key]).reshape(B, 3), f(T[:, :3, :3]), f(T[:, :3, 3]), f(targs[Queries.CAM_INTR]).reshape(B, 3, 3), W, H, self.delta, self.taus,
+               tn["row_diam"], normalized_by_diameter=self.normalized, **kw)
+        _, mssd = self.base.values(preds, targs)
+        can = targs[Queries.CORNERS_CAN if self.base.mssd_use_corners else "obj_verts_can"].to(dev)
+        if self.base.mssd_use_corners:
+            mode = dict(pred_pts=preds["corners_3d_abs"].detach())
+        else:
+            mode = dict(pred_R=rot.reshape(B, 3, 3), pred_t=preds[self.tsl_key].detach().reshape(B, 3))
+        g = (lambda x: f(x)) if hip else (lambda x: x.detach().to(dt))
+        args = (g(can), g(T), obj_idx.contiguous(), self.base.R, self.base.t, self.base.sym_count, g(targs[Queries.CAM_INTR].to(dev)))
+        mspd = (K.mspd if hip else mspd_values_torch)(*args, **{k: g(x) for k, x in mode.items()})
+        return dict(obj_idx=obj_idx, vsd_counts=v["counts"].to(dev), mssd=mssd, mspd=mspd)
+
+    def hits(self, val, dev):
+        """int64 [B, 3, T, n_thr] of one batch's values: strict `<`, in float64.  The VSD error is formed from the integer counts in float64, as
+        bop_toolkit forms it, so a sample exactly on a threshold falls where it falls there."""
+        tn = self._on(dev)
+        thr = tn["thr"]                                                                  # [3, n_thr] float64
+        c = val["vsd_counts"].to(torch.float64)
+        uni = c[:, 0:1]
+        e = torch.where(uni > 0, (c[:, 2:] + c[:, 1:2]) / uni.clamp_min(1.0), torch.ones_like(c[:, 2:]))      # [B,T]
+        B, T, n = e.shape[0], e.shape[1], thr.shape[1]
+        out = torch.zeros((B, 3, T, n), dtype=torch.int64, device=dev)
+        out[:, 0] = (e[:, :, None] < thr[0][None, None, :]).to(torch.int64)
+        oi = (val["obj_idx"] - 1).clamp(0, self.n_obj - 1)
+        diam = tn["diam"][oi]                                                            # NaN for an object without a diameter: never a hit
+        out[:, 1, 0] = (val["mssd"].to(torch.float64)[:, None] < thr[1][None, :] * diam[:, None]).to(torch.int64)
+        out[:, 2, 0] = (val["mspd"].to(torch.float64)[:, None] < thr[2][None, :]).to(torch.int64)
+        return out, oi
+
+    def feed_device(self, preds, targs, memo=None, **kwargs):
+        miss = self._missing(preds, targs)
+        if miss is not None:
+            if miss not in self._skipped:
+                self._skipped.add(miss)
+                import logging
+                logging.getLogger("anakin").warning(f"BOPRecall: batch without '{miss}'; such batches are skipped")
+            return []
+        mk = ("bop", id(self), id(self.table))
+        val = memo.get(mk) if memo is not None else None
+        if val is None:
+            val = self.values(preds, targs)
+            if memo is not None:
+                memo[mk] = val
+        dev = val["mssd"].device
+        h, oi = self.hits(val, dev)
+        if self._hits is None or self._hits.device != dev:
+            self._hits = torch.zeros((self.n_obj,) + tuple(h.shape[1:]), dtype=torch.int64, device=dev)
+            self._cnt = torch.zeros(self.n_obj, dtype=torch.int64, device=dev)
+        self._hits.index_add_(0, oi, h)
+        self._cnt.index_add_(0, oi, torch.ones_like(oi))
+        return [torch.full((1,), h.shape[0], dtype=torch.int64, device=dev)]
+
+    def feed_host(self, arrays, **kwargs):
+        for a in arrays:
+            self.count += int(a[0])
+
+    def feed(self, preds, targs, **kwargs):
+        self.feed_host([t.cpu().numpy() for t in self.feed_device(preds, targs)])
+
+    def get_measures(self, **kwargs):
+        if self._hits is None:
+            return {}
+        h, c = self._hits.cpu().numpy().astype(np.float64), self._cnt.cpu().numpy().astype(np.float64)
+        n, T = c.sum(), h.shape[2]
+        if n <= 0:
+            return {}
+        rec = [h[:, 0].sum(0).sum(0) / (n * T), h[:, 1, 0].sum(0) / n, h[:, 2, 0].sum(0) / n]      # per threshold
+        out = {"AR_VSD": float(rec[0].mean()), "AR_MSSD": float(rec[1].mean()), "AR_MSPD": float(rec[2].mean())}
+        out["AR"] = (out["AR_VSD"] + out["AR_MSSD"] + out["AR_MSPD"]) / 3.0
+        for i in np.nonzero(c)[0]:
+            out[f"{i + 1}.ar"] = float((h[i, 0].mean() + h[i, 1, 0].mean() + h[i, 2, 0].mean()) / (3.0 * c[i]))
+        out.update(recall_vsd=rec[0].tolist(), recall_mssd=rec[1].tolist(), recall_mspd=rec[2].tolist())
+        return out
+
+    def __str__(self):
+        m = self.get_measures() if self.count else {}
+        return " | ".join(f"{k}: {m[k]:6.4f}" for k in ("AR", "AR_VSD", "AR_MSSD", "AR_MSPD") if k in m)

@@ -850,6 +850,64 @@ int ab_interaction(const float* hand_verts, const int32_t* hand_faces, int Nh, i
                    const int64_t* obj_row, const float* rot, const float* tsl, int B, float contact_thr, float voxel, int max_voxels, int flags,
                    float* rows, int32_t* counts, float* sdf, float* wind, void* workspace, void* stream);
 
+/* ---- BOP pose errors of the evaluator, eager only (csrc/bop_recall.hip) -----------------------------------------------
+ * The two errors of bop_toolkit's pose_error.py that, with ab_mssd, make the BOP average recall: MSPD and VSD.
+ *
+ * ab_mspd: per sample b, with the symmetry set of ab_mssd (same table layout, same sym_count semantics, same clamping of obj_idx),
+ *   mspd[b] = min over k < sym_count of max over v < V of || proj(pred_v) - proj(R_gt (S_k.R can_v + S_k.t) + t_gt) ||      (pixels)
+ *   proj(X, Y, Z) = (fx X / Z + cx, fy Y / Z + cy) with cam_intr [B,9] row-major (fx, cx, fy, cy read from slots 0, 2, 4, 5; no skew).
+ * Rigid mode (pred_pts NULL): pred_v = pred_R[b] can_v + pred_t[b]; points mode (pred_pts [B,V,3], pred_R and pred_t NULL): read from
+ * memory.  A point whose camera-space Z is <= 0 in either pose makes the sample's error +inf (bop_toolkit divides by Z regardless and
+ * mirrors such a point through the principal point; here it is reported as what it is).  An empty set gives +inf.  fp32 throughout; squared
+ * distances are compared and ONE square root is taken at the end.  workspace: ab_mspd_workspace(B, Kmax, V) bytes.  No atomics: the bits are
+ * the same across calls and for a sample alone or inside a batch.  1 <= B <= 65535, V >= 1, n_obj >= 1, 1 <= Kmax <= 64 * 65535.
+ *
+ * ab_vsd: Visible Surface Discrepancy (pose_error.vsd, cost_type "step", visibility mode bop19) of a whole batch, fused: the three depth
+ * images live in LDS, one 32 x 32 tile at a time, and reach memory only through depth_out.
+ * The object is row clamp(rows[b], 0, n_obj - 1) of the packed table of ab_interaction (obj_verts [*,3], obj_faces int32 [*,3] with LOCAL
+ * indices, vert_off / face_off int32 [n_obj + 1]); max_obj_verts is the largest vertex count of the table (a mesh with more keeps its
+ * first max_obj_verts vertices; a face with an index outside its mesh is dropped).  rot_est / rot_gt [B,9], tsl_est / tsl_gt [B,3]: the
+ * estimated and the ground-truth pose; cam_intr [B,9]; depth_test [B,H,W] fp32 or NULL (all zero), 0 = no measurement; the occluder
+ * (both or neither): occ_verts [B,Nv,3] in the CAMERA frame, occ_faces int32 [Nf,3].  All lengths in one unit (the project's: metres):
+ * delta, diameter fp32 [n_obj] (per table row), taus_host: T <= AB_VSD_MAX_TAUS fp32 values in a HOST array read during the call.
+ * With an occluder, the test depth of a pixel is the nearest of the occluder, the object under the ground truth and depth_test where
+ * that is > 0 (what a depth sensor would have seen); without one it is depth_test as given.
+ * The stages are the contract that makes the result checkable bit for bit (restated in tests/bop_raster_ref.py):
+ *   A  fp32, this operation order, no FMA (the library is built with -ffp-contract=off):  camera point ((r0 x + r1 y) + r2 z) + t per row;
+ *      u = fx (X / Z) + cx, v = fy (Y / Z) + cy;  snapped to 1/256 px by floorf(u 256 + 0.5).  Pixel (x, y) is sampled AT (x, y) -- BOP's
+ *      convention (depth_im_to_dist_im_fast: pre_Xs = (x - cx) / fx) --, not at x + 1/2.  A triangle is dropped when a vertex has
+ *      Z <= AB_VSD_NEAR, when a snapped coordinate lies outside [-AB_VSD_RANGE, AB_VSD_RANGE] (with W, H <= 8192 every edge product stays
+ *      below 2^48), or when its area is zero.  No back-face culling; a clockwise triangle has its second and third vertex swapped.
+ *   B  integers: E0 = edge(v1, v2, p), E1 = edge(v2, v0, p), E2 = edge(v0, v1, p) in int64, edge(a, b, p) = (bx - ax)(py - ay) - (by - ay)(px - ax);
+ *      covered when all are >= 0 and every zero one belongs to a top or left edge (dy > 0, or dy == 0 and dx < 0): render.hip's rule.
+ *   C  float64, this order:  l_i = (double)E_i / (double)A, A = E0 + E1 + E2;  Z = 1 / ((l0 / Z0 + l1 / Z1) + l2 / Z2);  rounded to fp32; the
+ *      nearest surface wins by an unsigned minimum over the bit patterns (positive floats): order-independent, so the image is the same
+ *      on every call.  A pixel no triangle covers has depth 0.
+ *   D  float64 per pixel, the order of bop_toolkit:  pX = ((double)x - cx) / fx, pY likewise;  L = sqrt(((pX d)^2 + (pY d)^2) + d^2) for
+ *      each of the three depths d;  visible(L) = ((float)L - (float)L_test <= delta or L_test == 0) and L > 0;  vis_gt = visible(L_gt),
+ *      vis_est = visible(L_est) or (vis_gt and L_est > 0);  per tau: cost = |L_gt - L_est| (/ diameter when normalized_by_diameter) >= tau
+ *      over the intersection.
+ * counts int32 [B, 2 + T]: union pixels, complement pixels (union minus intersection), the cost count per tau.  err fp32 [B,T]:
+ * (cost_t + complement) / union formed in float64 and rounded, 1.0 where the union is empty.  depth_out [B,3,H,W] or NULL: the est, gt
+ * and test depth images.  workspace: ab_vsd_workspace(B, max_obj_verts, Nv, W, H, T) bytes (a 16-byte record per projected vertex, 2 + T
+ * partial counts per tile).  Three launches (vertex setup; one workgroup per (sample, tile); one workgroup per sample adding its tiles in
+ * turn).  The only atomics are the LDS minima of stage C; counts are integers added in a fixed order: two calls give the same bits and a
+ * sample does not depend on the batch around it.  1 <= B <= 65535, 1 <= W, H <= 8192, 1 <= T <= AB_VSD_MAX_TAUS, delta >= 0.
+ * Neither entry point is captured in a hipGraph anywhere in this project: the evaluator is fed outside the replayed graphs.              */
+#define AB_VSD_MAX_TAUS 16
+#define AB_VSD_NEAR 0.01f      /* metres */
+#define AB_VSD_RANGE 4194304   /* 2^22 snapped units = 16 384 px */
+long ab_mspd_workspace(int B, int Kmax, int V);
+int ab_mspd(const float* can, const float* obj_transf, const int64_t* obj_idx, const float* sym_R, const float* sym_t,
+            const int32_t* sym_count, int n_obj, int Kmax, const float* pred_R, const float* pred_t, const float* pred_pts,
+            const float* cam_intr, int B, int V, float* mspd, void* workspace, void* stream);
+long ab_vsd_workspace(int B, int max_obj_verts, int Nv, int W, int H, int T);
+int ab_vsd(const float* obj_verts, const int32_t* obj_faces, const int32_t* vert_off, const int32_t* face_off, int n_obj,
+           int max_obj_verts, const int64_t* rows, const float* rot_est, const float* tsl_est, const float* rot_gt, const float* tsl_gt,
+           const float* cam_intr, int B, int W, int H, const float* depth_test, const float* occ_verts, const int32_t* occ_faces, int Nv,
+           int Nf, float delta, const float* taus_host, int T, const float* diameter, int normalized_by_diameter, int32_t* counts,
+           float* err, float* depth_out, void* workspace, void* stream);
+
 /* ---- Argument contracts of the dispatcher ops (torch.ops.artiboost_hip.*, libartiboost_torch.so) ------------------------------------------
  * The C entry points above take raw pointers and trust their caller.  Their PyTorch-dispatcher form (ops that "validate
  * with TORCH_CHECK") is generated from this header by artiboost_amd/gen_torch_ops.py and checks, before the C call, for EVERY op:
@@ -927,6 +985,8 @@ int ab_interaction(const float* hand_verts, const int32_t* hand_faces, int Nh, i
  * @check ab_procrustes_loss: pred targ aligned g_pred >= B*n*3; root >= B*3; sample_loss >= B; loss >= 1
  * @check ab_mesh_metrics: pred >= B*N*3; targ >= B*M*3; root >= B*3; thresholds_host >= T; rows >= B*AB_MM_ROW; counts >= B*T*4; d_pg pa_d_pg >= B*N; d_gp pa_d_gp >= B*M; bytes workspace >= ab_mesh_metrics_workspace(B,N,M)
  * @check ab_interaction: hand_verts >= B*Nh*3; hand_faces >= Fh*3; vert_off face_off >= n_obj+1; obj_verts >= 3; obj_faces >= 3; obj_orient >= n_obj; obj_row >= B; rot >= B*9; tsl >= B*3; rows >= B*AB_IA_ROW; counts >= B*4; sdf wind >= B*Nh; bytes workspace >= ab_interaction_workspace(B,Nh,max_voxels)
+ * @check ab_mspd: can pred_pts >= B*V*3; obj_transf >= B*16; obj_idx mspd >= B; sym_R >= n_obj*Kmax*9; sym_t >= n_obj*Kmax*3; sym_count >= n_obj; pred_R cam_intr >= B*9; pred_t >= B*3; bytes workspace >= ab_mspd_workspace(B,Kmax,V)
+ * @check ab_vsd: obj_verts >= 3; obj_faces >= 3; vert_off face_off >= n_obj+1; rows >= B; rot_est rot_gt cam_intr >= B*9; tsl_est tsl_gt >= B*3; depth_test >= B*H*W; occ_verts >= B*Nv*3; occ_faces >= Nf*3; taus_host >= T; diameter >= n_obj; counts >= B*(2+T); err >= B*T; depth_out >= B*3*H*W; bytes workspace >= ab_vsd_workspace(B,max_obj_verts,Nv,W,H,T)
  */
 
 #ifdef __cplusplus
