@@ -1,11 +1,5 @@
-// The two BOP pose errors the evaluator lacked: MSPD and VSD of bop_toolkit's pose_error.py, each for a whole batch.
-//
-// ab_mspd: per sample, min over the object's TRUE symmetry set of max over the model points of || proj(pred_v) - proj(sym_k(gt)_v) || in
-//   pixels.  The structure of mssd_kernel (mssd.hip): a lane owns one symmetry and composes M = R_gt S_k.R, m = R_gt S_k.t + t_gt once; the
-//   sample's points go through LDS in SoA tiles, and the thread that stages a point also projects the PREDICTED point (the same for every
-//   symmetry), so the scan reads x, y, z, pu, pv with wave-uniform ds_read_b128.  The four waves hold the same 64 symmetries and take a
-//   quarter of each tile; per-chunk partials, a finalize launch with the one square root, no atomics.  A point with camera-space Z <= 0
-//   in either pose makes the sample's error +inf (a projection behind the camera is not a pixel).
+// VSD of bop_toolkit's pose_error.py for a whole batch (the other BOP error the evaluator lacked, MSPD, sits with MSSD
+// in csrc/mssd.hip).
 //
 // ab_vsd: Visible Surface Discrepancy, fused so that no depth image reaches HBM unless asked for.  The stages are a contract (the header
 //   has the full text; tests/bop_raster_ref.py restates it):
@@ -22,147 +16,6 @@
 // vsd_finalize_kernel (one workgroup per sample).
 #include "common.h"
 
-#define MSPD_THREADS 256
-#define MSPD_TILE 1024         // points staged per round: x y z | pu pv, 20 KiB
-
-__device__ __forceinline__ float bop_wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-template <bool POINTS>
-__global__ __launch_bounds__(MSPD_THREADS) void mspd_kernel(const float* __restrict__ can, const float* __restrict__ obj_transf,
-                                                            const int64_t* __restrict__ obj_idx, const float* __restrict__ sym_R,
-                                                            const float* __restrict__ sym_t, const int32_t* __restrict__ sym_count,
-                                                            int n_obj, int Kmax, const float* __restrict__ pred_R,
-                                                            const float* __restrict__ pred_t, const float* __restrict__ pred_pts,
-                                                            const float* __restrict__ cam_intr, int V, float* __restrict__ part) {
-    __shared__ __attribute__((aligned(16))) float vs[5 * MSPD_TILE];
-    __shared__ float s_max[4][64];
-    const int b = blockIdx.y, chunk = blockIdx.x, nchunks = gridDim.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t id = obj_idx[b] - 1;                                           // 1-based; an id outside the table is clamped into it
-    const int obj = id < 0 ? 0 : (id >= n_obj ? n_obj - 1 : (int)id);
-    const int cnt = min(max(sym_count[obj], 0), Kmax);
-    if (chunk * 64 >= cnt) return;                                              // block-uniform
-    const int k = min(chunk * 64 + lane, cnt - 1);                              // lanes past the count recompute the last member (masked below)
-    const float* T = obj_transf + (size_t)b * 16;
-    const float* SR = sym_R + ((size_t)obj * Kmax + k) * 9;
-    const float* St = sym_t + ((size_t)obj * Kmax + k) * 3;
-    const float* Kc = cam_intr + (size_t)b * 9;
-    const float fx = Kc[0], fy = Kc[4], cx = Kc[2], cy = Kc[5];
-    const float inf = __builtin_inff();
-    float A[9], a[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float g0 = T[i * 4 + 0], g1 = T[i * 4 + 1], g2 = T[i * 4 + 2];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) A[i * 3 + j] = (g0 * SR[j] + g1 * SR[3 + j]) + g2 * SR[6 + j];
-        a[i] = ((g0 * St[0] + g1 * St[1]) + g2 * St[2]) + T[i * 4 + 3];
-    }
-    float P[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, p[3] = {0.f, 0.f, 0.f};
-    if (!POINTS) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) P[i] = pred_R[(size_t)b * 9 + i];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) p[i] = pred_t[(size_t)b * 3 + i];
-    }
-    const float* cb = can + (size_t)b * V * 3;
-    const float* pb = POINTS ? pred_pts + (size_t)b * V * 3 : nullptr;
-    float best = 0.f;                                                           // squared pixel distances are >= 0
-    for (int v0 = 0; v0 < V; v0 += MSPD_TILE) {
-        const int n = min(MSPD_TILE, V - v0);
-        const int npad = (n + 15) & ~15;                                        // four waves x groups of four; <= MSPD_TILE
-        __syncthreads();
-        for (int j = threadIdx.x; j < npad; j += MSPD_THREADS) {
-            const size_t src = (size_t)(v0 + (j < n ? j : 0)) * 3;              // the tail repeats the tile's first point: the max is unchanged
-            const float x = cb[src], y = cb[src + 1], z = cb[src + 2];
-            float qx, qy, qz;
-            if (POINTS) { qx = pb[src]; qy = pb[src + 1]; qz = pb[src + 2]; }
-            else {
-                qx = ((P[0] * x + P[1] * y) + P[2] * z) + p[0];
-                qy = ((P[3] * x + P[4] * y) + P[5] * z) + p[1];
-                qz = ((P[6] * x + P[7] * y) + P[8] * z) + p[2];
-            }
-            const bool ok = qz > 0.f;
-            vs[j] = x; vs[MSPD_TILE + j] = y; vs[2 * MSPD_TILE + j] = z;
-            vs[3 * MSPD_TILE + j] = ok ? fx * (qx / qz) + cx : inf;             // a predicted point at or behind the camera: the sample is +inf
-            vs[4 * MSPD_TILE + j] = ok ? fy * (qy / qz) + cy : 0.f;
-        }
-        __syncthreads();
-        const int per = npad >> 2;                                              // this wave's quarter, a multiple of 4
-        const int ja = wave * per, jb = ja + per;
-        for (int j = ja; j < jb; j += 4) {
-            const float4 x4 = *(const float4*)&vs[j], y4 = *(const float4*)&vs[MSPD_TILE + j], z4 = *(const float4*)&vs[2 * MSPD_TILE + j];
-            const float4 u4 = *(const float4*)&vs[3 * MSPD_TILE + j], w4 = *(const float4*)&vs[4 * MSPD_TILE + j];
-            const float xs[4] = {x4.x, x4.y, x4.z, x4.w}, ys[4] = {y4.x, y4.y, y4.z, y4.w}, zs[4] = {z4.x, z4.y, z4.z, z4.w};
-            const float us[4] = {u4.x, u4.y, u4.z, u4.w}, ws[4] = {w4.x, w4.y, w4.z, w4.w};
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float X = ((A[0] * xs[u] + A[1] * ys[u]) + A[2] * zs[u]) + a[0];
-                const float Y = ((A[3] * xs[u] + A[4] * ys[u]) + A[5] * zs[u]) + a[1];
-                const float Z = ((A[6] * xs[u] + A[7] * ys[u]) + A[8] * zs[u]) + a[2];
-                const float du = (fx * (X / Z) + cx) - us[u], dv = (fy * (Y / Z) + cy) - ws[u];
-                float d2 = du * du + dv * dv;
-                if (!(Z > 0.f) || d2 != d2) d2 = inf;                           // behind the camera in the ground truth, or inf - inf
-                best = fmaxf(best, d2);
-            }
-        }
-    }
-    s_max[wave][lane] = best;
-    __syncthreads();
-    if (wave == 0) {
-        float m = fmaxf(fmaxf(s_max[0][lane], s_max[1][lane]), fmaxf(s_max[2][lane], s_max[3][lane]));
-        if (chunk * 64 + lane >= cnt) m = inf;
-        m = bop_wave_min(m);
-        if (lane == 0) part[(size_t)b * nchunks + chunk] = m;
-    }
-}
-
-__global__ __launch_bounds__(256) void mspd_finalize_kernel(const float* __restrict__ part, const int64_t* __restrict__ obj_idx,
-                                                            const int32_t* __restrict__ sym_count, int n_obj, int Kmax, int nchunks, int B,
-                                                            float* __restrict__ mspd) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= B) return;
-    const int64_t id = obj_idx[b] - 1;
-    const int obj = id < 0 ? 0 : (id >= n_obj ? n_obj - 1 : (int)id);
-    const int cnt = min(max(sym_count[obj], 0), Kmax);
-    const int used = (cnt + 63) >> 6;                                           // the chunks the first launch wrote
-    float m = __builtin_inff();                                                 // an empty set: +inf
-    for (int c = 0; c < used; ++c) m = fminf(m, part[(size_t)b * nchunks + c]);
-    mspd[b] = sqrtf(m);
-}
-
-extern "C" long ab_mspd_workspace(int B, int Kmax, int V) {
-    (void)V;
-    if (B < 1 || Kmax < 1) return 0;
-    return (long)B * ((Kmax + 63) / 64) * (long)sizeof(float);
-}
-
-extern "C" int ab_mspd(const float* can, const float* obj_transf, const int64_t* obj_idx, const float* sym_R, const float* sym_t,
-                       const int32_t* sym_count, int n_obj, int Kmax, const float* pred_R, const float* pred_t, const float* pred_pts,
-                       const float* cam_intr, int B, int V, float* mspd, void* workspace, void* stream) {
-    if (!can || !obj_transf || !obj_idx || !sym_R || !sym_t || !sym_count || !cam_intr || !mspd || !workspace) return AB_EINVAL;
-    if (B < 1 || B > 65535 || V < 1 || n_obj < 1 || Kmax < 1) return AB_EINVAL;
-    if (pred_pts ? (pred_R || pred_t) : (!pred_R || !pred_t)) return AB_EINVAL;   // points mode XOR rigid mode
-    const int nchunks = (Kmax + 63) / 64;
-    if (nchunks > 65535) return AB_EINVAL;
-    const dim3 grid(nchunks, B);
-    float* part = (float*)workspace;
-    if (pred_pts)
-        mspd_kernel<true><<<grid, MSPD_THREADS, 0, as_stream(stream)>>>(can, obj_transf, obj_idx, sym_R, sym_t, sym_count, n_obj, Kmax, pred_R,
-                                                                         pred_t, pred_pts, cam_intr, V, part);
-    else
-        mspd_kernel<false><<<grid, MSPD_THREADS, 0, as_stream(stream)>>>(can, obj_transf, obj_idx, sym_R, sym_t, sym_count, n_obj, Kmax, pred_R,
-                                                                          pred_t, pred_pts, cam_intr, V, part);
-    AB_LAUNCH_CHECK();
-    mspd_finalize_kernel<<<(B + 255) / 256, 256, 0, as_stream(stream)>>>(part, obj_idx, sym_count, n_obj, Kmax, nchunks, B, mspd);
-    AB_LAUNCH_CHECK();
-    return 0;
-}
-
-// ================================================================================================ VSD
 #define VSD_TILE 32
 #define VSD_THREADS 256
 #define VSD_NEAR AB_VSD_NEAR            // metres: a triangle with a vertex at Z <= VSD_NEAR is dropped

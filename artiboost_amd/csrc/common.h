@@ -37,4 +37,10 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float ab_nan() { return __builtin_nanf(""); }        // "not computed" in the evaluator's result rows
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }

@@ -34,7 +34,6 @@
 #define IA_HEAD 8              // int32 words per sample: first lattice index [3] | lattice points per axis [3] | n_lattice | capped
 #define IA_TWO_PI 6.2831855f
 
-__device__ __forceinline__ float ia_nan() { return __builtin_nanf(""); }
 __device__ __forceinline__ float ia_dot(float x0, float x1, float x2, float y0, float y1, float y2) {
     return __builtin_fmaf(x2, y2, __builtin_fmaf(x1, y1, x0 * y0));
 }
@@ -278,7 +277,7 @@ __global__ __launch_bounds__(256) void interaction_finalize_kernel(const float* 
     float* row = rows + (size_t)b * AB_IA_ROW;
     int32_t* cn = counts + (size_t)b * 4;
 #pragma unroll
-    for (int k = 0; k < AB_IA_ROW; ++k) row[k] = ia_nan();
+    for (int k = 0; k < AB_IA_ROW; ++k) row[k] = ab_nan();
     cn[0] = cn[1] = cn[2] = cn[3] = 0;
     if (flags & AB_IA_VERTS) {
         int n_in = 0;

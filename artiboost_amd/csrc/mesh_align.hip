@@ -4,25 +4,19 @@
 //
 // Chamfer.  x_i = keep (R can_i + t), y_j = keep (targ_j + root), keep = any(corners_vis != 0), formed here.  One workgroup per (sample,
 // chunk of 256 query points); the first ceil(N/256) chunks of a sample own points of x and scan y, the other ceil(M/256) own points of y and
-// scan x.  The scanned cloud goes through LDS in SoA tiles: one wave-uniform (broadcast) ds_read_b128 per coordinate serves four scanned
-// points for 64 queries, and a lane keeps a running minimum of the sum of squared differences and its index (strict <: the first minimum
-// wins, as argmin does).  x_i is the same fused-multiply-add chain wherever it is formed (staged tile or query register), so both directions
+// scan x.  The scan is nn_tile_scan (csrc/nn_tile.h), with the winner's index kept (the first minimum wins, as argmin does).
+// x_i is the same fused-multiply-add chain wherever it is formed (staged tile or query register), so both directions
 // see the same bits.  The gradient needs no scatter: a query of x adds d = x_i - y_i* to the sums  sum d,  sum d can_i^T;  a query of y
 // adds d = x_j* - y_j with can_j* gathered once.  A chunk's 13 sums (distance, 3, 9) are reduced in a fixed order (wave butterfly, then the
 // four waves in turn) into the workspace, and a second small launch adds the chunks of a sample in turn, scales, and sums the batch in a
 // fixed order.  No atomics: two calls give the same bits, and a sample's distances and (x B) gradients do not depend on the batch around it.
 //
-// Procrustes.  One wave per sample.  With Xc = targ - mean(targ) (the root cancels in the centred target: it enters the translation only),
-// Pc = pred - mean(pred), c = |Xc|_F + 1e-8, p = |Pc|_F + 1e-8, Xh = Xc / c, Ph = Pc / p and M = Xh^T Ph = u w v^T:
-//   R = u v^T (the orthogonal polar factor of M, no determinant correction),  s = sum w,  aligned_i = s c R Ph_i + mean(targ) + root,
+// Procrustes.  One wave per sample solves procrustes_fit (csrc/procrustes.h: c, p, s, R and the notation are defined there), then
 //   sample_loss = c^2 sum_i |s R Ph_i - Xh_i|^2 / (3n)   -- from the residual itself: 1 - s^2 has no digits left when s -> 1.
 // R is the optimum, so no SVD backward: d loss / d M = -2 c^2 s R / (3 n B), d loss / d Ph_i = -2 c^2 s (R^T Xh_i - s Ph_i) / (3 n B) up to
-// the 1e-8 of the norm (see the kernel), then through Ph = Pc / p (the radial part, -s Ph_i included, drops out) and the centring.  v comes from a cyclic Jacobi iteration on M^T M in registers, in its one-sided
-// form (the columns of M V are rotated until orthogonal; the squared matrix is never formed, so the rotation keeps its digits in the
-// flat direction of a hand -- a near-perfect prediction's gradient is a small difference that sees an error of R directly); the
-// columns of u are M v_k, orthonormalised largest first, the last one the cross product with the sign of its M v_3, so a rank-deficient M
-// (coplanar / collinear joints) gives an orthogonal R and finite numbers everywhere; s = sum u_k . M v_k.
+// the 1e-8 of the norm (see the kernel), then through Ph = Pc / p (the radial part, -s Ph_i included, drops out) and the centring.
 #include "common.h"
+#include "nn_tile.h"
 #include "procrustes.h"
 
 #define CH_THREADS 256         // one query point per thread
@@ -79,35 +73,15 @@ __global__ __launch_bounds__(CH_THREADS) void chamfer_rigid_kernel(const float* 
     } else {
         px = tb[(size_t)qc * 3] + rt[0]; py = tb[(size_t)qc * 3 + 1] + rt[1]; pz = tb[(size_t)qc * 3 + 2] + rt[2];
     }
-    float best = __builtin_inff();
-    int besti = 0;
-    for (int v0 = 0; v0 < ns; v0 += CH_TILE) {
-        const int n = min(CH_TILE, ns - v0);
-        const int npad = (n + 3) & ~3;                                           // <= CH_TILE (a multiple of 4)
-        __syncthreads();
-        for (int j = threadIdx.x; j < npad; j += CH_THREADS) {
-            const size_t src = (size_t)(v0 + (j < n ? j : 0)) * 3;               // the tail repeats the tile's first point: under strict < it never wins
-            float a0, a1, a2;
-            if (own_x) { a0 = tb[src] + rt[0]; a1 = tb[src + 1] + rt[1]; a2 = tb[src + 2] + rt[2]; }
-            else {
-                const float s0 = cb[src], s1 = cb[src + 1], s2 = cb[src + 2];
-                a0 = rigid1(R, t[0], s0, s1, s2); a1 = rigid1(R + 3, t[1], s0, s1, s2); a2 = rigid1(R + 6, t[2], s0, s1, s2);
-            }
-            vs[j] = a0; vs[CH_TILE + j] = a1; vs[2 * CH_TILE + j] = a2;
+    const nn_hit hit = nn_tile_scan<CH_TILE, CH_THREADS, true>(vs, ns, px, py, pz, [&](size_t src, float& a0, float& a1, float& a2) {
+        if (own_x) { a0 = tb[src] + rt[0]; a1 = tb[src + 1] + rt[1]; a2 = tb[src + 2] + rt[2]; }
+        else {
+            const float s0 = cb[src], s1 = cb[src + 1], s2 = cb[src + 2];
+            a0 = rigid1(R, t[0], s0, s1, s2); a1 = rigid1(R + 3, t[1], s0, s1, s2); a2 = rigid1(R + 6, t[2], s0, s1, s2);
         }
-        __syncthreads();
-        for (int j = 0; j < npad; j += 4) {
-            const float4 x4 = *(const float4*)&vs[j], y4 = *(const float4*)&vs[CH_TILE + j], z4 = *(const float4*)&vs[2 * CH_TILE + j];
-            const float xs[4] = {x4.x, x4.y, x4.z, x4.w}, ys[4] = {y4.x, y4.y, y4.z, y4.w}, zs[4] = {z4.x, z4.y, z4.z, z4.w};
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float dx = px - xs[u], dy = py - ys[u], dz = pz - zs[u];
-                const float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-                if (d < best) { best = d; besti = v0 + j + u; }
-            }
-        }
-    }
-    if (besti >= ns) besti = ns - 1;                                             // (cannot happen for finite inputs; keeps the gather in bounds)
+    });
+    const float best = hit.d2;
+    const int besti = hit.idx >= ns ? ns - 1 : hit.idx;                          // (cannot happen for finite inputs; keeps the gather in bounds)
     if (live) {
         if (dist) dist[(size_t)b * nq + q] = best;
         if (idx) idx[(size_t)b * nq + q] = besti;
@@ -213,89 +187,10 @@ __global__ __launch_bounds__(PR_THREADS) void procrustes_kernel(const float* __r
     const float* P = pred + (size_t)b * n * 3;
     const float* X = targ + (size_t)b * n * 3;
     const float inv_n = 1.f / (float)n;
-    // centroids
-    float mp[3] = {0.f, 0.f, 0.f}, mx[3] = {0.f, 0.f, 0.f};
-    for (int i = lane; i < n; i += 64)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { mp[k] += P[i * 3 + k]; mx[k] += X[i * 3 + k]; }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { mp[k] = wave_sum(mp[k]) * inv_n; mx[k] = wave_sum(mx[k]) * inv_n; }
-    // Frobenius norms and the raw correlation  C[a][b] = sum_i Xc_ia Pc_ib
-    float pp = 0.f, xx = 0.f, C[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) C[a][k] = 0.f;
-    for (int i = lane; i < n; i += 64) {
-        float pc[3], xc[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { pc[k] = P[i * 3 + k] - mp[k]; xc[k] = X[i * 3 + k] - mx[k]; }
-        pp += dot3(pc, pc); xx += dot3(xc, xc);
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) C[a][k] = __builtin_fmaf(xc[a], pc[k], C[a][k]);
-    }
-    pp = wave_sum(pp); xx = wave_sum(xx);
-    const float cs = sqrtf(xx) + 1e-8f, ps = sqrtf(pp) + 1e-8f;
-    const float icp = 1.f / (cs * ps);
-    float Mm[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) Mm[a][k] = wave_sum(C[a][k]) * icp;       // M = Xh^T Ph
-    // right singular vectors: W = M V with orthogonal columns (all lanes hold the same bits: the butterfly sums are lane-uniform)
-    float W[3][3], V[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { W[a][k] = Mm[a][k]; V[a][k] = a == k ? 1.f : 0.f; }
-#pragma unroll 1
-    for (int sweep = 0; sweep < PR_SWEEPS; ++sweep) { jacobi_rot(W, V, 0, 1); jacobi_rot(W, V, 0, 2); jacobi_rot(W, V, 1, 2); }
-    float lam[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) lam[k] = __builtin_fmaf(W[2][k], W[2][k], __builtin_fmaf(W[1][k], W[1][k], W[0][k] * W[0][k]));
-#define PR_SWAP(i, j)                                                                                      \
-    if (lam[i] < lam[j]) {                                                                                  \
-        float t_ = lam[i]; lam[i] = lam[j]; lam[j] = t_;                                                    \
-        for (int k_ = 0; k_ < 3; ++k_) {                                                                    \
-            t_ = V[k_][i]; V[k_][i] = V[k_][j]; V[k_][j] = t_;                                              \
-            t_ = W[k_][i]; W[k_][i] = W[k_][j]; W[k_][j] = t_;                                              \
-        }                                                                                                   \
-    }
-    PR_SWAP(0, 1) PR_SWAP(0, 2) PR_SWAP(1, 2)
-#undef PR_SWAP
-    // w_k = M v_k = w_k u_k; u: orthonormalised, largest first
-    float w[3][3], u[3][3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) w[k][a] = W[a][k];
-    float n1 = sqrtf(dot3(w[0], w[0]));
-    if (n1 > 1e-30f) { u[0][0] = w[0][0] / n1; u[0][1] = w[0][1] / n1; u[0][2] = w[0][2] / n1; }
-    else { u[0][0] = 1.f; u[0][1] = 0.f; u[0][2] = 0.f; }
-    float h = dot3(w[1], u[0]);
-    float e[3] = {w[1][0] - h * u[0][0], w[1][1] - h * u[0][1], w[1][2] - h * u[0][2]};
-    float n2 = sqrtf(dot3(e, e));
-    if (!(n2 > 1e-30f)) {                                                        // rank <= 1: any unit vector orthogonal to u1
-        const float a0 = fabsf(u[0][0]), a1 = fabsf(u[0][1]), a2 = fabsf(u[0][2]);
-        float ax[3] = {0.f, 0.f, 0.f};
-        ax[(a0 <= a1 && a0 <= a2) ? 0 : (a1 <= a2 ? 1 : 2)] = 1.f;
-        h = dot3(ax, u[0]);
-        e[0] = ax[0] - h * u[0][0]; e[1] = ax[1] - h * u[0][1]; e[2] = ax[2] - h * u[0][2];
-        n2 = sqrtf(dot3(e, e));
-    }
-    u[1][0] = e[0] / n2; u[1][1] = e[1] / n2; u[1][2] = e[2] / n2;
-    u[2][0] = u[0][1] * u[1][2] - u[0][2] * u[1][1];
-    u[2][1] = u[0][2] * u[1][0] - u[0][0] * u[1][2];
-    u[2][2] = u[0][0] * u[1][1] - u[0][1] * u[1][0];
-    if (dot3(u[2], w[2]) < 0.f) { u[2][0] = -u[2][0]; u[2][1] = -u[2][1]; u[2][2] = -u[2][2]; }     // a reflection when det M < 0
-    const float s = (dot3(u[0], w[0]) + dot3(u[1], w[1])) + dot3(u[2], w[2]);
-    float Rm[3][3];                                                               // R = u v^T
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) Rm[a][k] = __builtin_fmaf(u[2][a], V[k][2], __builtin_fmaf(u[1][a], V[k][1], u[0][a] * V[k][0]));
+    pr_fit f;
+    procrustes_fit(P, X, n, lane, f);
+    const float *mp = f.mp, *mx = f.mx, cs = f.c, ps = f.p, s = f.s;
+    const float(&Rm)[3][3] = f.R;
     // residual, loss, and the gradient's two inner products
     const float ic = 1.f / cs, ip = 1.f / ps;
     const float k0 = (-2.f * (cs * cs) * s) / (3.f * (float)n);

@@ -3,22 +3,20 @@
 //                     onto G (pa_epe, scale) and the two-way nearest-neighbour distances of P and of the aligned P' against G (their means --
 //                     mean_gp is ADD-S -- and the precision / recall counts and F-scores per threshold).
 //
-// Stage 1 (AB_MM_PAIRED | AB_MM_PROCRUSTES), one wave per sample: the solve of ab_procrustes_loss (csrc/mesh_align.hip), statement for
-// statement -- centroids, Frobenius norms with their 1e-8 guards, M = Gh^T Ph, one-sided Jacobi for v, u orthonormalised largest first with
-// the sign of the last column taken from M v_3 (no determinant correction: a mirrored prediction aligns by a reflection; a rank-deficient
-// cloud gives an orthogonal R and finite numbers).  It leaves the similarity in the workspace as the numbers `aligned` is formed from there,
+// Stage 1 (AB_MM_PAIRED | AB_MM_PROCRUSTES), one wave per sample: procrustes_fit (csrc/procrustes.h), the solve ab_procrustes_loss calls
+// too.  It leaves the similarity in the workspace as the numbers `aligned` is formed from there,
 //   P'_i = fma(s c, R ((P_i - mean P) / p), mean(targ) + root),
 // not as one folded 3x4 map: A P_i + t would subtract two half-metre vectors to get a centimetre one.  The paired sums are wave butterflies.
 // Stage 2 (AB_MM_NN), one workgroup per (sample, pass, direction, chunk of 256 query points): pass 0 scans P against G, pass 1 (with
 // AB_MM_PROCRUSTES) P' against G; the first ceil(N/256) chunks of a pass own points of the prediction and scan G, the other ceil(M/256) own
-// points of G and scan the prediction.  The scanned cloud goes through LDS in SoA tiles exactly as in ab_chamfer_rigid: one wave-uniform
-// ds_read_b128 per coordinate serves four scanned points for 64 queries, sums of squared differences (never |x|^2 + |y|^2 - 2 x.y), squared
+// points of G and scan the prediction.  The scan is nn_tile_scan (csrc/nn_tile.h), the one ab_chamfer_rigid runs, without the index: squared
 // lengths compared, one square root per query at the end.  P' is the same chain wherever it is formed (query register, staged tile,
 // stage 1), so every direction sees the same bits and no aligned [B,N,3] is written.  A chunk leaves its distance sum (wave butterfly, the
 // four waves in turn) and its counts below each threshold (ballot + popcount) in the workspace.
 // Stage 3, one thread per sample: adds the sample's chunks in turn, writes the means, the integer counts and the F-scores.
 // No atomics of any kind; two calls give the same bits, and a sample's row, counts and distances do not depend on the batch around it.
 #include "common.h"
+#include "nn_tile.h"
 #include "procrustes.h"
 
 #define MM_THREADS 256         // one query point per thread
@@ -28,8 +26,6 @@
 #define MM_WAVES 4             // stage 1: four waves per workgroup, one sample each
 
 struct mm_thresholds { float t[AB_MM_MAX_THRESHOLDS]; };
-
-__device__ __forceinline__ float mm_nan() { return __builtin_nanf(""); }
 
 // P'_i from the sample's similarity record: the statements ab_procrustes_loss forms `aligned` with.
 __device__ __forceinline__ void mm_align1(const float* sim, float p0, float p1, float p2, float& o0, float& o1, float& o2) {
@@ -54,7 +50,7 @@ __global__ __launch_bounds__(MM_WAVES * 64) void mesh_metrics_align_kernel(const
 #pragma unroll
     for (int k = 0; k < 3; ++k) rt[k] = root ? root[(size_t)b * 3 + k] : 0.f;
     float* row = rows + (size_t)b * AB_MM_ROW;
-    float epe = mm_nan(), ra_epe = mm_nan(), pa_epe = mm_nan(), scale = mm_nan();
+    float epe = ab_nan(), ra_epe = ab_nan(), pa_epe = ab_nan(), scale = ab_nan();
     if (flags & AB_MM_PAIRED) {
         float pc[3] = {0.f, 0.f, 0.f}, gc[3] = {0.f, 0.f, 0.f};
         if (center_idx >= 0) {
@@ -73,86 +69,17 @@ __global__ __launch_bounds__(MM_WAVES * 64) void mesh_metrics_align_kernel(const
         if (center_idx >= 0) ra_epe = wave_sum(r) / (float)n;
     }
     if (flags & AB_MM_PROCRUSTES) {
-        // the solve of procrustes_kernel (csrc/mesh_align.hip): keep the two in step
-        const float inv_n = 1.f / (float)n;
-        float mp[3] = {0.f, 0.f, 0.f}, mx[3] = {0.f, 0.f, 0.f};
-        for (int i = lane; i < n; i += 64)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { mp[k] += P[i * 3 + k]; mx[k] += X[i * 3 + k]; }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { mp[k] = wave_sum(mp[k]) * inv_n; mx[k] = wave_sum(mx[k]) * inv_n; }
-        float pp = 0.f, xx = 0.f, C[3][3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) C[a][k] = 0.f;
-        for (int i = lane; i < n; i += 64) {
-            float pc[3], xc[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { pc[k] = P[i * 3 + k] - mp[k]; xc[k] = X[i * 3 + k] - mx[k]; }
-            pp += dot3(pc, pc); xx += dot3(xc, xc);
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int k = 0; k < 3; ++k) C[a][k] = __builtin_fmaf(xc[a], pc[k], C[a][k]);
-        }
-        pp = wave_sum(pp); xx = wave_sum(xx);
-        const float cs = sqrtf(xx) + 1e-8f, ps = sqrtf(pp) + 1e-8f;
-        const float icp = 1.f / (cs * ps);
-        float W[3][3], V[3][3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { W[a][k] = wave_sum(C[a][k]) * icp; V[a][k] = a == k ? 1.f : 0.f; }      // W = M V, M = Gh^T Ph
-#pragma unroll 1
-        for (int sweep = 0; sweep < PR_SWEEPS; ++sweep) { jacobi_rot(W, V, 0, 1); jacobi_rot(W, V, 0, 2); jacobi_rot(W, V, 1, 2); }
-        float lam[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) lam[k] = __builtin_fmaf(W[2][k], W[2][k], __builtin_fmaf(W[1][k], W[1][k], W[0][k] * W[0][k]));
-#define MM_SWAP(i, j)                                                                                      \
-    if (lam[i] < lam[j]) {                                                                                  \
-        float t_ = lam[i]; lam[i] = lam[j]; lam[j] = t_;                                                    \
-        for (int k_ = 0; k_ < 3; ++k_) {                                                                    \
-            t_ = V[k_][i]; V[k_][i] = V[k_][j]; V[k_][j] = t_;                                              \
-            t_ = W[k_][i]; W[k_][i] = W[k_][j]; W[k_][j] = t_;                                              \
-        }                                                                                                   \
-    }
-        MM_SWAP(0, 1) MM_SWAP(0, 2) MM_SWAP(1, 2)
-#undef MM_SWAP
-        float w[3][3], u[3][3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int a = 0; a < 3; ++a) w[k][a] = W[a][k];
-        float n1 = sqrtf(dot3(w[0], w[0]));
-        if (n1 > 1e-30f) { u[0][0] = w[0][0] / n1; u[0][1] = w[0][1] / n1; u[0][2] = w[0][2] / n1; }
-        else { u[0][0] = 1.f; u[0][1] = 0.f; u[0][2] = 0.f; }
-        float h = dot3(w[1], u[0]);
-        float e[3] = {w[1][0] - h * u[0][0], w[1][1] - h * u[0][1], w[1][2] - h * u[0][2]};
-        float n2 = sqrtf(dot3(e, e));
-        if (!(n2 > 1e-30f)) {                                                    // rank <= 1: any unit vector orthogonal to u1
-            const float a0 = fabsf(u[0][0]), a1 = fabsf(u[0][1]), a2 = fabsf(u[0][2]);
-            float ax[3] = {0.f, 0.f, 0.f};
-            ax[(a0 <= a1 && a0 <= a2) ? 0 : (a1 <= a2 ? 1 : 2)] = 1.f;
-            h = dot3(ax, u[0]);
-            e[0] = ax[0] - h * u[0][0]; e[1] = ax[1] - h * u[0][1]; e[2] = ax[2] - h * u[0][2];
-            n2 = sqrtf(dot3(e, e));
-        }
-        u[1][0] = e[0] / n2; u[1][1] = e[1] / n2; u[1][2] = e[2] / n2;
-        u[2][0] = u[0][1] * u[1][2] - u[0][2] * u[1][1];
-        u[2][1] = u[0][2] * u[1][0] - u[0][0] * u[1][2];
-        u[2][2] = u[0][0] * u[1][1] - u[0][1] * u[1][0];
-        if (dot3(u[2], w[2]) < 0.f) { u[2][0] = -u[2][0]; u[2][1] = -u[2][1]; u[2][2] = -u[2][2]; }     // a reflection when det M < 0
-        const float s = (dot3(u[0], w[0]) + dot3(u[1], w[1])) + dot3(u[2], w[2]);
+        pr_fit f;
+        procrustes_fit(P, X, n, lane, f);
         float sim[MM_SIM];
-        sim[0] = mp[0]; sim[1] = mp[1]; sim[2] = mp[2]; sim[3] = 1.f / ps;
+        sim[0] = f.mp[0]; sim[1] = f.mp[1]; sim[2] = f.mp[2]; sim[3] = 1.f / f.p;
 #pragma unroll
         for (int a = 0; a < 3; ++a)
 #pragma unroll
-            for (int k = 0; k < 3; ++k) sim[4 + a * 3 + k] = __builtin_fmaf(u[2][a], V[k][2], __builtin_fmaf(u[1][a], V[k][1], u[0][a] * V[k][0]));   // R = u v^T
-        sim[13] = s * cs;
+            for (int k = 0; k < 3; ++k) sim[4 + a * 3 + k] = f.R[a][k];
+        sim[13] = f.s * f.c;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) sim[14 + k] = mx[k] + rt[k];
+        for (int k = 0; k < 3; ++k) sim[14 + k] = f.mx[k] + rt[k];
         sim[17] = sim[18] = sim[19] = 0.f;
         float a = 0.f;
         for (int i = lane; i < n; i += 64) {
@@ -160,7 +87,7 @@ __global__ __launch_bounds__(MM_WAVES * 64) void mesh_metrics_align_kernel(const
             mm_align1(sim, P[i * 3], P[i * 3 + 1], P[i * 3 + 2], q0, q1, q2);
             a += mm_len(q0 - (X[i * 3] + rt[0]), q1 - (X[i * 3 + 1] + rt[1]), q2 - (X[i * 3 + 2] + rt[2]));
         }
-        pa_epe = wave_sum(a) * inv_n;
+        pa_epe = wave_sum(a) * (1.f / (float)n);
         scale = sim[13] * sim[3];                                                // tr Sigma / |Pc|^2 = s c / p
         if (lane == 0) {                                                         // every lane holds the same bits
 #pragma unroll
@@ -204,34 +131,14 @@ __global__ __launch_bounds__(MM_THREADS) void mesh_metrics_scan_kernel(const flo
     } else {
         px = tb[(size_t)qc * 3] + rt[0]; py = tb[(size_t)qc * 3 + 1] + rt[1]; pz = tb[(size_t)qc * 3 + 2] + rt[2];
     }
-    float best = __builtin_inff();
-    for (int v0 = 0; v0 < ns; v0 += MM_TILE) {
-        const int n = min(MM_TILE, ns - v0);
-        const int npad = (n + 3) & ~3;                                           // <= MM_TILE (a multiple of 4)
-        __syncthreads();
-        for (int j = threadIdx.x; j < npad; j += MM_THREADS) {
-            const size_t src = (size_t)(v0 + (j < n ? j : 0)) * 3;               // the tail repeats the tile's first point: the minimum is unchanged
-            float a0, a1, a2;
-            if (own_p) { a0 = tb[src] + rt[0]; a1 = tb[src + 1] + rt[1]; a2 = tb[src + 2] + rt[2]; }
-            else {
-                a0 = pb[src]; a1 = pb[src + 1]; a2 = pb[src + 2];
-                if (pass) mm_align1(sim, a0, a1, a2, a0, a1, a2);
-            }
-            vs[j] = a0; vs[MM_TILE + j] = a1; vs[2 * MM_TILE + j] = a2;
+    const nn_hit hit = nn_tile_scan<MM_TILE, MM_THREADS, false>(vs, ns, px, py, pz, [&](size_t src, float& a0, float& a1, float& a2) {
+        if (own_p) { a0 = tb[src] + rt[0]; a1 = tb[src + 1] + rt[1]; a2 = tb[src + 2] + rt[2]; }
+        else {
+            a0 = pb[src]; a1 = pb[src + 1]; a2 = pb[src + 2];
+            if (pass) mm_align1(sim, a0, a1, a2, a0, a1, a2);
         }
-        __syncthreads();
-        for (int j = 0; j < npad; j += 4) {
-            const float4 x4 = *(const float4*)&vs[j], y4 = *(const float4*)&vs[MM_TILE + j], z4 = *(const float4*)&vs[2 * MM_TILE + j];
-            const float xs[4] = {x4.x, x4.y, x4.z, x4.w}, ys[4] = {y4.x, y4.y, y4.z, y4.w}, zs[4] = {z4.x, z4.y, z4.z, z4.w};
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float dx = px - xs[u], dy = py - ys[u], dz = pz - zs[u];
-                const float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-                best = d < best ? d : best;
-            }
-        }
-    }
-    const float d = sqrtf(best);
+    });
+    const float d = sqrtf(hit.d2);
     if (live && dist) dist[(size_t)b * nq + q] = d;
     const float a = wave_sum(live ? d : 0.f);
     int cnt[AB_MM_MAX_THRESHOLDS];
@@ -259,11 +166,11 @@ __global__ __launch_bounds__(256) void mesh_metrics_finalize_kernel(const float*
     const int b = blockIdx.x * 256 + (int)threadIdx.x;
     if (b >= B) return;
     float* row = rows + (size_t)b * AB_MM_ROW;
-    if (!(flags & (AB_MM_PAIRED | AB_MM_PROCRUSTES))) row[AB_MM_EPE] = row[AB_MM_RA_EPE] = row[AB_MM_PA_EPE] = row[AB_MM_SCALE] = mm_nan();
+    if (!(flags & (AB_MM_PAIRED | AB_MM_PROCRUSTES))) row[AB_MM_EPE] = row[AB_MM_RA_EPE] = row[AB_MM_PA_EPE] = row[AB_MM_SCALE] = ab_nan();
     const int per = cx + cy;
     const float* p = part + (size_t)b * passes * per * MM_PART;
     for (int pass = 0; pass < 2; ++pass) {
-        float mean[2] = {mm_nan(), mm_nan()};
+        float mean[2] = {ab_nan(), ab_nan()};
         int cnt[2][AB_MM_MAX_THRESHOLDS] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
         const bool have = pass < passes;                                         // passes = 0: no scan was asked for
         if (have) {
@@ -282,7 +189,7 @@ __global__ __launch_bounds__(256) void mesh_metrics_finalize_kernel(const float*
         row[pass ? AB_MM_PA_MEAN_GP : AB_MM_MEAN_GP] = mean[1];
 #pragma unroll
         for (int t = 0; t < AB_MM_MAX_THRESHOLDS; ++t) {
-            float f = mm_nan();
+            float f = ab_nan();
             if (have && t < T) {
                 const float pr = (float)cnt[0][t] / (float)N, rc = (float)cnt[1][t] / (float)M;
                 f = pr + rc > 0.f ? 2.f * pr * rc / (pr + rc) : 0.f;

@@ -850,7 +850,7 @@ int ab_interaction(const float* hand_verts, const int32_t* hand_faces, int Nh, i
                    const int64_t* obj_row, const float* rot, const float* tsl, int B, float contact_thr, float voxel, int max_voxels, int flags,
                    float* rows, int32_t* counts, float* sdf, float* wind, void* workspace, void* stream);
 
-/* ---- BOP pose errors of the evaluator, eager only (csrc/bop_recall.hip) -----------------------------------------------
+/* ---- BOP pose errors of the evaluator, eager only (ab_mspd: csrc/mssd.hip, ab_vsd: csrc/bop_recall.hip) ---------------
  * The two errors of bop_toolkit's pose_error.py that, with ab_mssd, make the BOP average recall: MSPD and VSD.
  *
  * ab_mspd: per sample b, with the symmetry set of ab_mssd (same table layout, same sym_count semantics, same clamping of obj_idx),

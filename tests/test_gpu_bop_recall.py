@@ -1,4 +1,4 @@
-"""ab_vsd and ab_mspd (csrc/bop_recall.hip) on the device.
+"""ab_vsd (csrc/bop_recall.hip) and ab_mspd (csrc/mssd.hip) on the device.
 
 ab_vsd against the stage restatement tests/bop_raster_ref.py: depth images bit-equal, counts equal, errors bit-equal after the same fp32 rounding
 -- stages A to D are written so that this holds; there is no tolerance.  B = 3 on a 48 x 40 image (non-square, partial 32 x 32 tiles on both

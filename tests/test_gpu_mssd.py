@@ -14,7 +14,7 @@ from test_mssd_host import (AR_TAGS, TOL_M, _eval_batches, cfg_for, check_golden
                             true_sets)
 
 pytestmark = pytest.mark.gpu
-TILE = 1024             # MSSD_TILE of csrc/mssd.hip: vertices staged per round
+TILE = 1024             # SYM_TILE of csrc/mssd.hip: vertices staged per round
 
 
 def _rot(rng):
