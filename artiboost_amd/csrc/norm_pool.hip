@@ -1,69 +1,158 @@
 // HBM-bound NHWC elementwise / reduction kernels around the conv stack: training-mode BatchNorm (statistics, apply,
 // backward), ReLU and residual fusion, 3x3/2 max-pool, global average pool, precision packing.
 // All tensors are [M = N*H*W pixels][C channels] with C % 8 == 0; every access is a 16-byte vector per lane.
+//
+// Every arithmetic body of the family is written ONCE below ("shared bodies") and the __global__ kernels only choose the loads, the
+// stores and the thread mapping around it: for this file the bits are the contract (the folded conv epilogues must agree with
+// bn_apply, every backward mask with the forward expression), and a copy that drifts by one operation is a silent wrong gradient.
 #include "common.h"
+#include <type_traits>
 
 template <typename T> struct Vec;
 template <> struct Vec<float> { static constexpr int N = 4; };
 template <> struct Vec<bf16_t> { static constexpr int N = 8; };
 
-template <typename T> __device__ __forceinline__ void vload(const T* p, float* f);
-template <> __device__ __forceinline__ void vload<float>(const float* p, float* f) {
-    float4 v = *(const float4*)p; f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+// ================================================================ shared bodies: vector access
+// N 32-bit words at p in one 4-, 8- or 16-byte access
+template <int N> __device__ __forceinline__ void ld_words(const void* p, uint32_t* w) {
+    if constexpr (N == 4) { const uint4 v = *(const uint4*)p; w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
+    else if constexpr (N == 2) { const uint2 v = *(const uint2*)p; w[0] = v.x; w[1] = v.y; }
+    else w[0] = *(const uint32_t*)p;
 }
-template <> __device__ __forceinline__ void vload<bf16_t>(const bf16_t* p, float* f) {
-    uint4 v = *(const uint4*)p;
-    uint32_t w[4] = {v.x, v.y, v.z, v.w};
+template <int N> __device__ __forceinline__ void st_words(void* p, const uint32_t* w) {
+    if constexpr (N == 4) *(uint4*)p = make_uint4(w[0], w[1], w[2], w[3]);
+    else if constexpr (N == 2) *(uint2*)p = make_uint2(w[0], w[1]);
+    else *(uint32_t*)p = w[0];
+}
+// V elements at p widened to fp32 (V = 4 or 8; fp32: 16-byte vectors).  T = bf16_t is also the decode of ONE plane of a split
+// tensor -- the hi plane alone carries the sign, which is all a ReLU mask needs of the activation.
+template <typename T, int V = Vec<T>::N> __device__ __forceinline__ void vload(const T* p, float* f) {
+    if constexpr (std::is_same<T, float>::value) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { f[2 * i] = __uint_as_float(w[i] << 16); f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u); }
-}
-template <typename T> __device__ __forceinline__ void vstore(T* p, const float* f);
-template <> __device__ __forceinline__ void vstore<float>(float* p, const float* f) {
-    *(float4*)p = make_float4(f[0], f[1], f[2], f[3]);
-}
-template <> __device__ __forceinline__ void vstore<bf16_t>(bf16_t* p, const float* f) {
-    uint32_t w[4];
+        for (int i = 0; i < V / 4; ++i) {
+            const float4 v = *(const float4*)(p + 4 * i);
+            f[4 * i] = v.x; f[4 * i + 1] = v.y; f[4 * i + 2] = v.z; f[4 * i + 3] = v.w;
+        }
+    } else {
+        uint32_t w[V / 2]; ld_words<V / 2>(p, w);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = pack_bf16x2(f[2 * i], f[2 * i + 1]);
-    *(uint4*)p = make_uint4(w[0], w[1], w[2], w[3]);
+        for (int i = 0; i < V / 2; ++i) {
+            f[2 * i] = __uint_as_float(w[i] << 16);
+            f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+        }
+    }
+}
+template <typename T, int V = Vec<T>::N> __device__ __forceinline__ void vstore(T* p, const float* f) {
+    if constexpr (std::is_same<T, float>::value) {
+#pragma unroll
+        for (int i = 0; i < V / 4; ++i) *(float4*)(p + 4 * i) = make_float4(f[4 * i], f[4 * i + 1], f[4 * i + 2], f[4 * i + 3]);
+    } else {
+        uint32_t w[V / 2];
+#pragma unroll
+        for (int i = 0; i < V / 2; ++i) w[i] = pack_bf16x2(f[2 * i], f[2 * i + 1]);
+        st_words<V / 2>(p, w);
+    }
 }
 
 template <typename T> __device__ __forceinline__ float round_to(float v);
 template <> __device__ __forceinline__ float round_to<float>(float v) { return v; }
 template <> __device__ __forceinline__ float round_to<bf16_t>(float v) { return bf16_to_f32(f32_to_bf16(v)); }
 
+// Split-bf16 ("bf16x3") planes: the fp32 elementwise passes that feed a convolution write its operand directly as (hi, lo) bf16
+// planes (conv_x3.hip): same bytes as the fp32 tensor they replace, and no separate split pass.
+template <int V> __device__ __forceinline__ void store_split(bf16_t* __restrict__ hi, bf16_t* __restrict__ lo, long e, const float* f) {
+    uint32_t h[V / 2], l[V / 2];
+#pragma unroll
+    for (int k = 0; k < V / 2; ++k) {
+        h[k] = pack_bf16x2(f[2 * k], f[2 * k + 1]);
+        l[k] = pack_bf16x2(f[2 * k] - __uint_as_float(h[k] << 16), f[2 * k + 1] - __uint_as_float(h[k] & 0xffff0000u));
+    }
+    st_words<V / 2>(hi + e, h);
+    st_words<V / 2>(lo + e, l);
+}
+// f = hi + lo: the fp32 value of V elements of a split tensor
+template <int V> __device__ __forceinline__ void load_planes(const bf16_t* __restrict__ hi, const bf16_t* __restrict__ lo, long e, float* f) {
+    float l[V]; vload<bf16_t, V>(hi + e, f); vload<bf16_t, V>(lo + e, l);
+#pragma unroll
+    for (int k = 0; k < V; ++k) f[k] += l[k];
+}
+
+// Max-pool winners: one byte per output element, the tap (dh * 3 + dw) that won
+template <int V> __device__ __forceinline__ void unpack_winners(const uint8_t* p, uint32_t* am) {
+    uint32_t w[V / 4]; ld_words<V / 4>(p, w);
+#pragma unroll
+    for (int k = 0; k < V; ++k) am[k] = (w[k / 4] >> (8 * (k & 3))) & 0xff;
+}
+template <int V> __device__ __forceinline__ void pack_winners(uint8_t* p, const uint32_t* am) {
+    uint32_t w[V / 4];
+#pragma unroll
+    for (int k = 0; k < V / 4; ++k) w[k] = am[4 * k] | (am[4 * k + 1] << 8) | (am[4 * k + 2] << 16) | (am[4 * k + 3] << 24);
+    st_words<V / 4>(p, w);
+}
+
+// (scale, shift) of V channels from c: the first two rows of a bnp [4][C]
+template <int V> __device__ __forceinline__ void load_scale_shift(const float* bnp, int C, int c, float* sc, float* sh) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) { sc[k] = bnp[c + k]; sh[k] = bnp[C + c + k]; }
+}
+
+// Grid-stride loop over the nvec V-element vectors of an [M][C] tensor, 256 threads per workgroup: loadp(c) fetches the parameters
+// of channels c .. c + V - 1, body(e) handles the vector at element e.  The grid stride (gridDim * 256 vectors) is a multiple of
+// C / V whenever 256 * V % C == 0: the thread's channels are then fixed and loadp runs once.
+template <int V, typename LoadP, typename Body>
+__device__ __forceinline__ void for_each_vec(long nvec, int C, LoadP loadp, Body body) {
+    const bool fixed = ((256 * V) % C) == 0;
+    if (fixed) loadp((int)(((long)threadIdx.x * V) % C));
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
+        const long e = i * V;
+        if (!fixed) loadp((int)(e % C));
+        body(e);
+    }
+}
+
 // rows of the [M][C] matrix reduced by one workgroup: ~1024 workgroups for large M, never fewer than 16 rows (the per-lane
 // row loop is a chain of dependent-latency loads; at small M short chains in more workgroups win)
 static inline int red_rows(long M) { long r = (M + 1023) / 1024; if (r < 16) r = 16; return (int)((r + 15) / 16 * 16); }
 
-// ---------------------------------------------------------------- column partial sums: (sum x, sum x^2) per block
-template <typename T>
-__global__ __launch_bounds__(256) void col_stats_kernel(const T* __restrict__ x, long M, int C, int rows_per_block, float* __restrict__ part) {
-    constexpr int V = Vec<T>::N;
-    const int vc = C / V;                  // vector lanes along channels
-    const int rl = 256 / vc;               // row lanes
-    const int cv = threadIdx.x % vc, rr = threadIdx.x / vc;
+// ---------------------------------------------------------------- row-lane reduction: one partial row (s, q) per workgroup
+// A workgroup of 256 threads reduces rows [blockIdx.x * rows_per_block, ...) of an [M][C] matrix over the CS channels from cl0 (a
+// channel slice; CS = C, cl0 = 0 for the whole row): CS / V vector lanes along the channels x rl row lanes.  rowop(r, c, s, q) adds
+// what row r contributes at channels c .. c + V - 1 to the lane's sums; each lane takes its rows in order, then the row lanes
+// are combined through LDS ([rl][CS][2] floats of dynamic shared memory) in lane order: part[blockIdx.x][cl0 .. cl0 + CS][2].
+template <int V> __device__ __forceinline__ int row_lane_channel(int CS) { return (int)(threadIdx.x % (CS / V)) * V; }   // within the slice
+template <int V, typename RowOp>
+__device__ __forceinline__ void row_reduce(long M, int C, int CS, int cl0, int rows_per_block, float* __restrict__ part, RowOp rowop) {
+    const int vcs = CS / V;                // vector lanes along channels
+    const int rl = 256 / vcs;              // row lanes
+    const int cl = row_lane_channel<V>(CS), rr = threadIdx.x / vcs;
     long r0 = (long)blockIdx.x * rows_per_block;
     long r1 = r0 + rows_per_block; if (r1 > M) r1 = M;
     float s[V], q[V];
 #pragma unroll
     for (int i = 0; i < V; ++i) { s[i] = 0.f; q[i] = 0.f; }
     if (rr < rl)
-        for (long r = r0 + rr; r < r1; r += rl) {
-            float f[V]; vload<T>(x + r * C + cv * V, f);
-#pragma unroll
-            for (int i = 0; i < V; ++i) { s[i] += f[i]; q[i] += f[i] * f[i]; }
-        }
-    extern __shared__ float sm[];          // [rl][C][2]
+        for (long r = r0 + rr; r < r1; r += rl) rowop(r, cl0 + cl, s, q);
+    extern __shared__ float sm[];
     if (rr < rl)
 #pragma unroll
-        for (int i = 0; i < V; ++i) { sm[(rr * C + cv * V + i) * 2] = s[i]; sm[(rr * C + cv * V + i) * 2 + 1] = q[i]; }
+        for (int i = 0; i < V; ++i) { sm[(rr * CS + cl + i) * 2] = s[i]; sm[(rr * CS + cl + i) * 2 + 1] = q[i]; }
     __syncthreads();
-    for (int c = threadIdx.x; c < C; c += 256) {
+    for (int c = threadIdx.x; c < CS; c += 256) {
         float a = 0.f, b = 0.f;
-        for (int k = 0; k < rl; ++k) { a += sm[(k * C + c) * 2]; b += sm[(k * C + c) * 2 + 1]; }
-        part[((long)blockIdx.x * C + c) * 2] = a; part[((long)blockIdx.x * C + c) * 2 + 1] = b;
+        for (int k = 0; k < rl; ++k) { a += sm[(k * CS + c) * 2]; b += sm[(k * CS + c) * 2 + 1]; }
+        part[((long)blockIdx.x * C + cl0 + c) * 2] = a; part[((long)blockIdx.x * C + cl0 + c) * 2 + 1] = b;
     }
+}
+
+// column partial sums: (sum x, sum x^2) per block
+template <typename T>
+__global__ __launch_bounds__(256) void col_stats_kernel(const T* __restrict__ x, long M, int C, int rows_per_block, float* __restrict__ part) {
+    constexpr int V = Vec<T>::N;
+    row_reduce<V>(M, C, C, 0, rows_per_block, part, [&](long r, int c, float* s, float* q) {
+        float f[V]; vload<T>(x + r * C + c, f);
+#pragma unroll
+        for (int i = 0; i < V; ++i) { s[i] += f[i]; q[i] += f[i] * f[i]; }
+    });
 }
 
 // Fixed-order reduction of per-workgroup partials part[nparts][C][2] for CPW channels per workgroup of 1024 threads
@@ -101,16 +190,51 @@ __device__ __forceinline__ void reduce_parts_1024(const float* __restrict__ part
     s = 0; q = 0;
     if (pl == 0) for (int k = 0; k < 16; ++k) { s += sm[(k * CPW + cl) * 2]; q += sm[(k * CPW + cl) * 2 + 1]; }
 }
-static inline int finalize_cpw(int C) {
+static inline int finalize_cpw() {
     // channels per workgroup of the finalize launches: 2, 4 and 8 measure the same end to end (6.25-6.28 ms/step; the
     // launches sit at their ~5 us launch + cross-XCD read latency floor whatever their shape) -- 8 unless AB_BNFIN_CPW says so
     static const int force = getenv("AB_BNFIN_CPW") ? atoi(getenv("AB_BNFIN_CPW")) : 0;
-    (void)C;
     return (force == 2 || force == 4) ? force : 8;
 }
 
 // ---------------------------------------------------------------- BN finalize: partials -> scale/shift, saved stats
 // bnp: float [4][C] = scale (gamma*invstd), shift, mean, invstd.  running stats updated in place when non-null.
+struct BnChannel { float sc, sh, mean, invstd; double var, n; };   // n: the element count
+// one channel's parameters from its sums (s, q) = (sum x, sum x^2) over `count` elements
+__device__ __forceinline__ BnChannel bn_params_from_sums(double s, double q, long count, float g, float bt, float eps) {
+    BnChannel p;
+    p.n = (double)count;
+    double mean = s / p.n;
+    double var = q / p.n - mean * mean; if (var < 0) var = 0;
+    p.invstd = (float)(1.0 / sqrt(var + (double)eps));
+    p.sc = g * p.invstd; p.sh = bt - (float)mean * p.sc; p.mean = (float)mean; p.var = var;
+    return p;
+}
+// ... written to column c of bnp
+__device__ __forceinline__ void bn_store_params(const BnChannel& p, float* __restrict__ bnp, int C, int c) {
+    bnp[c] = p.sc; bnp[C + c] = p.sh; bnp[2 * C + c] = p.mean; bnp[3 * C + c] = p.invstd;
+}
+// ... folded into the running statistics, whose old values are (rm, rv); the variance as its unbiased estimate
+__device__ __forceinline__ void bn_update_running(const BnChannel& p, long count, float momentum, float rm, float rv, float* __restrict__ running_mean,
+                                                  float* __restrict__ running_var, int c) {
+    double unb = count > 1 ? p.var * p.n / (double)(count - 1) : p.var;
+    running_mean[c] = (1.f - momentum) * rm + momentum * p.mean;
+    running_var[c] = (1.f - momentum) * rv + momentum * (float)unb;
+}
+// eval mode: column c of bnp from the running statistics
+__device__ __forceinline__ void bn_eval_params_one(int C, int c, const float* gamma, const float* beta, const float* rm, const float* rv,
+                                                   float eps, float* bnp) {
+    float invstd = 1.f / sqrtf(rv[c] + eps);
+    float sc = gamma[c] * invstd;
+    bnp[c] = sc; bnp[C + c] = beta[c] - rm[c] * sc; bnp[2 * C + c] = rm[c]; bnp[3 * C + c] = invstd;
+}
+// the backward's sums of channel c: dbeta = sum dz, dgamma = sum dz * xhat, and both again as bwdp [2][C]
+__device__ __forceinline__ void bn_store_bwd_sums(double s, double q, float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                  float* __restrict__ bwdp, int C, int c) {
+    dbeta[c] = (float)s; dgamma[c] = (float)q;
+    bwdp[c] = (float)s; bwdp[C + c] = (float)q;
+}
+
 // block = CPW channels x 1024/CPW part-lanes, grid = ceil(C/CPW)
 template <int CPW>
 __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restrict__ part, int nparts, int C, long count,
@@ -126,16 +250,9 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
     if (fin) { g = gamma[c]; bt = beta[c]; if (running_mean) { rm = running_mean[c]; rv = running_var[c]; } }
     double s, q; reduce_parts_1024<CPW>(part, nparts, C, c, s, q, sm);
     if (fin) {
-        double mean = s / (double)count;
-        double var = q / (double)count - mean * mean; if (var < 0) var = 0;
-        float invstd = (float)(1.0 / sqrt(var + (double)eps));
-        float sc = g * invstd;
-        bnp[c] = sc; bnp[C + c] = bt - (float)mean * sc; bnp[2 * C + c] = (float)mean; bnp[3 * C + c] = invstd;
-        if (running_mean) {
-            double unb = count > 1 ? var * (double)count / (double)(count - 1) : var;
-            running_mean[c] = (1.f - momentum) * rm + momentum * (float)mean;
-            running_var[c] = (1.f - momentum) * rv + momentum * (float)unb;
-        }
+        const BnChannel p = bn_params_from_sums(s, q, count, g, bt, eps);
+        bn_store_params(p, bnp, C, c);
+        if (running_mean) bn_update_running(p, count, momentum, rm, rv, running_mean, running_var, c);
     }
 }
 
@@ -144,68 +261,85 @@ __global__ void bn_eval_params_kernel(int C, const float* gamma, const float* be
                                       float eps, float* bnp) {
     int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    float invstd = 1.f / sqrtf(rv[c] + eps);
-    float sc = gamma[c] * invstd;
-    bnp[c] = sc; bnp[C + c] = beta[c] - rm[c] * sc; bnp[2 * C + c] = rm[c]; bnp[3 * C + c] = invstd;
+    bn_eval_params_one(C, c, gamma, beta, rm, rv, eps, bnp);
 }
 
-// every BatchNorm of a network in ONE launch: desc[n][5] = (gamma offset, beta offset in `flat`; running_mean, running_var offset in
-// `stats`; output offset in `out`), C = desc[n][5 * .. ] -- see ab_bn_eval_params_batch
+// every BatchNorm of a network in ONE launch: desc[n][6] = (gamma offset, beta offset in `flat`; running_mean, running_var offset in
+// `stats`; output offset in `out`; C) -- see ab_bn_eval_params_batch
 __global__ void bn_eval_params_batch_kernel(const float* __restrict__ flat, const float* __restrict__ stats, const int* __restrict__ desc,
                                             float eps, float* __restrict__ out) {
     const int* d = desc + blockIdx.y * 6;
     const int C = d[5];
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const float* gamma = flat + d[0]; const float* beta = flat + d[1]; const float* rm = stats + d[2]; const float* rv = stats + d[3];
-    float* bnp = out + d[4];
-    float invstd = 1.f / sqrtf(rv[c] + eps);
-    float sc = gamma[c] * invstd;
-    bnp[c] = sc; bnp[C + c] = beta[c] - rm[c] * sc; bnp[2 * C + c] = rm[c]; bnp[3 * C + c] = invstd;
+    bn_eval_params_one(C, c, flat + d[0], flat + d[1], stats + d[2], stats + d[3], eps, out + d[4]);
 }
 
 // ---------------------------------------------------------------- BN apply (+residual) (+ReLU)
+// Forward elementwise body: f = [relu]( f*sc + sh [+ r] ) in fp32, the expression the folded conv epilogues and every backward mask
+// repeat.  RES says where the residual r comes from:
+enum {
+    RES_F32 = 0,       // none (res == NULL) or an fp32 tensor `res`
+    RES_PLANES = 1,    // its (hi, lo) planes res_hi, res_lo; `res` unused -- the block input need not exist in fp32
+    RES_RAWBN = 2,     // `res` is itself a raw conv output and the residual is res*sc2 + sh2 (the downsample branch, resnet.py:95-99:
+                       // its BatchNorm output is never materialised)
+    RES_ANY = 3        // RES_F32 or RES_PLANES, told apart by res_hi != NULL at run time (the 4-channel form)
+};
+// loads r; false: there is no residual
+template <int V, int RES>
+__device__ __forceinline__ bool load_res(const float* __restrict__ res, const bf16_t* __restrict__ res_hi, const bf16_t* __restrict__ res_lo,
+                                         long e, float* r) {
+    if (RES == RES_PLANES || (RES == RES_ANY && res_hi)) { load_planes<V>(res_hi, res_lo, e, r); return true; }
+    if (res) vload<float, V>(res + e, r);
+    return res != nullptr;
+}
+template <int V, int RES>
+__device__ __forceinline__ void bn_fwd_elem(float* f, float* r, bool has_res, const float* sc, const float* sh, const float* sc2, const float* sh2, int relu) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        float v = f[k] * sc[k] + sh[k];
+        if constexpr (RES == RES_RAWBN) r[k] = r[k] * sc2[k] + sh2[k];
+        if (has_res) v += r[k];
+        if (relu) v = fmaxf(v, 0.f);
+        f[k] = v;
+    }
+}
+// ... of the V fp32 elements at e, stored as fp32 `out` (optional) and as split planes
+template <int V, int RES>
+__device__ __forceinline__ void bn_fwd_x3(long e, const float* __restrict__ y, const float* __restrict__ res, const bf16_t* __restrict__ res_hi,
+                                          const bf16_t* __restrict__ res_lo, const float* sc, const float* sh, const float* sc2, const float* sh2,
+                                          int relu, float* __restrict__ out, bf16_t* __restrict__ hi, bf16_t* __restrict__ lo) {
+    float f[V], r[V];
+    vload<float, V>(y + e, f);
+    const bool has_res = load_res<V, RES>(res, res_hi, res_lo, e, r);
+    bn_fwd_elem<V, RES>(f, r, has_res, sc, sh, sc2, sh2, relu);
+    if (out) vstore<float, V>(out + e, f);
+    store_split<V>(hi, lo, e, f);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ y, const T* __restrict__ res,
                                                        const float* __restrict__ bnp, long nvec, int C, int relu,
                                                        T* __restrict__ out) {
     constexpr int V = Vec<T>::N;
-    // grid stride (gridDim*256 vectors) is a multiple of C/V whenever 256*V % C == 0: the thread's channels are fixed
-    const bool fixed = ((256 * V) % C) == 0;
     float sc[V], sh[V];
-    if (fixed) {
-        int c = (int)(((long)threadIdx.x * V) % C);
-#pragma unroll
-        for (int k = 0; k < V; ++k) { sc[k] = bnp[c + k]; sh[k] = bnp[C + c + k]; }
-    }
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-        long e = i * V;
-        if (!fixed) {
-            int c = (int)(e % C);
-#pragma unroll
-            for (int k = 0; k < V; ++k) { sc[k] = bnp[c + k]; sh[k] = bnp[C + c + k]; }
-        }
+    for_each_vec<V>(nvec, C, [&](int c) { load_scale_shift<V>(bnp, C, c, sc, sh); }, [&](long e) {
         float f[V]; vload<T>(y + e, f);
         float r[V];
         if (res) vload<T>(res + e, r);
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            float v = f[k] * sc[k] + sh[k];
-            if (res) v += r[k];
-            if (relu) v = fmaxf(v, 0.f);
-            f[k] = v;
-        }
+        bn_fwd_elem<V, RES_F32>(f, r, res != nullptr, sc, sh, nullptr, nullptr, relu);
         vstore<T>(out + e, f);
-    }
+    });
 }
 
-// gradient of the 3x3/2 max-pool input at pixel (n,h,w), channels cv*V..: sum over the <= 4 windows that cover the pixel
-// of dpool where the recorded winner is this pixel (what maxpool_bwd_kernel stores, rounded to T the same way)
+// ---------------------------------------------------------------- 3x3/2 max-pool gradient gathers (see the pooling kernels below)
+// gradient of the 3x3/2 max-pool input at row r = (n,h,w) of the [N*H*W][C] map, channels c .. c + V - 1: sum over the <= 4 windows
+// that cover the pixel of dpool where the recorded winner is this pixel (what maxpool_bwd_kernel stores, rounded to T the same way)
 template <typename T>
-__device__ __forceinline__ void pool_gather(const uint8_t* __restrict__ idx, const T* __restrict__ dpool, int n, int h, int w,
-                                            int H, int W, int C, int cv, float* acc) {
+__device__ __forceinline__ void pool_gather(const uint8_t* __restrict__ idx, const T* __restrict__ dpool, long r, int H, int W, int C, int c, float* acc) {
     constexpr int V = Vec<T>::N;
     const int Ho = H / 2, Wo = W / 2;
+    const int w = (int)(r % W); const long t = r / W; const int h = (int)(t % H), n = (int)(t / H);
 #pragma unroll
     for (int k = 0; k < V; ++k) acc[k] = 0.f;
     for (int ho = h / 2; ho <= (h + 1) / 2; ++ho) {
@@ -214,17 +348,8 @@ __device__ __forceinline__ void pool_gather(const uint8_t* __restrict__ idx, con
         for (int wo = w / 2; wo <= (w + 1) / 2; ++wo) {
             if (wo >= Wo) continue;
             int code = dh * 3 + (w - (wo * 2 - 1));
-            long o = (((long)n * Ho + ho) * Wo + wo) * C + cv * V;
-            uint8_t am[V];
-            if constexpr (V == 8) {
-                uint2 q = *(const uint2*)(idx + o);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { am[k] = (q.x >> (8 * k)) & 0xff; am[4 + k] = (q.y >> (8 * k)) & 0xff; }
-            } else {
-                uint32_t q = *(const uint32_t*)(idx + o);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) am[k] = (q >> (8 * k)) & 0xff;
-            }
+            long o = (((long)n * Ho + ho) * Wo + wo) * C + c;
+            uint32_t am[V]; unpack_winners<V>(idx + o, am);
             float g[V]; vload<T>(dpool + o, g);
 #pragma unroll
             for (int k = 0; k < V; ++k) if (am[k] == code) acc[k] += g[k];
@@ -233,8 +358,106 @@ __device__ __forceinline__ void pool_gather(const uint8_t* __restrict__ idx, con
 #pragma unroll
     for (int k = 0; k < V; ++k) acc[k] = round_to<T>(acc[k]);
 }
+// ... of the input row PAIR (2p, 2p+1) at column w, channels c .. c + V - 1 (acc0, acc1; not rounded): row 2p lies in pooled row p
+// only, row 2p+1 in p and p+1 -- the winners / gradients of pooled row p are loaded once for both (4 loads of each kind instead of 6)
+template <typename T, int V>
+__device__ __forceinline__ void pool_gather_pair(const uint8_t* __restrict__ idx, const T* __restrict__ dout, int n, int p, int w, int Ho, int Wo,
+                                                 int C, int c, float* acc0, float* acc1) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) { acc0[k] = 0.f; acc1[k] = 0.f; }
+#pragma unroll
+    for (int dp = 0; dp < 2; ++dp) {
+        const int ho = p + dp;
+        if (ho >= Ho) continue;
+        for (int wo = w / 2; wo <= (w + 1) / 2; ++wo) {
+            if (wo >= Wo) continue;
+            const int cw = w - (wo * 2 - 1);
+            const long o = (((long)n * Ho + ho) * Wo + wo) * C + c;
+            uint32_t am[V]; unpack_winners<V>(idx + o, am);
+            float g[V]; vload<T, V>(dout + o, g);
+            // window rows of pooled row ho: 2ho-1 .. 2ho+1.  dp = 0: input row 2p is its row 1, row 2p+1 its row 2;
+            // dp = 1: input row 2p+1 is row 0 of pooled row p+1.  (Selects, not `if (...) acc += g`: the conditional statement
+            // compiled to EXEC-masked branches with an element of g loaded under one of them, +1 % on pool_bwd_bn_apply_x3.)
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                const int a = (int)am[k];
+                if (dp == 0) {
+                    acc0[k] = (a == 3 + cw) ? acc0[k] + g[k] : acc0[k];
+                    acc1[k] = (a == 6 + cw) ? acc1[k] + g[k] : acc1[k];
+                } else {
+                    acc1[k] = (a == cw) ? acc1[k] + g[k] : acc1[k];
+                }
+            }
+        }
+    }
+}
 
 // ---------------------------------------------------------------- BN backward
+// Backward elementwise bodies, for V channels whose parameters sit in a BnBwd:
+//   relu_mask    dz = dout where the ReLU passed, else 0
+//   bn_bwd_sums  s += dz, q += dz * xhat                                  (pass 1)
+//   bn_bwd_dy    dy = gamma*invstd * (dz - mean(dz) - xhat * mean(dz*xhat))  (pass 2)
+enum { RELU_NONE = 0, RELU_OUT = 1, RELU_RECOMPUTE = 2 };      // the `relu` argument of the backward entry points
+template <int V> struct BnBwd { float ga[V], sh[V], mu[V], is[V], k1[V], k2[V]; };   // gamma*invstd, shift, mean, invstd, mean(dz), mean(dz*xhat)
+template <int V> __device__ __forceinline__ void load_bn_stats(BnBwd<V>& P, const float* __restrict__ bnp, int C, int c) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        P.ga[k] = bnp[c + k]; P.sh[k] = bnp[C + c + k];
+        P.mu[k] = bnp[2 * C + c + k]; P.is[k] = bnp[3 * C + c + k];
+    }
+}
+// ... and the means from the channel sums: sums [2][S] = (sum dz, sum dz * xhat), read from channel cs (bwdp with S = C and
+// cs = c, or the 64 channels of a workgroup's own finalize)
+template <int V>
+__device__ __forceinline__ void load_bwd_params(BnBwd<V>& P, const float* __restrict__ bnp, int C, int c, const float* sums, int S, int cs, float invM) {
+    load_bn_stats<V>(P, bnp, C, c);
+#pragma unroll
+    for (int k = 0; k < V; ++k) { P.k1[k] = sums[cs + k] * invM; P.k2[k] = sums[S + cs + k] * invM; }
+}
+// the stored activation for the relu == 1 mask: `out`, or the hi plane of the split activation (fp32 tensors only: same sign,
+// half the bytes of the fp32 copy)
+template <typename T, int V>
+__device__ __forceinline__ void load_relu_out(int relu, const T* __restrict__ out, const bf16_t* __restrict__ out_hi, long e, float* o) {
+    if (relu != RELU_OUT) return;
+    if (out_hi) vload<bf16_t, V>(out_hi + e, o); else vload<T, V>(out + e, o);
+}
+// g: dout -> dz.  relu == 1: the mask from the stored activation o; relu == 2: recomputed from y with bn_apply's own expression (same
+// f32 value that was clamped and stored), which saves reading the activation (o is not read); relu == 0: none
+template <int V> __device__ __forceinline__ void relu_mask(const BnBwd<V>& P, int relu, float* g, const float* o, const float* yy) {
+    if (relu == RELU_OUT) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) g[k] = (o[k] > 0.f) ? g[k] : 0.f;
+    } else if (relu == RELU_RECOMPUTE) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) g[k] = (yy[k] * P.ga[k] + P.sh[k] > 0.f) ? g[k] : 0.f;
+    }
+}
+template <int V> __device__ __forceinline__ void bn_bwd_sums(const BnBwd<V>& P, const float* dz, const float* yy, float* s, float* q) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) { s[k] += dz[k]; q[k] += dz[k] * ((yy[k] - P.mu[k]) * P.is[k]); }
+}
+template <int V> __device__ __forceinline__ void bn_bwd_dy(const BnBwd<V>& P, const float* dz, const float* yy, float* d) {
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        const float xhat = (yy[k] - P.mu[k]) * P.is[k];
+        d[k] = P.ga[k] * (dz[k] - P.k1[k] - xhat * P.k2[k]);
+    }
+}
+// pass 2 on the 8 fp32 elements at e, dy written as split planes (its only consumers are the data- and weight-gradient convs),
+// dz optionally as fp32 (the residual gradient)
+__device__ __forceinline__ void bn_bwd_x3(const BnBwd<8>& P, long e, const float* __restrict__ dout, const float* __restrict__ out,
+                                          const bf16_t* __restrict__ out_hi, const float* __restrict__ y, int relu, bf16_t* __restrict__ dy_hi,
+                                          bf16_t* __restrict__ dy_lo, float* __restrict__ dz_out) {
+    float g[8], o[8], yy[8], d[8];
+    vload<float, 8>(dout + e, g);
+    vload<float, 8>(y + e, yy);
+    load_relu_out<float, 8>(relu, out, out_hi, e, o);
+    relu_mask<8>(P, relu, g, o, yy);
+    bn_bwd_dy<8>(P, g, yy, d);
+    store_split<8>(dy_hi, dy_lo, e, d);
+    if (dz_out) vstore<float, 8>(dz_out + e, g);
+}
+
 // pass 1: dz = dout * (out > 0 if relu); partial sums of dz and dz * xhat per channel
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict__ dout, const T* __restrict__ out,
@@ -244,54 +467,18 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict_
                                                             const bf16_t* __restrict__ out_hi = nullptr) {
     constexpr int V = Vec<T>::N;
     // wide tensors (C / V > 256: the 2048-channel stage of the Bottleneck ResNets): gridDim.y slices of CS = C / gridDim.y channels
-    const int CS = C / (int)gridDim.y, vcs = CS / V, rl = 256 / vcs;
-    const int cv = (int)blockIdx.y * vcs + (int)(threadIdx.x % vcs), rr = threadIdx.x / vcs;
-    long r0 = (long)blockIdx.x * rows_per_block;
-    long r1 = r0 + rows_per_block; if (r1 > M) r1 = M;
-    float s[V], q[V], mean[V], istd[V], sc[V], sh[V];
-#pragma unroll
-    for (int i = 0; i < V; ++i) {
-        s[i] = 0.f; q[i] = 0.f; mean[i] = bnp[2 * C + cv * V + i]; istd[i] = bnp[3 * C + cv * V + i];
-        sc[i] = bnp[cv * V + i]; sh[i] = bnp[C + cv * V + i];
-    }
-    if (rr < rl)
-        for (long r = r0 + rr; r < r1; r += rl) {
-            long e = r * C + cv * V;
-            float g[V], o[V], yy[V];
-            if (pool_idx) {       // dout is the POOLED gradient: gather this pixel's share (fused max-pool backward)
-                int w = (int)(r % pW); long t = r / pW; int h = (int)(t % pH); int n = (int)(t / pH);
-                pool_gather<T>(pool_idx, dout, n, h, w, pH, pW, C, cv, g);
-            } else vload<T>(dout + e, g);
-            vload<T>(y + e, yy);
-            if (relu == 1) {
-                // out_hi (fp32 tensors only, V == 4): the ReLU mask from the hi plane of the split activation (same sign,
-                // half the bytes of the fp32 copy)
-                if (out_hi) {
-                    const uint2 h = *(const uint2*)(out_hi + e);
-                    o[0] = __uint_as_float(h.x << 16); o[1] = __uint_as_float(h.x & 0xffff0000u);
-                    if constexpr (V >= 4) { o[2] = __uint_as_float(h.y << 16); o[3] = __uint_as_float(h.y & 0xffff0000u); }
-                } else vload<T>(out + e, o);
-            }
-#pragma unroll
-            for (int i = 0; i < V; ++i) {
-                // relu == 2: the mask is recomputed from y with bn_apply's own expression (same f32 value that was
-                // clamped and stored), which saves reading the activation
-                const bool dead = relu == 1 ? !(o[i] > 0.f) : relu == 2 ? !(yy[i] * sc[i] + sh[i] > 0.f) : false;
-                float dz = dead ? 0.f : g[i];
-                s[i] += dz; q[i] += dz * ((yy[i] - mean[i]) * istd[i]);
-            }
-        }
-    extern __shared__ float sm[];
-    const int cl0 = (int)blockIdx.y * CS;                 // first channel of this slice
-    if (rr < rl)
-#pragma unroll
-        for (int i = 0; i < V; ++i) { sm[(rr * CS + cv * V + i - cl0) * 2] = s[i]; sm[(rr * CS + cv * V + i - cl0) * 2 + 1] = q[i]; }
-    __syncthreads();
-    for (int c = threadIdx.x; c < CS; c += 256) {
-        float a = 0.f, b = 0.f;
-        for (int k = 0; k < rl; ++k) { a += sm[(k * CS + c) * 2]; b += sm[(k * CS + c) * 2 + 1]; }
-        part[((long)blockIdx.x * C + cl0 + c) * 2] = a; part[((long)blockIdx.x * C + cl0 + c) * 2 + 1] = b;
-    }
+    const int CS = C / (int)gridDim.y, cl0 = (int)blockIdx.y * CS;
+    BnBwd<V> P; load_bn_stats<V>(P, bnp, C, cl0 + row_lane_channel<V>(CS));
+    row_reduce<V>(M, C, CS, cl0, rows_per_block, part, [&](long r, int c, float* s, float* q) {
+        const long e = r * C + c;
+        float g[V], o[V], yy[V];
+        if (pool_idx) pool_gather<T>(pool_idx, dout, r, pH, pW, C, c, g);   // dout is the POOLED gradient: gather this pixel's share (fused max-pool backward)
+        else vload<T>(dout + e, g);
+        vload<T>(y + e, yy);
+        load_relu_out<T, V>(relu, out, out_hi, e, o);
+        relu_mask<V>(P, relu, g, o, yy);
+        bn_bwd_sums<V>(P, g, yy, s, q);
+    });
 }
 
 // reduce partials -> dgamma, dbeta (written to the flat grad buffer) and bwdp[2][C] = (sum dz, sum dz*xhat)
@@ -303,13 +490,10 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __re
     const int c = blockIdx.x * CPW + cl;
     __shared__ double sm[16 * CPW * 2];
     double s, q; reduce_parts_1024<CPW>(part, nparts, C, c, s, q, sm);
-    if (pl == 0 && c < C) {
-        dbeta[c] = (float)s; dgamma[c] = (float)q;
-        bwdp[c] = (float)s; bwdp[C + c] = (float)q;
-    }
+    if (pl == 0 && c < C) bn_store_bwd_sums(s, q, dgamma, dbeta, bwdp, C, c);
 }
 
-// pass 2: dy = gamma*invstd * (dz - mean(dz) - xhat * mean(dz*xhat));  optionally also writes dz (residual gradient)
+// pass 2: dy;  optionally also writes dz (residual gradient)
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__ dout, const T* __restrict__ out,
                                                            const T* __restrict__ y, const float* __restrict__ bnp,
@@ -318,38 +502,18 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
                                                            const uint8_t* __restrict__ pool_idx = nullptr, int pH = 0, int pW = 0) {
     constexpr int V = Vec<T>::N;
     const float invM = 1.f / (float)M;
-    const bool fixed = ((256 * V) % C) == 0;
-    float ga[V], sh[V], mu[V], is[V], k1[V], k2[V];    // gamma*invstd, shift, mean, invstd, mean(dz), mean(dz*xhat)
-    auto loadp = [&](int c) {
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            ga[k] = bnp[c + k]; sh[k] = bnp[C + c + k]; mu[k] = bnp[2 * C + c + k]; is[k] = bnp[3 * C + c + k];
-            k1[k] = bwdp[c + k] * invM; k2[k] = bwdp[C + c + k] * invM;
-        }
-    };
-    if (fixed) loadp((int)(((long)threadIdx.x * V) % C));
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-        long e = i * V;
-        if (!fixed) loadp((int)(e % C));
+    BnBwd<V> P;
+    for_each_vec<V>(nvec, C, [&](int c) { load_bwd_params<V>(P, bnp, C, c, bwdp, C, c, invM); }, [&](long e) {
         float g[V], o[V], yy[V], d[V];
-        if (pool_idx) {
-            long r = e / C; int cvv = (int)(e - r * C) / V;
-            int w = (int)(r % pW); long t = r / pW; int h = (int)(t % pH); int n = (int)(t / pH);
-            pool_gather<T>(pool_idx, dout, n, h, w, pH, pW, C, cvv, g);
-        } else vload<T>(dout + e, g);
+        if (pool_idx) { const long r = e / C; pool_gather<T>(pool_idx, dout, r, pH, pW, C, (int)(e - r * C), g); }
+        else vload<T>(dout + e, g);
         vload<T>(y + e, yy);
-        if (relu == 1) vload<T>(out + e, o);
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            const bool dead = relu == 1 ? !(o[k] > 0.f) : relu == 2 ? !(yy[k] * ga[k] + sh[k] > 0.f) : false;
-            float dz = dead ? 0.f : g[k];
-            float xhat = (yy[k] - mu[k]) * is[k];
-            d[k] = ga[k] * (dz - k1[k] - xhat * k2[k]);
-            g[k] = dz;
-        }
+        load_relu_out<T, V>(relu, out, nullptr, e, o);
+        relu_mask<V>(P, relu, g, o, yy);
+        bn_bwd_dy<V>(P, g, yy, d);
         vstore<T>(dy + e, d);
         if (dz_out) vstore<T>(dz_out + e, g);
-    }
+    });
 }
 
 // ---------------------------------------------------------------- elementwise add (gradient accumulation)
@@ -382,12 +546,9 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ 
         const int wo = (int)(col / (unsigned)vc), cv = (int)(col - (unsigned)wo * vc);
         const int n = blockIdx.z, ho = blockIdx.y;
         const long i = (((long)n * Ho + ho) * Wo + wo) * vc + cv;
-        float m[V]; uint8_t am[V];
+        float m[V]; uint32_t am[V];
         float sc[V], sh[V];
-        if (bnp) {
-#pragma unroll
-            for (int k = 0; k < V; ++k) { sc[k] = bnp[cv * V + k]; sh[k] = bnp[C + cv * V + k]; }
-        }
+        if (bnp) load_scale_shift<V>(bnp, C, cv * V, sc, sh);
 #pragma unroll
         for (int k = 0; k < V; ++k) { m[k] = -INFINITY; am[k] = 0; }
 #pragma unroll
@@ -402,28 +563,15 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ 
                     for (int k = 0; k < V; ++k) f[k] = round_to<T>(fmaxf(f[k] * sc[k] + sh[k], 0.f));
                 }
 #pragma unroll
-                for (int k = 0; k < V; ++k) if (f[k] > m[k]) { m[k] = f[k]; am[k] = (uint8_t)(dh * 3 + dw); }
+                for (int k = 0; k < V; ++k) if (f[k] > m[k]) { m[k] = f[k]; am[k] = dh * 3 + dw; }
             }
         }
         vstore<T>(out + i * V, m);
         if constexpr (V == 4) {
-            if (out_hi) {        // fp32 path: the pooled tensor also as (hi, lo) planes for the split-bf16 convolutions that read it
-                const uint32_t h0 = pack_bf16x2(m[0], m[1]), h1 = pack_bf16x2(m[2], m[3]);
-                const uint32_t l0 = pack_bf16x2(m[0] - __uint_as_float(h0 << 16), m[1] - __uint_as_float(h0 & 0xffff0000u));
-                const uint32_t l1 = pack_bf16x2(m[2] - __uint_as_float(h1 << 16), m[3] - __uint_as_float(h1 & 0xffff0000u));
-                *(uint2*)(out_hi + i * 4) = make_uint2(h0, h1);
-                *(uint2*)(out_lo + i * 4) = make_uint2(l0, l1);
-            }
+            // fp32 path: the pooled tensor also as (hi, lo) planes for the split-bf16 convolutions that read it
+            if (out_hi) store_split<4>(out_hi, out_lo, i * 4, m);
         }
-        if (idx) {
-            if constexpr (V == 8) {
-                uint2 o; o.x = am[0] | (am[1] << 8) | (am[2] << 16) | ((uint32_t)am[3] << 24);
-                o.y = am[4] | (am[5] << 8) | (am[6] << 16) | ((uint32_t)am[7] << 24);
-                *(uint2*)(idx + i * V) = o;
-            } else {
-                *(uint32_t*)(idx + i * V) = am[0] | (am[1] << 8) | (am[2] << 16) | ((uint32_t)am[3] << 24);
-            }
-        }
+        if (idx) pack_winners<V>(idx + i * V, am);
     }
 }
 template <typename T>
@@ -431,46 +579,14 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const uint8_t* __restr
                                                           int N, int H, int W, int C, T* __restrict__ dx) {
     constexpr int V = Vec<T>::N;
     const int Ho = H / 2, Wo = W / 2, vc = C / V;
-    // grid (ceil(W*vc / 256), H/2, N): a thread owns one channel vector of the input row PAIR (2p, 2p+1): row 2p lies in pooled
-    // row p only, row 2p+1 in p and p+1 -- the winners / gradients of pooled row p are loaded once for both (4 loads of each kind
-    // instead of 6, half the workgroups); 32-bit index math only
+    // grid (ceil(W*vc / 256), H/2, N): a thread owns one channel vector of the input row PAIR (2p, 2p+1) -- half the workgroups of
+    // one row per thread; 32-bit index math only
     const unsigned col = blockIdx.x * 256 + threadIdx.x;
     if (col < (unsigned)(W * vc)) {
         const int w = (int)(col / (unsigned)vc), cv = (int)(col - (unsigned)w * vc);
         const int n = blockIdx.z, p = blockIdx.y;
         float acc0[V], acc1[V];
-#pragma unroll
-        for (int k = 0; k < V; ++k) { acc0[k] = 0.f; acc1[k] = 0.f; }
-#pragma unroll
-        for (int dp = 0; dp < 2; ++dp) {
-            const int ho = p + dp;
-            if (ho >= Ho) continue;
-            for (int wo = w / 2; wo <= (w + 1) / 2; ++wo) {
-                if (wo >= Wo) continue;
-                const int cw = w - (wo * 2 - 1);
-                const long o = (((long)n * Ho + ho) * Wo + wo) * C + cv * V;
-                uint8_t am[V];
-                if constexpr (V == 8) {
-                    uint2 q = *(const uint2*)(idx + o);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) { am[k] = (q.x >> (8 * k)) & 0xff; am[4 + k] = (q.y >> (8 * k)) & 0xff; }
-                } else {
-                    uint32_t q = *(const uint32_t*)(idx + o);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) am[k] = (q >> (8 * k)) & 0xff;
-                }
-                float g[V]; vload<T>(dout + o, g);
-                // window rows of pooled row ho: 2ho-1 .. 2ho+1.  dp = 0: input row 2p is its row 1, row 2p+1 its row 2;
-                // dp = 1: input row 2p+1 is row 0 of pooled row p+1
-                if (dp == 0) {
-#pragma unroll
-                    for (int k = 0; k < V; ++k) { if (am[k] == 3 + cw) acc0[k] += g[k]; if (am[k] == 6 + cw) acc1[k] += g[k]; }
-                } else {
-#pragma unroll
-                    for (int k = 0; k < V; ++k) if (am[k] == cw) acc1[k] += g[k];
-                }
-            }
-        }
+        pool_gather_pair<T, V>(idx, dout, n, p, w, Ho, Wo, C, cv * V, acc0, acc1);
         const long i = (((long)n * H + 2 * p) * W + w) * vc + cv;
         vstore<T>(dx + i * V, acc0);
         vstore<T>(dx + (i + (long)W * vc) * V, acc1);
@@ -492,48 +608,24 @@ __global__ __launch_bounds__(256) void pool_bwd_bn_reduce_kernel(const uint8_t* 
     const bool ok = col < (unsigned)(W * vc);
     const int w = ok ? (int)(col / (unsigned)vc) : 0, cv = ok ? (int)(col - (unsigned)w * vc) : 0;
     const int n = blockIdx.z;
-    float sc[4], sh[4], mean[4], istd[4], s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        sc[k] = bnp[cv * 4 + k]; sh[k] = bnp[C + cv * 4 + k]; mean[k] = bnp[2 * C + cv * 4 + k]; istd[k] = bnp[3 * C + cv * 4 + k];
-    }
+    float s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
+    BnBwd<4> P; load_bn_stats<4>(P, bnp, C, cv * 4);
     if (ok)
         for (int rp = 0; rp < RP; ++rp) {
             const int p = blockIdx.y * RP + rp;
             if (p >= Ho) break;
-            float acc0[4] = {0.f, 0.f, 0.f, 0.f}, acc1[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int dp = 0; dp < 2; ++dp) {
-                const int ho = p + dp;
-                if (ho >= Ho) continue;
-                for (int wo = w / 2; wo <= (w + 1) / 2; ++wo) {
-                    if (wo >= Wo) continue;
-                    const int cw = w - (wo * 2 - 1);
-                    const long o = (((long)n * Ho + ho) * Wo + wo) * C + cv * 4;
-                    const uint32_t qd = *(const uint32_t*)(idx + o);
-                    const float4 g4 = *(const float4*)(dout + o);
-                    const float g[4] = {g4.x, g4.y, g4.z, g4.w};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int am = (qd >> (8 * k)) & 0xff;
-                        if (dp == 0) { if (am == 3 + cw) acc0[k] += g[k]; if (am == 6 + cw) acc1[k] += g[k]; }
-                        else if (am == cw) acc1[k] += g[k];
-                    }
-                }
-            }
+            float acc0[4], acc1[4], ya[4], yb[4];
+            pool_gather_pair<float, 4>(idx, dout, n, p, w, Ho, Wo, C, cv * 4, acc0, acc1);
             const long i = ((((long)n * H + 2 * p) * W + w) * vc + cv) * 4;
-            const float4 y0 = *(const float4*)(y + i), y1 = *(const float4*)(y + i + (long)W * C);
-            const float ya[4] = {y0.x, y0.y, y0.z, y0.w}, yb[4] = {y1.x, y1.y, y1.z, y1.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                acc0[k] = (ya[k] * sc[k] + sh[k] > 0.f) ? acc0[k] : 0.f;
-                acc1[k] = (yb[k] * sc[k] + sh[k] > 0.f) ? acc1[k] : 0.f;
-                s[k] += acc0[k]; q[k] += acc0[k] * ((ya[k] - mean[k]) * istd[k]);
-                s[k] += acc1[k]; q[k] += acc1[k] * ((yb[k] - mean[k]) * istd[k]);
-            }
+            vload<float, 4>(y + i, ya);
+            vload<float, 4>(y + i + (long)W * C, yb);
+            relu_mask<4>(P, RELU_RECOMPUTE, acc0, nullptr, ya);
+            relu_mask<4>(P, RELU_RECOMPUTE, acc1, nullptr, yb);
+            bn_bwd_sums<4>(P, acc0, ya, s, q);
+            bn_bwd_sums<4>(P, acc1, yb, s, q);
             if constexpr (WRITE_DZ) {
-                *(float4*)(dz + i) = make_float4(acc0[0], acc0[1], acc0[2], acc0[3]);
-                *(float4*)(dz + i + (long)W * C) = make_float4(acc1[0], acc1[1], acc1[2], acc1[3]);
+                vstore<float, 4>(dz + i, acc0);
+                vstore<float, 4>(dz + i + (long)W * C, acc1);
             }
         }
     // threads sharing cv: tid % vc (vc divides 256 for C = 64 .. 1024); fixed-order combine
@@ -700,33 +792,10 @@ __global__ __launch_bounds__(256) void colsum_finalize_kernel(const float* __res
     if (pl == 0 && c < C) { for (int k = 1; k < 32; ++k) s += sm[k][cl]; out[c] = (float)s; }
 }
 
-// ================================================================ split-bf16 ("bf16x3") producers
-// The fp32 elementwise passes that feed a convolution write its operand directly as (hi, lo) bf16 planes (conv_x3.hip):
-// same bytes as the fp32 tensor they replace, and no separate split pass.  8 channels per thread.
-__device__ __forceinline__ void store_split8(bf16_t* __restrict__ hi, bf16_t* __restrict__ lo, long e, const float* f) {
-    uint32_t h[4], l[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        h[k] = pack_bf16x2(f[2 * k], f[2 * k + 1]);
-        l[k] = pack_bf16x2(f[2 * k] - __uint_as_float(h[k] << 16), f[2 * k + 1] - __uint_as_float(h[k] & 0xffff0000u));
-    }
-    *(uint4*)(hi + e) = make_uint4(h[0], h[1], h[2], h[3]);
-    *(uint4*)(lo + e) = make_uint4(l[0], l[1], l[2], l[3]);
-}
-__device__ __forceinline__ void load8(const float* __restrict__ p, float* f) {
-    const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
-    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-__device__ __forceinline__ void store8(float* __restrict__ p, const float* f) {
-    *(float4*)p = make_float4(f[0], f[1], f[2], f[3]); *(float4*)(p + 4) = make_float4(f[4], f[5], f[6], f[7]);
-}
-
-// out = [relu]( y*scale + shift [+ res] ) -> fp32 `out` (optional) and split planes
-// res_bnp != NULL: `res` is itself a raw conv output and the residual is res*scale2 + shift2 (the downsample branch,
-// resnet.py:95-99: its BatchNorm output is never materialised)
+// ================================================================ split-bf16 ("bf16x3") producers: fp32 in, 8 channels per thread
+// out = [relu]( y*scale + shift [+ res] ) -> fp32 `out` (optional) and split planes; the residual forms: RES_* above
 // (RESBN is a template parameter: as a run-time branch the second parameter set doubled the time of EVERY launch of this kernel,
 // 540 -> 1 005 us per step over its 34 launches)
-// RESPL: the residual arrives as its (hi, lo) planes (res_hi, res_lo; `res` unused) -- the block input need not exist in fp32.
 template <bool RESBN, bool RESPL = false>
 __global__ __launch_bounds__(256) void bn_apply_x3_kernel(const float* __restrict__ y, const float* __restrict__ res,
                                                           const float* __restrict__ bnp, long nvec, int C, int relu,
@@ -734,131 +803,37 @@ __global__ __launch_bounds__(256) void bn_apply_x3_kernel(const float* __restric
                                                           const float* __restrict__ res_bnp = nullptr,
                                                           const bf16_t* __restrict__ res_hi = nullptr,
                                                           const bf16_t* __restrict__ res_lo = nullptr) {
-    const bool fixed = ((256 * 8) % C) == 0;
+    constexpr int RES = RESPL ? RES_PLANES : RESBN ? RES_RAWBN : RES_F32;
     float sc[8], sh[8], sc2[RESBN ? 8 : 1], sh2[RESBN ? 8 : 1];
-    if (fixed) {
-        const int c = (int)(((long)threadIdx.x * 8) % C);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { sc[k] = bnp[c + k]; sh[k] = bnp[C + c + k]; }
-        if constexpr (RESBN) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { sc2[k] = res_bnp[c + k]; sh2[k] = res_bnp[C + c + k]; }
-        }
-    }
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-        const long e = i * 8;
-        if (!fixed) {
-            const int c = (int)(e % C);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { sc[k] = bnp[c + k]; sh[k] = bnp[C + c + k]; }
-            if constexpr (RESBN) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { sc2[k] = res_bnp[c + k]; sh2[k] = res_bnp[C + c + k]; }
-            }
-        }
-        float f[8], r[8];
-        load8(y + e, f);
-        if constexpr (RESPL) {
-            const uint4 h4 = *(const uint4*)(res_hi + e), l4 = *(const uint4*)(res_lo + e);
-            const uint32_t hw[4] = {h4.x, h4.y, h4.z, h4.w}, lw[4] = {l4.x, l4.y, l4.z, l4.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                r[2 * k] = __uint_as_float(hw[k] << 16) + __uint_as_float(lw[k] << 16);
-                r[2 * k + 1] = __uint_as_float(hw[k] & 0xffff0000u) + __uint_as_float(lw[k] & 0xffff0000u);
-            }
-        } else if (res) load8(res + e, r);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            float v = f[k] * sc[k] + sh[k];
-            if constexpr (RESBN) r[k] = r[k] * sc2[k] + sh2[k];
-            if (RESPL || res) v += r[k];
-            if (relu) v = fmaxf(v, 0.f);
-            f[k] = v;
-        }
-        if (out) store8(out + e, f);
-        store_split8(hi, lo, e, f);
-    }
+    for_each_vec<8>(nvec, C, [&](int c) {
+        load_scale_shift<8>(bnp, C, c, sc, sh);
+        if constexpr (RESBN) load_scale_shift<8>(res_bnp, C, c, sc2, sh2);
+    }, [&](long e) { bn_fwd_x3<8, RES>(e, y, res, res_hi, res_lo, sc, sh, sc2, sh2, relu, out, hi, lo); });
 }
 
 // ... for C % 8 == 4 (no layer of the models: the route of a convolution whose fold the conv kernels refuse, and the head with a channel
-// count that is a multiple of 4 only): 4 channels per thread, the same expressions in the same order, so the same bits as the
-// 8-channel form and as the affine epilogues of the convolutions
+// count that is a multiple of 4 only): 4 channels per thread
 __global__ __launch_bounds__(256) void bn_apply_x3_c4_kernel(const float* __restrict__ y, const float* __restrict__ res,
                                                              const float* __restrict__ bnp, long nvec, int C, int relu,
                                                              float* __restrict__ out, bf16_t* __restrict__ hi, bf16_t* __restrict__ lo,
                                                              const bf16_t* __restrict__ res_hi, const bf16_t* __restrict__ res_lo) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
         const long e = i * 4;
-        const int c = (int)(e % C);
-        const float4 f4 = *(const float4*)(y + e);
-        float f[4] = {f4.x, f4.y, f4.z, f4.w}, r[4] = {0.f, 0.f, 0.f, 0.f};
-        if (res_hi) {
-            const uint2 h2 = *(const uint2*)(res_hi + e), l2 = *(const uint2*)(res_lo + e);
-            r[0] = __uint_as_float(h2.x << 16) + __uint_as_float(l2.x << 16);
-            r[1] = __uint_as_float(h2.x & 0xffff0000u) + __uint_as_float(l2.x & 0xffff0000u);
-            r[2] = __uint_as_float(h2.y << 16) + __uint_as_float(l2.y << 16);
-            r[3] = __uint_as_float(h2.y & 0xffff0000u) + __uint_as_float(l2.y & 0xffff0000u);
-        } else if (res) {
-            const float4 r4 = *(const float4*)(res + e);
-            r[0] = r4.x; r[1] = r4.y; r[2] = r4.z; r[3] = r4.w;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float v = f[k] * bnp[c + k] + bnp[C + c + k];
-            if (res_hi || res) v += r[k];
-            if (relu) v = fmaxf(v, 0.f);
-            f[k] = v;
-        }
-        if (out) *(float4*)(out + e) = make_float4(f[0], f[1], f[2], f[3]);
-        const uint32_t h0 = pack_bf16x2(f[0], f[1]), h1 = pack_bf16x2(f[2], f[3]);
-        *(uint2*)(hi + e) = make_uint2(h0, h1);
-        *(uint2*)(lo + e) = make_uint2(pack_bf16x2(f[0] - __uint_as_float(h0 << 16), f[1] - __uint_as_float(h0 & 0xffff0000u)),
-                                       pack_bf16x2(f[2] - __uint_as_float(h1 << 16), f[3] - __uint_as_float(h1 & 0xffff0000u)));
+        float sc[4], sh[4]; load_scale_shift<4>(bnp, C, (int)(e % C), sc, sh);
+        bn_fwd_x3<4, RES_ANY>(e, y, res, res_hi, res_lo, sc, sh, nullptr, nullptr, relu, out, hi, lo);
     }
 }
 
-// BatchNorm-backward pass 2 with dy written as split planes (its only consumers are the data- and weight-gradient convs)
+// BatchNorm-backward pass 2 with dy written as split planes
 __global__ __launch_bounds__(256) void bn_bwd_apply_x3_kernel(const float* __restrict__ dout, const float* __restrict__ out,
                                                               const float* __restrict__ y, const float* __restrict__ bnp,
                                                               const float* __restrict__ bwdp, long nvec, int C, long M, int relu,
                                                               bf16_t* __restrict__ dy_hi, bf16_t* __restrict__ dy_lo,
                                                               float* __restrict__ dz_out, const bf16_t* __restrict__ out_hi) {
     const float invM = 1.f / (float)M;
-    const bool fixed = ((256 * 8) % C) == 0;
-    float ga[8], sh[8], mu[8], is[8], k1[8], k2[8];
-    auto loadp = [&](int c) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            ga[k] = bnp[c + k]; sh[k] = bnp[C + c + k]; mu[k] = bnp[2 * C + c + k]; is[k] = bnp[3 * C + c + k];
-            k1[k] = bwdp[c + k] * invM; k2[k] = bwdp[C + c + k] * invM;
-        }
-    };
-    if (fixed) loadp((int)(((long)threadIdx.x * 8) % C));
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-        const long e = i * 8;
-        if (!fixed) loadp((int)(e % C));
-        float g[8], o[8], yy[8], d[8];
-        load8(dout + e, g);
-        load8(y + e, yy);
-        if (relu == 1) {
-            if (out_hi) {
-                const uint4 h = *(const uint4*)(out_hi + e);
-                const uint32_t hw[4] = {h.x, h.y, h.z, h.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { o[2 * k] = __uint_as_float(hw[k] << 16); o[2 * k + 1] = __uint_as_float(hw[k] & 0xffff0000u); }
-            } else load8(out + e, o);
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const bool dead = relu == 1 ? !(o[k] > 0.f) : relu == 2 ? !(yy[k] * ga[k] + sh[k] > 0.f) : false;
-            const float dz = dead ? 0.f : g[k];
-            const float xhat = (yy[k] - mu[k]) * is[k];
-            d[k] = ga[k] * (dz - k1[k] - xhat * k2[k]);
-            g[k] = dz;
-        }
-        store_split8(dy_hi, dy_lo, e, d);
-        if (dz_out) store8(dz_out + e, g);
-    }
+    BnBwd<8> P;
+    for_each_vec<8>(nvec, C, [&](int c) { load_bwd_params<8>(P, bnp, C, c, bwdp, C, c, invM); },
+                    [&](long e) { bn_bwd_x3(P, e, dout, out, out_hi, y, relu, dy_hi, dy_lo, dz_out); });
 }
 
 // ---------------------------------------------------------------- BatchNorm finalize INSIDE the apply passes (round 4)
@@ -869,7 +844,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_x3_kernel(const float* __res
 // channels (256 B of every pixel's fp32 row, 128 B of each plane -- whole cache lines) over a strip of pixels, so its prologue reads only
 // rows x 64 x 8 bytes (16 - 128 KB from L2) with 4 row-lanes per channel, fixed summation order (rows r = lane, lane + 4, ... in a double
 // each, then the four lanes in order): deterministic.  The workgroup of pixel strip 0 writes bnp / the running statistics / dgamma, dbeta
-// for its slice.  Arithmetic of the parameters and of the elementwise body: bn_finalize_kernel / bn_apply_x3_kernel / bn_bwd_apply_x3_kernel.
+// for its slice.
 #define BNFIN_MAX_ROWS 64
 #define BNFIN_SLICE 64
 
@@ -884,73 +859,44 @@ __device__ __forceinline__ void bnfin_reduce(const float* __restrict__ part, int
     s = ((sm[cl * 2] + sm[(64 + cl) * 2]) + sm[(128 + cl) * 2]) + sm[(192 + cl) * 2];
     q = ((sm[cl * 2 + 1] + sm[(64 + cl) * 2 + 1]) + sm[(128 + cl) * 2 + 1]) + sm[(192 + cl) * 2 + 1];
 }
+// the workgroup's place: channel slice from c0, pixel strip `strip` of `nstrips`; a thread takes channels c0 + j * 8 .. of the pixels
+// strip * 32 + pl, + nstrips * 32, ... (8 channel groups of a pixel, 32 pixels per pass)
+struct BnFinTile { int c0, strip, nstrips, j, pl; };
+__device__ __forceinline__ BnFinTile bnfin_tile(int C) {
+    const int nsl = C / BNFIN_SLICE;
+    return {(int)(blockIdx.x % nsl) * BNFIN_SLICE, (int)(blockIdx.x / nsl), (int)(gridDim.x / nsl), (int)(threadIdx.x & 7), (int)(threadIdx.x >> 3)};
+}
 
 struct BnFinArgs {
     const float* part; int nparts; long count; const float* gamma; const float* beta; float eps, momentum;
     float* running_mean; float* running_var; float* bnp;      // bnp [4][C]: written by the strip-0 workgroups
 };
 
-// RES: 0 no residual / fp32 residual `res`, 1 residual as (hi, lo) planes, 2 `res` is a raw conv output normalised by res_bnp on the fly
+// RES: RES_F32, RES_PLANES or RES_RAWBN
 template <int RES>
 __global__ __launch_bounds__(256) void bn_fin_apply_x3_kernel(BnFinArgs fa, const float* __restrict__ y, const float* __restrict__ res,
                                                               const bf16_t* __restrict__ res_hi, const bf16_t* __restrict__ res_lo,
                                                               const float* __restrict__ res_bnp, long M, int C, int relu,
                                                               float* __restrict__ out, bf16_t* __restrict__ hi, bf16_t* __restrict__ lo) {
     __shared__ double sm[4 * 64 * 2];
-    __shared__ float par[2][BNFIN_SLICE];
-    const int nsl = C / BNFIN_SLICE, slice = blockIdx.x % nsl, strip = blockIdx.x / nsl, nstrips = gridDim.x / nsl;
-    const int c0 = slice * BNFIN_SLICE;
-    double s, q; bnfin_reduce(fa.part, fa.nparts, C, c0, sm, s, q);
+    __shared__ float par[2][BNFIN_SLICE];          // (scale, shift) of the slice: a bnp of 64 channels
+    const BnFinTile t = bnfin_tile(C);
+    double s, q; bnfin_reduce(fa.part, fa.nparts, C, t.c0, sm, s, q);
     if (threadIdx.x < 64) {
-        const int c = c0 + threadIdx.x;
-        const float g = fa.gamma[c], bt = fa.beta[c];
-        double mean = s / (double)fa.count;
-        double var = q / (double)fa.count - mean * mean; if (var < 0) var = 0;
-        float invstd = (float)(1.0 / sqrt(var + (double)fa.eps));
-        float sc = g * invstd, sh = bt - (float)mean * sc;
-        par[0][threadIdx.x] = sc; par[1][threadIdx.x] = sh;
-        if (strip == 0) {
-            fa.bnp[c] = sc; fa.bnp[C + c] = sh; fa.bnp[2 * C + c] = (float)mean; fa.bnp[3 * C + c] = invstd;
-            if (fa.running_mean) {
-                double unb = fa.count > 1 ? var * (double)fa.count / (double)(fa.count - 1) : var;
-                fa.running_mean[c] = (1.f - fa.momentum) * fa.running_mean[c] + fa.momentum * (float)mean;
-                fa.running_var[c] = (1.f - fa.momentum) * fa.running_var[c] + fa.momentum * (float)unb;
-            }
+        const int c = t.c0 + threadIdx.x;
+        const BnChannel p = bn_params_from_sums(s, q, fa.count, fa.gamma[c], fa.beta[c], fa.eps);
+        par[0][threadIdx.x] = p.sc; par[1][threadIdx.x] = p.sh;
+        if (t.strip == 0) {
+            bn_store_params(p, fa.bnp, C, c);
+            if (fa.running_mean) bn_update_running(p, fa.count, fa.momentum, fa.running_mean[c], fa.running_var[c], fa.running_mean, fa.running_var, c);
         }
     }
     __syncthreads();
-    const int j = threadIdx.x & 7, pl = threadIdx.x >> 3;             // 8 channel groups of a pixel, 32 pixels per pass
-    float sc[8], sh[8], sc2[RES == 2 ? 8 : 1], sh2[RES == 2 ? 8 : 1];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { sc[k] = par[0][j * 8 + k]; sh[k] = par[1][j * 8 + k]; }
-    if constexpr (RES == 2) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { sc2[k] = res_bnp[c0 + j * 8 + k]; sh2[k] = res_bnp[C + c0 + j * 8 + k]; }
-    }
-    for (long p = (long)strip * 32 + pl; p < M; p += (long)nstrips * 32) {
-        const long e = p * C + c0 + j * 8;
-        float f[8], r[8];
-        load8(y + e, f);
-        if constexpr (RES == 1) {
-            const uint4 h4 = *(const uint4*)(res_hi + e), l4 = *(const uint4*)(res_lo + e);
-            const uint32_t hw[4] = {h4.x, h4.y, h4.z, h4.w}, lw[4] = {l4.x, l4.y, l4.z, l4.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                r[2 * k] = __uint_as_float(hw[k] << 16) + __uint_as_float(lw[k] << 16);
-                r[2 * k + 1] = __uint_as_float(hw[k] & 0xffff0000u) + __uint_as_float(lw[k] & 0xffff0000u);
-            }
-        } else if (res) load8(res + e, r);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            float v = f[k] * sc[k] + sh[k];
-            if constexpr (RES == 2) r[k] = r[k] * sc2[k] + sh2[k];
-            if (RES == 1 || res) v += r[k];
-            if (relu) v = fmaxf(v, 0.f);
-            f[k] = v;
-        }
-        if (out) store8(out + e, f);
-        store_split8(hi, lo, e, f);
-    }
+    float sc[8], sh[8], sc2[RES == RES_RAWBN ? 8 : 1], sh2[RES == RES_RAWBN ? 8 : 1];
+    load_scale_shift<8>(&par[0][0], BNFIN_SLICE, t.j * 8, sc, sh);
+    if constexpr (RES == RES_RAWBN) load_scale_shift<8>(res_bnp, C, t.c0 + t.j * 8, sc2, sh2);
+    for (long p = (long)t.strip * 32 + t.pl; p < M; p += (long)t.nstrips * 32)
+        bn_fwd_x3<8, RES>(p * C + t.c0 + t.j * 8, y, res, res_hi, res_lo, sc, sh, sc2, sh2, relu, out, hi, lo);
 }
 
 // BatchNorm backward, pass 2 with its finalize inside: part[nparts][C][2] = per-tile (sum dz, sum dz * xhat)
@@ -962,50 +908,16 @@ __global__ __launch_bounds__(256) void bn_fin_bwd_apply_x3_kernel(const float* _
                                                                   float* __restrict__ dz_out, const bf16_t* __restrict__ out_hi) {
     __shared__ double sm[4 * 64 * 2];
     __shared__ float par[2][BNFIN_SLICE];
-    const int nsl = C / BNFIN_SLICE, slice = blockIdx.x % nsl, strip = blockIdx.x / nsl, nstrips = gridDim.x / nsl;
-    const int c0 = slice * BNFIN_SLICE;
-    double s, q; bnfin_reduce(part, nparts, C, c0, sm, s, q);
+    const BnFinTile t = bnfin_tile(C);
+    double s, q; bnfin_reduce(part, nparts, C, t.c0, sm, s, q);
     if (threadIdx.x < 64) {
         par[0][threadIdx.x] = (float)s; par[1][threadIdx.x] = (float)q;
-        if (strip == 0) {
-            const int c = c0 + threadIdx.x;
-            dbeta[c] = (float)s; dgamma[c] = (float)q; bwdp[c] = (float)s; bwdp[C + c] = (float)q;
-        }
+        if (t.strip == 0) bn_store_bwd_sums(s, q, dgamma, dbeta, bwdp, C, t.c0 + threadIdx.x);
     }
     __syncthreads();
-    const float invM = 1.f / (float)M;
-    const int j = threadIdx.x & 7, pl = threadIdx.x >> 3;
-    float ga[8], sh[8], mu[8], is[8], k1[8], k2[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int c = c0 + j * 8 + k;
-        ga[k] = bnp[c]; sh[k] = bnp[C + c]; mu[k] = bnp[2 * C + c]; is[k] = bnp[3 * C + c];
-        k1[k] = par[0][j * 8 + k] * invM; k2[k] = par[1][j * 8 + k] * invM;
-    }
-    for (long p = (long)strip * 32 + pl; p < M; p += (long)nstrips * 32) {
-        const long e = p * C + c0 + j * 8;
-        float g[8], o[8], yy[8], d[8];
-        load8(dout + e, g);
-        load8(y + e, yy);
-        if (relu == 1) {
-            if (out_hi) {
-                const uint4 h = *(const uint4*)(out_hi + e);
-                const uint32_t hw[4] = {h.x, h.y, h.z, h.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { o[2 * k] = __uint_as_float(hw[k] << 16); o[2 * k + 1] = __uint_as_float(hw[k] & 0xffff0000u); }
-            } else load8(out + e, o);
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const bool dead = relu == 1 ? !(o[k] > 0.f) : relu == 2 ? !(yy[k] * ga[k] + sh[k] > 0.f) : false;
-            const float dz = dead ? 0.f : g[k];
-            const float xhat = (yy[k] - mu[k]) * is[k];
-            d[k] = ga[k] * (dz - k1[k] - xhat * k2[k]);
-            g[k] = dz;
-        }
-        store_split8(dy_hi, dy_lo, e, d);
-        if (dz_out) store8(dz_out + e, g);
-    }
+    BnBwd<8> P; load_bwd_params<8>(P, bnp, C, t.c0 + t.j * 8, &par[0][0], BNFIN_SLICE, t.j * 8, 1.f / (float)M);
+    for (long p = (long)t.strip * 32 + t.pl; p < M; p += (long)t.nstrips * 32)
+        bn_bwd_x3(P, p * C + t.c0 + t.j * 8, dout, out, out_hi, y, relu, dy_hi, dy_lo, dz_out);
 }
 
 static bool bnfin_ok(int nparts, int C) {
@@ -1037,15 +949,13 @@ __global__ __launch_bounds__(256) void maxpool_fwd_x3_kernel(const float* __rest
     if (col >= (unsigned)(Wo * vc)) return;
     const int wo = (int)(col / (unsigned)vc), cv = (int)(col - (unsigned)wo * vc);
     const int n = blockIdx.z, ho0 = blockIdx.y * PFX_ROWS;
-    float sc[8], sh[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { sc[k] = bnp[cv * 8 + k]; sh[k] = bnp[C + cv * 8 + k]; }
+    float sc[8], sh[8]; load_scale_shift<8>(bnp, C, cv * 8, sc, sh);
     const bool w0ok = wo > 0;                                // H, W even: only h = -1 / w = -1 can fall outside
     auto load_row = [&](int h, float (*r)[8]) {              // the three taps of input row h
 #pragma unroll
         for (int dw = 0; dw < 3; ++dw) {
             if (dw == 0 && !w0ok) continue;
-            load8(y + (((long)n * H + h) * W + (wo * 2 + dw - 1)) * C + cv * 8, r[dw]);
+            vload<float, 8>(y + (((long)n * H + h) * W + (wo * 2 + dw - 1)) * C + cv * 8, r[dw]);
         }
     };      // (RAW values are kept: relu(bn(.)) is applied at the comparison, so the winner's raw value is at hand for `ywin`)
     float top[3][8], mid[3][8], bot[3][8];
@@ -1074,10 +984,10 @@ __global__ __launch_bounds__(256) void maxpool_fwd_x3_kernel(const float* __rest
         scan(mid, 3);
         scan(bot, 6);
         const long e = ((((long)n * Ho + ho) * Wo + wo) * vc + cv) * 8;
-        if (out) store8(out + e, m);           // (NULL: the pooled tensor is wanted as planes only)
-        *(uint2*)(idx + e) = make_uint2(am[0] | (am[1] << 8) | (am[2] << 16) | (am[3] << 24), am[4] | (am[5] << 8) | (am[6] << 16) | (am[7] << 24));
-        store_split8(out_hi, out_lo, e, m);
-        if (ywin) store8(ywin + e, mraw);      // the winner's RAW conv output: what the backward's reduction needs of y
+        if (out) vstore<float, 8>(out + e, m);           // (NULL: the pooled tensor is wanted as planes only)
+        pack_winners<8>(idx + e, am);
+        store_split<8>(out_hi, out_lo, e, m);
+        if (ywin) vstore<float, 8>(ywin + e, mraw);      // the winner's RAW conv output: what the backward's reduction needs of y
 #pragma unroll
         for (int dw = 0; dw < 3; ++dw)
 #pragma unroll
@@ -1097,71 +1007,32 @@ __global__ __launch_bounds__(256) void pool_bwd_bn_apply_x3_kernel(const uint8_t
     if (col >= (unsigned)(W * vc)) return;
     const int w = (int)(col / (unsigned)vc), cv = (int)(col - (unsigned)w * vc);
     const int n = blockIdx.z, p = blockIdx.y;
-    float acc0[8], acc1[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { acc0[k] = 0.f; acc1[k] = 0.f; }
-#pragma unroll
-    for (int dp = 0; dp < 2; ++dp) {
-        const int ho = p + dp;
-        if (ho >= Ho) continue;
-        for (int wo = w / 2; wo <= (w + 1) / 2; ++wo) {
-            if (wo >= Wo) continue;
-            const int cw = w - (wo * 2 - 1);
-            const long o = (((long)n * Ho + ho) * Wo + wo) * C + cv * 8;
-            const uint2 qd = *(const uint2*)(idx + o);
-            float g[8]; load8(dout + o, g);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int am = ((k < 4 ? qd.x : qd.y) >> (8 * (k & 3))) & 0xff;
-                if (dp == 0) { if (am == 3 + cw) acc0[k] += g[k]; if (am == 6 + cw) acc1[k] += g[k]; }
-                else if (am == cw) acc1[k] += g[k];
-            }
-        }
-    }
+    float acc0[8], acc1[8], ya[8], yb[8], d0[8], d1[8];
+    pool_gather_pair<float, 8>(idx, dout, n, p, w, Ho, Wo, C, cv * 8, acc0, acc1);
     const long e = ((((long)n * H + 2 * p) * W + w) * vc + cv) * 8;
-    float ya[8], yb[8], d0[8], d1[8];
-    load8(y + e, ya); load8(y + e + (long)W * C, yb);
+    vload<float, 8>(y + e, ya);
+    vload<float, 8>(y + e + (long)W * C, yb);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
+    for (int k = 0; k < 8; ++k) {      // channel by channel: a channel's six parameters are loaded where its two rows use them
         const int c = cv * 8 + k;
-        const float ga = bnp[c], sh = bnp[C + c], mu = bnp[2 * C + c], is = bnp[3 * C + c];
-        const float k1 = bwdp[c] * invM, k2 = bwdp[C + c] * invM;
-        const float z0 = (ya[k] * ga + sh > 0.f) ? acc0[k] : 0.f, z1 = (yb[k] * ga + sh > 0.f) ? acc1[k] : 0.f;
-        d0[k] = ga * (z0 - k1 - ((ya[k] - mu) * is) * k2);
-        d1[k] = ga * (z1 - k1 - ((yb[k] - mu) * is) * k2);
+        BnBwd<1> P; load_bwd_params<1>(P, bnp, C, c, bwdp, C, c, invM);
+        relu_mask<1>(P, RELU_RECOMPUTE, acc0 + k, nullptr, ya + k);
+        relu_mask<1>(P, RELU_RECOMPUTE, acc1 + k, nullptr, yb + k);
+        bn_bwd_dy<1>(P, acc0 + k, ya + k, d0 + k);
+        bn_bwd_dy<1>(P, acc1 + k, yb + k, d1 + k);
     }
-    store_split8(dy_hi, dy_lo, e, d0);
-    store_split8(dy_hi, dy_lo, e + (long)W * C, d1);
+    store_split<8>(dy_hi, dy_lo, e, d0);
+    store_split<8>(dy_hi, dy_lo, e + (long)W * C, d1);
 }
 
 // column sums of a split tensor (hi + lo): the bias gradient of the final layer from the dlogits planes
 __global__ __launch_bounds__(256) void col_stats_x3_kernel(const bf16_t* __restrict__ hi, const bf16_t* __restrict__ lo, long M, int C,
                                                           int rows_per_block, float* __restrict__ part) {
-    const int vc = C / 8, rl = 256 / vc;
-    const int cv = threadIdx.x % vc, rr = threadIdx.x / vc;
-    long r0 = (long)blockIdx.x * rows_per_block;
-    long r1 = r0 + rows_per_block; if (r1 > M) r1 = M;
-    float s[8], q[8];
+    row_reduce<8>(M, C, C, 0, rows_per_block, part, [&](long r, int c, float* s, float* q) {
+        float v[8]; load_planes<8>(hi, lo, r * C + c, v);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { s[i] = 0.f; q[i] = 0.f; }
-    if (rr < rl)
-        for (long r = r0 + rr; r < r1; r += rl) {
-            float a[8], b[8];
-            vload<bf16_t>(hi + r * C + cv * 8, a);
-            vload<bf16_t>(lo + r * C + cv * 8, b);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { const float v = a[i] + b[i]; s[i] += v; q[i] += v * v; }
-        }
-    extern __shared__ float sm[];
-    if (rr < rl)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { sm[(rr * C + cv * 8 + i) * 2] = s[i]; sm[(rr * C + cv * 8 + i) * 2 + 1] = q[i]; }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += 256) {
-        float a = 0.f, b = 0.f;
-        for (int k = 0; k < rl; ++k) { a += sm[(k * C + c) * 2]; b += sm[(k * C + c) * 2 + 1]; }
-        part[((long)blockIdx.x * C + c) * 2] = a; part[((long)blockIdx.x * C + c) * 2 + 1] = b;
-    }
+        for (int i = 0; i < 8; ++i) { s[i] += v[i]; q[i] += v[i] * v[i]; }
+    });
 }
 
 // BatchNorm-backward reduction of  maxpool3x3/2(relu(bn(y)))  over the POOLED elements only: the masked gradient is non-zero at
@@ -1171,52 +1042,44 @@ __global__ __launch_bounds__(256) void col_stats_x3_kernel(const bf16_t* __restr
 __global__ __launch_bounds__(256) void pool_win_bn_reduce_kernel(const float* __restrict__ dpool, const float* __restrict__ ywin,
                                                                   const float* __restrict__ bnp, long M, int C, int rows_per_block,
                                                                   float* __restrict__ part) {
-    const int vc = C / 8, rl = 256 / vc;
-    const int cv = threadIdx.x % vc, rr = threadIdx.x / vc;
-    long r0 = (long)blockIdx.x * rows_per_block;
-    long r1 = r0 + rows_per_block; if (r1 > M) r1 = M;
-    float s[8], q[8], sc[8], sh[8], mu[8], is[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        s[i] = 0.f; q[i] = 0.f;
-        sc[i] = bnp[cv * 8 + i]; sh[i] = bnp[C + cv * 8 + i]; mu[i] = bnp[2 * C + cv * 8 + i]; is[i] = bnp[3 * C + cv * 8 + i];
-    }
-    if (rr < rl)
-        for (long r = r0 + rr; r < r1; r += rl) {
-            float g[8], yw[8];
-            load8(dpool + r * C + cv * 8, g);
-            load8(ywin + r * C + cv * 8, yw);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float dz = (yw[i] * sc[i] + sh[i] > 0.f) ? g[i] : 0.f;
-                s[i] += dz; q[i] += dz * ((yw[i] - mu[i]) * is[i]);
-            }
-        }
-    extern __shared__ float sm[];
-    if (rr < rl)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { sm[(rr * C + cv * 8 + i) * 2] = s[i]; sm[(rr * C + cv * 8 + i) * 2 + 1] = q[i]; }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += 256) {
-        float a = 0.f, b = 0.f;
-        for (int k = 0; k < rl; ++k) { a += sm[(k * C + c) * 2]; b += sm[(k * C + c) * 2 + 1]; }
-        part[((long)blockIdx.x * C + c) * 2] = a; part[((long)blockIdx.x * C + c) * 2 + 1] = b;
-    }
+    BnBwd<8> P; load_bn_stats<8>(P, bnp, C, row_lane_channel<8>(C));
+    row_reduce<8>(M, C, C, 0, rows_per_block, part, [&](long r, int c, float* s, float* q) {
+        float g[8], yw[8];
+        vload<float, 8>(dpool + r * C + c, g);
+        vload<float, 8>(ywin + r * C + c, yw);
+        relu_mask<8>(P, RELU_RECOMPUTE, g, nullptr, yw);
+        bn_bwd_sums<8>(P, g, yw, s, q);
+    });
 }
 
 // ================================================================ C ABI
 static inline int grid_for(long nvec) { long b = (nvec + 255) / 256; return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b)); }
-#define DISPATCH(dtype, CALL_F, CALL_B) do { if ((dtype) == AB_DT_F32) { CALL_F; } else if ((dtype) == AB_DT_BF16) { CALL_B; } else return AB_EINVAL; } while (0)
+static inline int vec_of(int dtype) { return dtype == AB_DT_F32 ? 4 : 8; }      // elements per 16-byte vector
+// runs the statement(s) with T = float / bf16_t for dtype; any other dtype returns AB_EINVAL
+#define DISPATCH(dtype, ...) do { \
+        if ((dtype) == AB_DT_F32) { using T = float; __VA_ARGS__; } \
+        else if ((dtype) == AB_DT_BF16) { using T = bf16_t; __VA_ARGS__; } \
+        else return AB_EINVAL; \
+    } while (0)
+// the finalize launches: launch(CPW as an integral constant, grid) for the CPW that finalize_cpw() picks
+template <typename F> static void launch_finalize(int C, F launch) {
+    switch (finalize_cpw()) {
+    case 2: launch(std::integral_constant<int, 2>(), (C + 1) / 2); break;
+    case 4: launch(std::integral_constant<int, 4>(), (C + 3) / 4); break;
+    default: launch(std::integral_constant<int, 8>(), (C + 7) / 8); break;
+    }
+}
+// grid of the pooling kernels: x = 256-thread workgroups over a row's cols x vc channel vectors, y = rows, z = N
+static inline dim3 pool_grid(int cols, int vc, int rows, int N) { return dim3((unsigned)(((long)cols * vc + 255) / 256), (unsigned)rows, (unsigned)N); }
 
 extern "C" int ab_col_stats_nparts(long M) { int r = red_rows(M); return (int)((M + r - 1) / r); }
 
 extern "C" int ab_col_stats(const void* x, int dtype, long M, int C, float* part, void* stream) {
     if (!x || !part) return AB_EINVAL;
-    int V = dtype == AB_DT_F32 ? 4 : 8;
+    int V = vec_of(dtype);
     if (C % V || C / V > 256) return AB_ESHAPE;
     int np = ab_col_stats_nparts(M); int rl = 256 / (C / V); size_t sh = (size_t)rl * C * 2 * 4;
-    DISPATCH(dtype, (col_stats_kernel<float><<<np, 256, sh, as_stream(stream)>>>((const float*)x, M, C, red_rows(M), part)),
-             (col_stats_kernel<bf16_t><<<np, 256, sh, as_stream(stream)>>>((const bf16_t*)x, M, C, red_rows(M), part)));
+    DISPATCH(dtype, col_stats_kernel<T><<<np, 256, sh, as_stream(stream)>>>((const T*)x, M, C, red_rows(M), part));
     AB_LAUNCH_CHECK(); return 0;
 }
 
@@ -1225,11 +1088,9 @@ extern "C" int ab_bn_finalize(const float* part, int nparts, int C, long count, 
                               void* stream) {
     if (!part || !gamma || !beta || !bnp) return AB_EINVAL;
     hipStream_t st = as_stream(stream);
-    switch (finalize_cpw(C)) {
-    case 2: bn_finalize_kernel<2><<<(C + 1) / 2, 1024, 0, st>>>(part, nparts, C, count, gamma, beta, eps, momentum, running_mean, running_var, bnp); break;
-    case 4: bn_finalize_kernel<4><<<(C + 3) / 4, 1024, 0, st>>>(part, nparts, C, count, gamma, beta, eps, momentum, running_mean, running_var, bnp); break;
-    default: bn_finalize_kernel<8><<<(C + 7) / 8, 1024, 0, st>>>(part, nparts, C, count, gamma, beta, eps, momentum, running_mean, running_var, bnp); break;
-    }
+    launch_finalize(C, [&](auto cpw, int grid) {
+        bn_finalize_kernel<decltype(cpw)::value><<<grid, 1024, 0, st>>>(part, nparts, C, count, gamma, beta, eps, momentum, running_mean, running_var, bnp);
+    });
     AB_LAUNCH_CHECK(); return 0;
 }
 
@@ -1251,38 +1112,33 @@ extern "C" int ab_bn_eval_params_batch(const float* flat, const float* stats, co
 extern "C" int ab_bn_apply(const void* y, const void* res, const float* bnp, int dtype, long M, int C, int relu,
                            void* out, void* stream) {
     if (!y || !bnp || !out) return AB_EINVAL;
-    int V = dtype == AB_DT_F32 ? 4 : 8; if (C % V) return AB_ESHAPE;
+    int V = vec_of(dtype); if (C % V) return AB_ESHAPE;
     long nvec = M * C / V;
-    DISPATCH(dtype, (bn_apply_kernel<float><<<grid_for(nvec), 256, 0, as_stream(stream)>>>((const float*)y, (const float*)res, bnp, nvec, C, relu, (float*)out)),
-             (bn_apply_kernel<bf16_t><<<grid_for(nvec), 256, 0, as_stream(stream)>>>((const bf16_t*)y, (const bf16_t*)res, bnp, nvec, C, relu, (bf16_t*)out)));
+    DISPATCH(dtype, bn_apply_kernel<T><<<grid_for(nvec), 256, 0, as_stream(stream)>>>((const T*)y, (const T*)res, bnp, nvec, C, relu, (T*)out));
     AB_LAUNCH_CHECK(); return 0;
 }
 
 static void launch_bn_bwd_finalize(const float* part, int np, int C, float* dgamma, float* dbeta, float* bwdp, hipStream_t st) {
-    switch (finalize_cpw(C)) {
-    case 2: bn_bwd_finalize_kernel<2><<<(C + 1) / 2, 1024, 0, st>>>(part, np, C, dgamma, dbeta, bwdp); break;
-    case 4: bn_bwd_finalize_kernel<4><<<(C + 3) / 4, 1024, 0, st>>>(part, np, C, dgamma, dbeta, bwdp); break;
-    default: bn_bwd_finalize_kernel<8><<<(C + 7) / 8, 1024, 0, st>>>(part, np, C, dgamma, dbeta, bwdp); break;
-    }
+    launch_finalize(C, [&](auto cpw, int grid) { bn_bwd_finalize_kernel<decltype(cpw)::value><<<grid, 1024, 0, st>>>(part, np, C, dgamma, dbeta, bwdp); });
 }
 
 static int bn_bwd_impl(const void* dout, const void* out, const void* y, const float* bnp, int dtype, long M, int C,
                        int relu, float* part, float* bwdp, float* dgamma, float* dbeta, void* dy, void* dz_out,
                        const uint8_t* pool_idx, int pH, int pW, hipStream_t st, int given_parts = 0) {
-    int V = dtype == AB_DT_F32 ? 4 : 8;
+    int V = vec_of(dtype);
     int ysl = 1;                                  // channel slices of the reduction (<= 256 V-channel groups each)
     while (C / V / ysl > 256) ysl *= 2;
     if (C % V || C % (V * ysl)) return AB_ESHAPE;
     int np = given_parts > 0 ? given_parts : ab_col_stats_nparts(M); const int cs = C / ysl; int rl = 256 / (cs / V); size_t sh = (size_t)rl * cs * 2 * 4;
     if (given_parts <= 0)
-    DISPATCH(dtype, (bn_bwd_reduce_kernel<float><<<dim3(np, ysl), 256, sh, st>>>((const float*)dout, (const float*)out, (const float*)y, bnp, M, C, relu, red_rows(M), part, pool_idx, pH, pW)),
-             (bn_bwd_reduce_kernel<bf16_t><<<dim3(np, ysl), 256, sh, st>>>((const bf16_t*)dout, (const bf16_t*)out, (const bf16_t*)y, bnp, M, C, relu, red_rows(M), part, pool_idx, pH, pW)));
+        DISPATCH(dtype, bn_bwd_reduce_kernel<T><<<dim3(np, ysl), 256, sh, st>>>((const T*)dout, (const T*)out, (const T*)y, bnp, M, C, relu,
+                                                                                red_rows(M), part, pool_idx, pH, pW));
     AB_LAUNCH_CHECK();
     launch_bn_bwd_finalize(part, np, C, dgamma, dbeta, bwdp, st);
     AB_LAUNCH_CHECK();
     long nvec = M * C / V;
-    DISPATCH(dtype, (bn_bwd_apply_kernel<float><<<grid_for(nvec), 256, 0, st>>>((const float*)dout, (const float*)out, (const float*)y, bnp, bwdp, nvec, C, M, relu, (float*)dy, (float*)dz_out, pool_idx, pH, pW)),
-             (bn_bwd_apply_kernel<bf16_t><<<grid_for(nvec), 256, 0, st>>>((const bf16_t*)dout, (const bf16_t*)out, (const bf16_t*)y, bnp, bwdp, nvec, C, M, relu, (bf16_t*)dy, (bf16_t*)dz_out, pool_idx, pH, pW)));
+    DISPATCH(dtype, bn_bwd_apply_kernel<T><<<grid_for(nvec), 256, 0, st>>>((const T*)dout, (const T*)out, (const T*)y, bnp, bwdp, nvec, C, M, relu,
+                                                                           (T*)dy, (T*)dz_out, pool_idx, pH, pW));
     AB_LAUNCH_CHECK(); return 0;
 }
 
@@ -1315,27 +1171,24 @@ extern "C" int ab_bn_relu_maxpool_bwd(const void* dpool, const void* idx, const 
 }
 
 extern "C" int ab_add(const void* a, const void* b, int dtype, long n, void* out, void* stream) {
-    int V = dtype == AB_DT_F32 ? 4 : 8; if (n % V) return AB_ESHAPE;
+    int V = vec_of(dtype); if (n % V) return AB_ESHAPE;
     long nvec = n / V;
-    DISPATCH(dtype, (add_kernel<float><<<grid_for(nvec), 256, 0, as_stream(stream)>>>((const float*)a, (const float*)b, nvec, (float*)out)),
-             (add_kernel<bf16_t><<<grid_for(nvec), 256, 0, as_stream(stream)>>>((const bf16_t*)a, (const bf16_t*)b, nvec, (bf16_t*)out)));
+    DISPATCH(dtype, add_kernel<T><<<grid_for(nvec), 256, 0, as_stream(stream)>>>((const T*)a, (const T*)b, nvec, (T*)out));
     AB_LAUNCH_CHECK(); return 0;
 }
 
 extern "C" int ab_maxpool3x3s2_fwd(const void* x, int dtype, int N, int H, int W, int C, void* out, void* idx, void* stream) {
-    int V = dtype == AB_DT_F32 ? 4 : 8; if (C % V || (H & 1) || (W & 1)) return AB_ESHAPE;
-    dim3 pgrid((unsigned)(((long)(W / 2) * (C / V) + 255) / 256), (unsigned)(H / 2), (unsigned)N);
-    DISPATCH(dtype, (maxpool_fwd_kernel<float><<<pgrid, 256, 0, as_stream(stream)>>>((const float*)x, nullptr, N, H, W, C, (float*)out, (uint8_t*)idx)),
-             (maxpool_fwd_kernel<bf16_t><<<pgrid, 256, 0, as_stream(stream)>>>((const bf16_t*)x, nullptr, N, H, W, C, (bf16_t*)out, (uint8_t*)idx)));
+    int V = vec_of(dtype); if (C % V || (H & 1) || (W & 1)) return AB_ESHAPE;
+    DISPATCH(dtype, maxpool_fwd_kernel<T><<<pool_grid(W / 2, C / V, H / 2, N), 256, 0, as_stream(stream)>>>((const T*)x, nullptr, N, H, W, C, (T*)out,
+                                                                                                            (uint8_t*)idx));
     AB_LAUNCH_CHECK(); return 0;
 }
 extern "C" int ab_bn_relu_maxpool3x3s2_fwd(const void* y, const float* bnp, int dtype, int N, int H, int W, int C, void* out,
                                            void* idx, void* stream) {
     if (!y || !bnp || !out) return AB_EINVAL;
-    int V = dtype == AB_DT_F32 ? 4 : 8; if (C % V || (H & 1) || (W & 1)) return AB_ESHAPE;
-    dim3 pgrid((unsigned)(((long)(W / 2) * (C / V) + 255) / 256), (unsigned)(H / 2), (unsigned)N);
-    DISPATCH(dtype, (maxpool_fwd_kernel<float><<<pgrid, 256, 0, as_stream(stream)>>>((const float*)y, bnp, N, H, W, C, (float*)out, (uint8_t*)idx)),
-             (maxpool_fwd_kernel<bf16_t><<<pgrid, 256, 0, as_stream(stream)>>>((const bf16_t*)y, bnp, N, H, W, C, (bf16_t*)out, (uint8_t*)idx)));
+    int V = vec_of(dtype); if (C % V || (H & 1) || (W & 1)) return AB_ESHAPE;
+    DISPATCH(dtype, maxpool_fwd_kernel<T><<<pool_grid(W / 2, C / V, H / 2, N), 256, 0, as_stream(stream)>>>((const T*)y, bnp, N, H, W, C, (T*)out,
+                                                                                                            (uint8_t*)idx));
     AB_LAUNCH_CHECK(); return 0;
 }
 // fp32 in, fp32 + (hi, lo) bf16 planes out: the pooled tensor is read by three split-bf16 convolutions (layer1.0 conv1, its
@@ -1346,12 +1199,12 @@ extern "C" int ab_bn_relu_maxpool3x3s2_fwd_x3(const float* y, const float* bnp, 
     if (C % 4 || (H & 1) || (W & 1)) return AB_ESHAPE;
     static const int v8 = getenv("AB_POOL_FWD_V8") ? atoi(getenv("AB_POOL_FWD_V8")) : 1;
     if (v8 && C % 8 == 0 && idx) {
-        dim3 g8((unsigned)(((long)(W / 2) * (C / 8) + 255) / 256), (unsigned)((H / 2 + PFX_ROWS - 1) / PFX_ROWS), (unsigned)N);
+        const dim3 g8 = pool_grid(W / 2, C / 8, (H / 2 + PFX_ROWS - 1) / PFX_ROWS, N);
         maxpool_fwd_x3_kernel<<<g8, 256, 0, as_stream(stream)>>>(y, bnp, N, H, W, C, out, (uint8_t*)idx, (bf16_t*)out_hi, (bf16_t*)out_lo, nullptr);
         AB_LAUNCH_CHECK(); return 0;
     }
-    dim3 pgrid((unsigned)(((long)(W / 2) * (C / 4) + 255) / 256), (unsigned)(H / 2), (unsigned)N);
-    maxpool_fwd_kernel<float><<<pgrid, 256, 0, as_stream(stream)>>>(y, bnp, N, H, W, C, out, (uint8_t*)idx, (bf16_t*)out_hi, (bf16_t*)out_lo);
+    const dim3 g4 = pool_grid(W / 2, C / 4, H / 2, N);
+    maxpool_fwd_kernel<float><<<g4, 256, 0, as_stream(stream)>>>(y, bnp, N, H, W, C, out, (uint8_t*)idx, (bf16_t*)out_hi, (bf16_t*)out_lo);
     AB_LAUNCH_CHECK(); return 0;
 }
 // ... also writing ywin [N,H/2,W/2,C] fp32: the RAW conv output at each window's winner, for ab_bn_relu_maxpool_bwd_x3w
@@ -1359,31 +1212,29 @@ extern "C" int ab_bn_relu_maxpool3x3s2_fwd_x3w(const float* y, const float* bnp,
                                                void* out_lo, void* idx, float* ywin, void* stream) {
     if (!y || !bnp || !out_hi || !out_lo || !idx || !ywin) return AB_EINVAL;          // out may be NULL: planes only
     if (C % 8 || (H & 1) || (W & 1)) return AB_ESHAPE;
-    dim3 g8((unsigned)(((long)(W / 2) * (C / 8) + 255) / 256), (unsigned)((H / 2 + PFX_ROWS - 1) / PFX_ROWS), (unsigned)N);
+    const dim3 g8 = pool_grid(W / 2, C / 8, (H / 2 + PFX_ROWS - 1) / PFX_ROWS, N);
     maxpool_fwd_x3_kernel<<<g8, 256, 0, as_stream(stream)>>>(y, bnp, N, H, W, C, out, (uint8_t*)idx, (bf16_t*)out_hi, (bf16_t*)out_lo, ywin);
     AB_LAUNCH_CHECK(); return 0;
 }
 extern "C" int ab_maxpool3x3s2_bwd(const void* idx, const void* dout, int dtype, int N, int H, int W, int C, void* dx,
                                    void* stream) {
-    int V = dtype == AB_DT_F32 ? 4 : 8; if (C % V || (H & 1) || (W & 1)) return AB_ESHAPE;
-    dim3 pgrid((unsigned)(((long)W * (C / V) + 255) / 256), (unsigned)(H / 2), (unsigned)N);
-    DISPATCH(dtype, (maxpool_bwd_kernel<float><<<pgrid, 256, 0, as_stream(stream)>>>((const uint8_t*)idx, (const float*)dout, N, H, W, C, (float*)dx)),
-             (maxpool_bwd_kernel<bf16_t><<<pgrid, 256, 0, as_stream(stream)>>>((const uint8_t*)idx, (const bf16_t*)dout, N, H, W, C, (bf16_t*)dx)));
+    int V = vec_of(dtype); if (C % V || (H & 1) || (W & 1)) return AB_ESHAPE;
+    DISPATCH(dtype, maxpool_bwd_kernel<T><<<pool_grid(W, C / V, H / 2, N), 256, 0, as_stream(stream)>>>((const uint8_t*)idx, (const T*)dout, N, H, W, C,
+                                                                                                    (T*)dx));
     AB_LAUNCH_CHECK(); return 0;
 }
 
 extern "C" int ab_avgpool_fwd(const void* x, int dtype, int N, int HW, int C, float* out, void* stream) {
     if (!x || !out) return AB_EINVAL;
-    if (C % (dtype == AB_DT_F32 ? 4 : 8)) return AB_ESHAPE;
-    DISPATCH(dtype, (avgpool_fwd_kernel<float><<<dim3(N, (C + 127) / 128), 256, 0, as_stream(stream)>>>((const float*)x, HW, C, out)),
-             (avgpool_fwd_kernel<bf16_t><<<dim3(N, (C + 255) / 256), 256, 0, as_stream(stream)>>>((const bf16_t*)x, HW, C, out)));
+    const int V = vec_of(dtype); if (C % V) return AB_ESHAPE;
+    DISPATCH(dtype, avgpool_fwd_kernel<T><<<dim3(N, (C + 32 * V - 1) / (32 * V)), 256, 0, as_stream(stream)>>>((const T*)x, HW, C, out));
     AB_LAUNCH_CHECK(); return 0;
 }
 extern "C" int ab_avgpool_bwd(const float* g, int dtype, int N, int HW, int C, void* dx, int accumulate, void* stream) {
     if (!g || !dx) return AB_EINVAL;
-    if (C % (dtype == AB_DT_F32 ? 4 : 8)) return AB_ESHAPE;
-    DISPATCH(dtype, (avgpool_bwd_kernel<float><<<grid_for((long)N * HW * C / 4), 256, 0, as_stream(stream)>>>(g, HW, C, (long)N * HW * C / 4, (float*)dx, accumulate)),
-             (avgpool_bwd_kernel<bf16_t><<<grid_for((long)N * HW * C / 8), 256, 0, as_stream(stream)>>>(g, HW, C, (long)N * HW * C / 8, (bf16_t*)dx, accumulate)));
+    const int V = vec_of(dtype); if (C % V) return AB_ESHAPE;
+    const long nvec = (long)N * HW * C / V;
+    DISPATCH(dtype, avgpool_bwd_kernel<T><<<grid_for(nvec), 256, 0, as_stream(stream)>>>(g, HW, C, nvec, (T*)dx, accumulate));
     AB_LAUNCH_CHECK(); return 0;
 }
 
@@ -1393,29 +1244,25 @@ extern "C" int ab_cast_f32_bf16(const float* src, long n, void* dst, void* strea
 }
 extern "C" int ab_transpose_oki(const float* src, int O, int K, int I, int dtype, void* dst, void* stream) {
     long n = (long)O * K * I;
-    DISPATCH(dtype, (transpose_oki_kernel<float><<<grid_for(n), 256, 0, as_stream(stream)>>>(src, O, K, I, (float*)dst)),
-             (transpose_oki_kernel<bf16_t><<<grid_for(n), 256, 0, as_stream(stream)>>>(src, O, K, I, (bf16_t*)dst)));
+    DISPATCH(dtype, transpose_oki_kernel<T><<<grid_for(n), 256, 0, as_stream(stream)>>>(src, O, K, I, (T*)dst));
     AB_LAUNCH_CHECK(); return 0;
 }
 extern "C" int ab_transpose_oki_batch(const ab_transpose_desc* desc_dev, int ntensors, long total_tiles, int dtype,
                                       void* stream) {
     if (!desc_dev || ntensors < 1 || total_tiles < 1 || total_tiles > 0x7fffffffL) return AB_EINVAL;
-    DISPATCH(dtype, (transpose_oki_batch_kernel<float><<<(unsigned)total_tiles, 256, 0, as_stream(stream)>>>(desc_dev, ntensors)),
-             (transpose_oki_batch_kernel<bf16_t><<<(unsigned)total_tiles, 256, 0, as_stream(stream)>>>(desc_dev, ntensors)));
+    DISPATCH(dtype, transpose_oki_batch_kernel<T><<<(unsigned)total_tiles, 256, 0, as_stream(stream)>>>(desc_dev, ntensors));
     AB_LAUNCH_CHECK(); return 0;
 }
 extern "C" int ab_image_pad_nhwc4(const float* img_nchw, int dtype, int N, int H, int W, void* out, void* stream) {
     long n = (long)N * (H + 6) * (W + 8);
-    DISPATCH(dtype, (image_pad_kernel<float><<<grid_for(n), 256, 0, as_stream(stream)>>>(img_nchw, N, H, W, (float*)out)),
-             (image_pad_kernel<bf16_t><<<grid_for(n), 256, 0, as_stream(stream)>>>(img_nchw, N, H, W, (bf16_t*)out)));
+    DISPATCH(dtype, image_pad_kernel<T><<<grid_for(n), 256, 0, as_stream(stream)>>>(img_nchw, N, H, W, (T*)out));
     AB_LAUNCH_CHECK(); return 0;
 }
 
 extern "C" int ab_relu_bwd(const void* dout, const void* out, int dtype, long n, void* dz, void* stream) {
-    int V = dtype == AB_DT_F32 ? 4 : 8; if (n % V) return AB_ESHAPE;
+    int V = vec_of(dtype); if (n % V) return AB_ESHAPE;
     long nvec = n / V;
-    DISPATCH(dtype, (relu_bwd_kernel<float><<<grid_for(nvec), 256, 0, as_stream(stream)>>>((const float*)dout, (const float*)out, nvec, (float*)dz)),
-             (relu_bwd_kernel<bf16_t><<<grid_for(nvec), 256, 0, as_stream(stream)>>>((const bf16_t*)dout, (const bf16_t*)out, nvec, (bf16_t*)dz)));
+    DISPATCH(dtype, relu_bwd_kernel<T><<<grid_for(nvec), 256, 0, as_stream(stream)>>>((const T*)dout, (const T*)out, nvec, (T*)dz));
     AB_LAUNCH_CHECK(); return 0;
 }
 // column sums (bias gradient) of x [M][C]: part = float [ab_col_stats_nparts(M)][C][2] workspace, out float [C]
@@ -1527,10 +1374,11 @@ extern "C" int ab_bn_bwd_x3(const float* dout, const void* out, int out_is_hi_pl
 // row pairs per workgroup of the reduction: 4 / 8 / 16 -> 91 + 18 / 92 + 9 / 110 + 6 us for the pass + its finalize over 2 048 / 1 024 /
 // 512 partial rows
 static int pbr_rp() { static const int v = getenv("AB_PBR_RP") ? atoi(getenv("AB_PBR_RP")) : 8; return (v == 4 || v == 16) ? v : 8; }
+static dim3 pbr_grid(int N, int H, int W, int C) { return pool_grid(W, C / 4, (H / 2 + pbr_rp() - 1) / pbr_rp(), N); }
 extern "C" int ab_bn_relu_maxpool_bwd_x3_nparts(int N, int H, int W, int C) {
     if ((H & 1) || (W & 1) || C % 8 || C / 4 > 256 || 256 % (C / 4)) return 0;
-    const int gx = (int)(((long)W * (C / 4) + 255) / 256), gy = (H / 2 + pbr_rp() - 1) / pbr_rp();
-    return gx * gy * N;
+    const dim3 g = pbr_grid(N, H, W, C);
+    return (int)(g.x * g.y * g.z);
 }
 extern "C" int ab_bn_relu_maxpool_bwd_x3(const float* dpool, const void* idx, const float* y, const float* bnp, int N, int H, int W,
                                          int C, float* part, float* bwdp, float* dgamma, float* dbeta, float* dz, void* dy_hi,
@@ -1539,7 +1387,7 @@ extern "C" int ab_bn_relu_maxpool_bwd_x3(const float* dpool, const void* idx, co
     const int np = ab_bn_relu_maxpool_bwd_x3_nparts(N, H, W, C);
     if (!np) return AB_ESHAPE;
     hipStream_t st = as_stream(stream);
-    dim3 grid((unsigned)(((long)W * (C / 4) + 255) / 256), (unsigned)((H / 2 + pbr_rp() - 1) / pbr_rp()), (unsigned)N);
+    const dim3 grid = pbr_grid(N, H, W, C);
     static const int regather = getenv("AB_POOL_BWD_REGATHER") ? atoi(getenv("AB_POOL_BWD_REGATHER")) : 1;
     const long M = (long)N * H * W, nvec = M * C / 8;
 #define PBR_LAUNCH(RP, WR) pool_bwd_bn_reduce_kernel<RP, WR><<<grid, 256, 256 * 8 * 4, st>>>((const uint8_t*)idx, dpool, y, bnp, N, H, W, C, dz, part)
@@ -1551,8 +1399,7 @@ extern "C" int ab_bn_relu_maxpool_bwd_x3(const float* dpool, const void* idx, co
     launch_bn_bwd_finalize(part, np, C, dgamma, dbeta, bwdp, st);
     AB_LAUNCH_CHECK();
     if (regather) {
-        dim3 g2((unsigned)(((long)W * (C / 8) + 255) / 256), (unsigned)(H / 2), (unsigned)N);
-        pool_bwd_bn_apply_x3_kernel<<<g2, 256, 0, st>>>((const uint8_t*)idx, dpool, y, bnp, bwdp, N, H, W, C, 1.f / (float)M,
+        pool_bwd_bn_apply_x3_kernel<<<pool_grid(W, C / 8, H / 2, N), 256, 0, st>>>((const uint8_t*)idx, dpool, y, bnp, bwdp, N, H, W, C, 1.f / (float)M,
                                                        (bf16_t*)dy_hi, (bf16_t*)dy_lo);
     } else
         bn_bwd_apply_x3_kernel<<<grid_for(nvec), 256, 0, st>>>(dz, nullptr, y, bnp, bwdp, nvec, C, M, 0, (bf16_t*)dy_hi, (bf16_t*)dy_lo, nullptr, nullptr);
@@ -1573,8 +1420,7 @@ extern "C" int ab_bn_relu_maxpool_bwd_x3w(const float* dpool, const void* idx, c
     AB_LAUNCH_CHECK();
     launch_bn_bwd_finalize(part, np, C, dgamma, dbeta, bwdp, st);
     AB_LAUNCH_CHECK();
-    dim3 g2((unsigned)(((long)W * (C / 8) + 255) / 256), (unsigned)(H / 2), (unsigned)N);
-    pool_bwd_bn_apply_x3_kernel<<<g2, 256, 0, st>>>((const uint8_t*)idx, dpool, y, bnp, bwdp, N, H, W, C, 1.f / (float)M,
+    pool_bwd_bn_apply_x3_kernel<<<pool_grid(W, C / 8, H / 2, N), 256, 0, st>>>((const uint8_t*)idx, dpool, y, bnp, bwdp, N, H, W, C, 1.f / (float)M,
                                                    (bf16_t*)dy_hi, (bf16_t*)dy_lo);
     AB_LAUNCH_CHECK(); return 0;
 }
