@@ -13,20 +13,17 @@
 // This register-staged kernel is the f32 / odd-shape path (and the reference the full-size check compares against);
 // bf16 problems are routed to wgrad3x3.hip (3x3 / stride 1: all nine taps per workgroup) or wgrad_gemm2.hip (everything
 // else, LDS-DMA operands) by ab_conv2d_wgrad / ab_conv2d_stem_wgrad below.  wgrad_reduce serves all three.
-#include "common.h"
+#include "wgrad_common.h"
+#include "wgrad.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short short4_t __attribute__((ext_vector_type(4)));
-
-struct WgradArgs {
+struct WgradArgs {            // filled by wgrad_fill_conv / wgrad_fill_stem (wgrad.h)
     const void* X; const void* DY; float* slabs;
     int N, Ha, Wa, Ca;        // x tensor (Ca = channel pitch)
     int P, Q, Cout;           // dy tensor [N,P,Q,Cout]
-    int a_sh, a_sw;
-    int ntaps, seglen;        // seglen = J-elements contributed by one tap (Cin, or 32 for the padded stem rows)
-    int jtot;                 // ntaps * seglen  (row length of dW)
-    int M, rows_per_slice, nslices;
+    int stride;
+    int ntaps, Cin;           // Cin = J-elements contributed by one tap (32 for the padded stem rows)
+    int jtot;                 // ntaps * Cin  (row length of dW)
+    int M, rows_per_slice;
     int8_t dh[16], dw[16];
 };
 
@@ -67,7 +64,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs g) {
     for (int s = 0; s < NJ; ++s) {
         int id = tid + 256 * s; jr[s] = id / CJ; jc[s] = id - jr[s] * CJ;
         int jj = j0 + jc[s] * CE;                 // global J index of the chunk
-        jtap[s] = jj / g.seglen; jel[s] = jj - jtap[s] * g.seglen;
+        jtap[s] = jj / g.Cin; jel[s] = jj - jtap[s] * g.Cin;
     }
     uint4 ri[NI], rj[NJ];
     auto gload = [&](int rbase) {
@@ -84,7 +81,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs g) {
             if (jr[s] < BR && m < r_end) {
                 int n = m / PQ, r = m - n * PQ;
                 int p = r / g.Q, q = r - p * g.Q;
-                int hi = p * g.a_sh + g.dh[jtap[s]], wi = q * g.a_sw + g.dw[jtap[s]];
+                int hi = p * g.stride + g.dh[jtap[s]], wi = q * g.stride + g.dw[jtap[s]];
                 if ((unsigned)hi < (unsigned)g.Ha && (unsigned)wi < (unsigned)g.Wa)
                     rj[s] = *(const uint4*)(X + (((long)n * g.Ha + hi) * g.Wa + wi) * g.Ca + jel[s]);
             }
@@ -121,26 +118,18 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs g) {
                 uint4 fa[TI], fb[TJ];
 #pragma unroll
                 for (int a = 0; a < TI; ++a) {
-                    const unsigned char* p = SI(cur) + (kk * 16 + rsub) * PI + (wave_i * TI * 32 + a * 32 + csub) * 2;
-                    short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4_t*)p);
-                    short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4_t*)(p + 4 * PI));
-                    uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-                    fa[a] = make_uint4(l2.x, l2.y, h2.x, h2.y);
+                    const unsigned p = lds_addr_of(SI(cur)) + (kk * 16 + rsub) * PI + (wave_i * TI * 32 + a * 32 + csub) * 2;
+                    fa[a] = tr_pair(p, p + 4 * PI);
                 }
 #pragma unroll
                 for (int b = 0; b < TJ; ++b) {
-                    const unsigned char* p = SJ(cur) + (kk * 16 + rsub) * PJ + (wave_j * TJ * 32 + b * 32 + csub) * 2;
-                    short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4_t*)p);
-                    short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4_t*)(p + 4 * PJ));
-                    uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-                    fb[b] = make_uint4(l2.x, l2.y, h2.x, h2.y);
+                    const unsigned p = lds_addr_of(SJ(cur)) + (kk * 16 + rsub) * PJ + (wave_j * TJ * 32 + b * 32 + csub) * 2;
+                    fb[b] = tr_pair(p, p + 4 * PJ);
                 }
 #pragma unroll
                 for (int a = 0; a < TI; ++a)
 #pragma unroll
-                    for (int b = 0; b < TJ; ++b)
-                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[a]),
-                                                                           __builtin_bit_cast(bf16x8, fb[b]), acc[a][b], 0, 0, 0);
+                    for (int b = 0; b < TJ; ++b) mfma16(acc[a][b], fa[a], fb[b]);
             }
         } else {
             const int l32 = lane & 31, half = lane >> 5;
@@ -168,45 +157,38 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs g) {
 #pragma unroll
     for (int a = 0; a < TI; ++a)
 #pragma unroll
-        for (int b = 0; b < TJ; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int row = i0 + wave_i * TI * 32 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                int col = j0 + wave_j * TJ * 32 + b * 32 + (lane & 31);
-                out[(long)row * g.jtot + col] = acc[a][b][r];
-            }
+        for (int b = 0; b < TJ; ++b) store_acc_tile(out, g.jtot, i0 + wave_i * TI * 32 + a * 32, j0 + wave_j * TJ * 32 + b * 32, acc[a][b]);
 }
 
 // dW[e] (+)= sum_s slabs[s][e]; optionally drops padded taps: dst row layout [Cout][dst_j], src [Cout][src_j].
 // (256/KY) element quads x KY slice lanes per workgroup (KY = 4 for few slabs, 16 otherwise): lane ky sums slices ky, ky+KY,
 // ... in order, the KY partials are then combined in fixed order through LDS (deterministic; every load is a 16-byte
-// vector, contiguous along the row).
+// vector, contiguous along the row).  `block`: the workgroup's index in this reduction; part: KY * (256 / KY + 1) float4 of LDS.
 template <int KY>
-__global__ __launch_bounds__(256) void wgrad_reduce(const float* __restrict__ slabs, int nslices, long slab_elems, int src_j,
-                                                    int dst_j, float* __restrict__ dst, int accumulate, int stem_mask) {
+__device__ __forceinline__ void reduce_slabs(float4* part, unsigned block, const float* __restrict__ slabs, int nslices, long slab_elems, int src_j,
+                                             int dst_j, float* __restrict__ dst, int accumulate, int stem_mask) {
     constexpr int QX = 256 / KY;
-    __shared__ float4 part[KY][QX + 1];
     const int qx = threadIdx.x % QX, ky = threadIdx.x / QX;
-    const long quad = (long)blockIdx.x * QX + qx;
+    const long quad = (long)block * QX + qx;
     const long total = (slab_elems / src_j) * dst_j;
     const long e = quad * 4;
     const bool live = e < total;
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    long row = 0; int col = 0;
+    int col = 0;
     if (live) {
-        row = e / dst_j; col = (int)(e - row * dst_j);
+        const long row = e / dst_j; col = (int)(e - row * dst_j);
         const float* src = slabs + row * src_j + col;
         for (int k = ky; k < nslices; k += KY) {
             float4 v = *(const float4*)(src + (long)k * slab_elems);
             s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
         }
     }
-    part[ky][qx] = s;
+    part[ky * (QX + 1) + qx] = s;
     __syncthreads();
     if (ky == 0 && live) {
-        float4 t = part[0][qx];
+        float4 t = part[qx];
 #pragma unroll
-        for (int k = 1; k < KY; ++k) { float4 v = part[k][qx]; t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
+        for (int k = 1; k < KY; ++k) { float4 v = part[k * (QX + 1) + qx]; t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
         if (stem_mask) {                                      // padding taps of the [7][8][4] stem layout
             if ((col & 31) >= 28) t = make_float4(0.f, 0.f, 0.f, 0.f);
             t.w = 0.f;
@@ -215,6 +197,13 @@ __global__ __launch_bounds__(256) void wgrad_reduce(const float* __restrict__ sl
         if (accumulate) { float4 o = *d; t.x += o.x; t.y += o.y; t.z += o.z; t.w += o.w; }
         *d = t;
     }
+}
+
+template <int KY>
+__global__ __launch_bounds__(256) void wgrad_reduce(const float* __restrict__ slabs, int nslices, long slab_elems, int src_j,
+                                                    int dst_j, float* __restrict__ dst, int accumulate, int stem_mask) {
+    __shared__ float4 part[KY * (256 / KY + 1)];
+    reduce_slabs<KY>(part, blockIdx.x, slabs, nslices, slab_elems, src_j, dst_j, dst, accumulate, stem_mask);
 }
 
 // ---- deferred slab reductions: ab_conv2d_wgrad_deferred / ab_conv2d_stem_wgrad_deferred record the reduction they would
@@ -227,48 +216,22 @@ struct ReduceBatch {
     int block0[AB_WGRAD_BATCH_MAX + 1];          // first workgroup of descriptor i
     int n;
 };
-static inline int reduce_ky(int ns) { return ns <= 8 ? 4 : 16; }
+static inline __host__ __device__ int reduce_ky(int ns) { return ns <= 8 ? 4 : 16; }
 static inline long reduce_blocks(const ab_wgrad_reduce_desc& d) {
     const long total = (d.slab_elems / d.src_j) * d.dst_j;
     const int qx = 256 / reduce_ky(d.nslices);
     return (total / 4 + qx - 1) / qx;
 }
 
-// same arithmetic, in the same order, as wgrad_reduce<KY> of the descriptor's slice count: bit-identical results
+// the body of wgrad_reduce<KY> of the descriptor's slice count (a branch every lane of the workgroup takes alike)
 __global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(const ReduceBatch b) {
     __shared__ float4 part[16 * 17 + 4];
     int di = 0;
     while (di + 1 < b.n && (int)blockIdx.x >= b.block0[di + 1]) ++di;
     const ab_wgrad_reduce_desc& d = b.d[di];
-    const int KY = d.nslices <= 8 ? 4 : 16, QX = 256 / KY;
-    const int qx = threadIdx.x % QX, ky = threadIdx.x / QX;
-    const long quad = (long)((int)blockIdx.x - b.block0[di]) * QX + qx;
-    const long total = (d.slab_elems / d.src_j) * d.dst_j;
-    const long e = quad * 4;
-    const bool live = e < total;
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    int col = 0;
-    if (live) {
-        const long row = e / d.dst_j; col = (int)(e - row * d.dst_j);
-        const float* src = d.slabs + row * d.src_j + col;
-        for (int k = ky; k < d.nslices; k += KY) {
-            float4 v = *(const float4*)(src + (long)k * d.slab_elems);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-    }
-    part[ky * (QX + 1) + qx] = s;
-    __syncthreads();
-    if (ky == 0 && live) {
-        float4 t = part[qx];
-        for (int k = 1; k < KY; ++k) { float4 v = part[k * (QX + 1) + qx]; t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
-        if (d.stem_mask) {
-            if ((col & 31) >= 28) t = make_float4(0.f, 0.f, 0.f, 0.f);
-            t.w = 0.f;
-        }
-        float4* o = (float4*)(d.dst + e);
-        if (d.accumulate) { float4 v = *o; t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
-        *o = t;
-    }
+    const int block = (int)blockIdx.x - b.block0[di];
+    if (reduce_ky(d.nslices) == 4) reduce_slabs<4>(part, block, d.slabs, d.nslices, d.slab_elems, d.src_j, d.dst_j, d.dst, d.accumulate, d.stem_mask);
+    else reduce_slabs<16>(part, block, d.slabs, d.nslices, d.slab_elems, d.src_j, d.dst_j, d.dst, d.accumulate, d.stem_mask);
 }
 
 extern "C" int ab_wgrad_reduce_batch(const ab_wgrad_reduce_desc* desc, int n, void* stream) {
@@ -294,31 +257,20 @@ extern "C" int ab_wgrad_reduce_batch(const ab_wgrad_reduce_desc* desc, int n, vo
     return 0;
 }
 
-static int launch_reduce(const float* slabs, int ns, long slab_elems, int src_j, int dst_j, float* dst, int accumulate,
-                         int stem_mask, hipStream_t st) {
-    if (g_reduce_sink) {
-        ab_wgrad_reduce_desc* d = g_reduce_sink;
-        d->slabs = slabs; d->dst = dst; d->slab_elems = slab_elems; d->nslices = ns; d->src_j = src_j; d->dst_j = dst_j;
-        d->accumulate = accumulate; d->stem_mask = stem_mask;
-        return 0;
-    }
-    const long total = (slab_elems / src_j) * dst_j;
-    if (ns <= 8) wgrad_reduce<4><<<(unsigned)((total / 4 + 63) / 64), 256, 0, st>>>(slabs, ns, slab_elems, src_j, dst_j, dst, accumulate, stem_mask);
-    else wgrad_reduce<16><<<(unsigned)((total / 4 + 15) / 16), 256, 0, st>>>(slabs, ns, slab_elems, src_j, dst_j, dst, accumulate, stem_mask);
+int wgrad_launch_reduce(const float* slabs, int ns, long slab_elems, int src_j, int dst_j, float* dst, int accumulate,
+                        int stem_mask, hipStream_t st) {
+    ab_wgrad_reduce_desc d = {};
+    d.slabs = slabs; d.dst = dst; d.slab_elems = slab_elems; d.nslices = ns; d.src_j = src_j; d.dst_j = dst_j;
+    d.accumulate = accumulate; d.stem_mask = stem_mask;
+    if (g_reduce_sink) { *g_reduce_sink = d; return 0; }
+    const unsigned blocks = (unsigned)reduce_blocks(d);
+    if (reduce_ky(ns) == 4) wgrad_reduce<4><<<blocks, 256, 0, st>>>(slabs, ns, slab_elems, src_j, dst_j, dst, accumulate, stem_mask);
+    else wgrad_reduce<16><<<blocks, 256, 0, st>>>(slabs, ns, slab_elems, src_j, dst_j, dst, accumulate, stem_mask);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }
 
-// A launch that runs as two half-batches (conv_x3.hip, X3_WGRAD_MAX_M) must not record its reductions: both halves write the same
-// slab workspace and one descriptor holds one reduction.  It calls this first; each half then reduces at once, in stream order,
-// and the *_deferred caller's descriptor keeps nslices == 0 (nothing pending).
 void wgrad_reduce_now() { g_reduce_sink = nullptr; }
-
-// the fixed-order slab reduction for the weight-gradient kernels of other translation units (conv_x3.hip)
-int wgrad_launch_reduce(const float* slabs, int ns, long slab_elems, int src_j, int dst_j, float* dst, int accumulate,
-                        int stem_mask, hipStream_t st) {
-    return launch_reduce(slabs, ns, slab_elems, src_j, dst_j, dst, accumulate, stem_mask, st);
-}
 
 static void pick_wgrad(int M, int Cout, int jtot, int* bi, int* bj, int* nslices, int* rows) {
     *bi = (Cout % 128 == 0) ? 128 : 64;
@@ -327,18 +279,9 @@ static void pick_wgrad(int M, int Cout, int jtot, int* bi, int* bj, int* nslices
     int want = (int)((640 + tiles - 1) / tiles);            // ~2.5 workgroups per CU
     int maxs = (M + 1023) / 1024;                            // at least 1024 pixels per slice
     int ns = want < 1 ? 1 : want; if (ns > maxs) ns = maxs; if (ns < 1) ns = 1; if (ns > 512) ns = 512;
-    int r = (M + ns - 1) / ns; r = (r + 31) / 32 * 32;
-    *nslices = (M + r - 1) / r; *rows = r;
+    *rows = wgrad_rows_per_slice(M, ns, 32);
+    *nslices = (M + *rows - 1) / *rows;
 }
-
-int wgrad3x3_slices(int N, int H, int W, int Cin, int Cout);
-int wgrad3x3_run(const void* x, const void* dy, float* slabs, int N, int H, int W, int Cin, int Cout, hipStream_t st);
-int wgrad_gemm2_slices(int M, int Cout, int Cin, int ntaps);
-int wgrad_gemm2_max_slices(int M, int Cout, int jtot);
-int wgrad_gemm2_stem_slices(int N, int H, int W, int Cout);
-int wgrad_gemm2_stem_run(const void* xpad, const void* dy, float* slabs, int N, int H, int W, int Cout, hipStream_t st);
-int wgrad_gemm2_run(const void* x, const void* dy, float* slabs, int N, int H, int W, int Cin, int Cout, int kh, int kw,
-                    int stride, int pad, hipStream_t st);
 
 extern "C" long ab_conv2d_wgrad_workspace(int M, int Cout, int jtot) {
     int bi, bj, ns, rows; pick_wgrad(M, Cout, jtot, &bi, &bj, &ns, &rows);
@@ -354,8 +297,8 @@ extern "C" long ab_conv2d_wgrad_workspace(int M, int Cout, int jtot) {
 }
 
 template <typename T>
-static int launch_wgrad(const WgradArgs& g, int bi, int bj, hipStream_t st) {
-    dim3 grid((g.Cout / bi) * (g.jtot / bj), g.nslices);
+static int launch_wgrad(const WgradArgs& g, int bi, int bj, int ns, hipStream_t st) {
+    dim3 grid((g.Cout / bi) * (g.jtot / bj), ns);
     if (bi == 128 && bj == 128) wgrad_kernel<T, 128, 128><<<grid, 256, 0, st>>>(g);
     else if (bi == 128 && bj == 64) wgrad_kernel<T, 128, 64><<<grid, 256, 0, st>>>(g);
     else if (bi == 64 && bj == 128) wgrad_kernel<T, 64, 128><<<grid, 256, 0, st>>>(g);
@@ -367,11 +310,10 @@ static int launch_wgrad(const WgradArgs& g, int bi, int bj, hipStream_t st) {
 static int run_wgrad(WgradArgs& g, int dtype, float* dw, int dst_j, int accumulate, hipStream_t st, int stem_mask = 0) {
     int bi, bj, ns, rows; pick_wgrad(g.M, g.Cout, g.jtot, &bi, &bj, &ns, &rows);
     if (g.Cout % bi || g.jtot % bj) return AB_ESHAPE;
-    g.nslices = ns; g.rows_per_slice = rows;
-    int rc = dtype == AB_DT_BF16 ? launch_wgrad<bf16_t>(g, bi, bj, st) : dtype == AB_DT_F32 ? launch_wgrad<float>(g, bi, bj, st) : AB_EINVAL;
-    if (rc) return rc;
-    long slab = (long)g.Cout * g.jtot;
-    return launch_reduce(g.slabs, ns, slab, g.jtot, dst_j, dw, accumulate, stem_mask, st);
+    g.rows_per_slice = rows;
+    return wgrad_then_reduce([&] { return dtype == AB_DT_BF16 ? launch_wgrad<bf16_t>(g, bi, bj, ns, st)
+                                        : dtype == AB_DT_F32 ? launch_wgrad<float>(g, bi, bj, ns, st) : AB_EINVAL; },
+                             g.slabs, ns, g.Cout, g.jtot, dst_j, dw, accumulate, stem_mask, st);
 }
 
 // dw: float [Cout][kh][kw][Cin] (OHWI).  workspace: ab_conv2d_wgrad_workspace(N*Ho*Wo, Cout, kh*kw*Cin) bytes.
@@ -380,32 +322,23 @@ extern "C" int ab_conv2d_wgrad(const void* x, const void* dy, float* dw, int dty
                                void* stream) {
     if (!x || !dy || !dw || !workspace) return AB_EINVAL;
     if (kh * kw > 16 || Cin % 64 || Cout % 64) return AB_ESHAPE;
+    float* const slabs = (float*)workspace;
+    const hipStream_t st = as_stream(stream);
+    const int jtot = kh * kw * Cin;
     if (dtype == AB_DT_BF16 && kh == 3 && kw == 3 && stride == 1 && pad == 1) {
-        int ns = wgrad3x3_slices(N, H, W, Cin, Cout);
-        if (ns > 0) {
-            int rc = wgrad3x3_run(x, dy, (float*)workspace, N, H, W, Cin, Cout, as_stream(stream));
-            if (rc) return rc;
-            long slab = (long)Cout * 9 * Cin;
-            return launch_reduce((float*)workspace, ns, slab, 9 * Cin, 9 * Cin, dw, accumulate, 0, as_stream(stream));
-        }
+        if (int ns = wgrad3x3_slices(N, H, W, Cin, Cout))
+            return wgrad_then_reduce([&] { return wgrad3x3_run(x, dy, slabs, N, H, W, Cin, Cout, st); }, slabs, ns, Cout, jtot, jtot, dw,
+                                     accumulate, 0, st);
     }
     if (dtype == AB_DT_BF16) {
         const int M = N * ((H + 2 * pad - kh) / stride + 1) * ((W + 2 * pad - kw) / stride + 1);
-        int ns = wgrad_gemm2_slices(M, Cout, Cin, kh * kw);
-        if (ns > 0) {
-            int rc = wgrad_gemm2_run(x, dy, (float*)workspace, N, H, W, Cin, Cout, kh, kw, stride, pad, as_stream(stream));
-            if (rc) return rc;
-            long slab = (long)Cout * kh * kw * Cin;
-            return launch_reduce((float*)workspace, ns, slab, kh * kw * Cin, kh * kw * Cin, dw, accumulate, 0, as_stream(stream));
-        }
+        if (int ns = wgrad_gemm2_slices(M, Cout, Cin, kh * kw))
+            return wgrad_then_reduce([&] { return wgrad_gemm2_run(x, dy, slabs, N, H, W, Cin, Cout, kh, kw, stride, pad, st); }, slabs, ns,
+                                     Cout, jtot, jtot, dw, accumulate, 0, st);
     }
     WgradArgs g = {};
-    g.X = x; g.DY = dy; g.slabs = (float*)workspace;
-    g.N = N; g.Ha = H; g.Wa = W; g.Ca = Cin;
-    g.P = (H + 2 * pad - kh) / stride + 1; g.Q = (W + 2 * pad - kw) / stride + 1; g.Cout = Cout;
-    g.a_sh = g.a_sw = stride; g.ntaps = kh * kw; g.seglen = Cin; g.jtot = kh * kw * Cin; g.M = N * g.P * g.Q;
-    for (int i = 0; i < kh; ++i) for (int j = 0; j < kw; ++j) { g.dh[i * kw + j] = (int8_t)(i - pad); g.dw[i * kw + j] = (int8_t)(j - pad); }
-    return run_wgrad(g, dtype, dw, g.jtot, accumulate, as_stream(stream));
+    wgrad_fill_conv(g, x, dy, slabs, N, H, W, Cin, Cout, kh, kw, stride, pad);
+    return run_wgrad(g, dtype, dw, g.jtot, accumulate, st);
 }
 
 // Stem (see ab_conv2d_stem_fwd): x is the zero-bordered NHWC4 image; dw: float [Cout][7][8][4].
@@ -413,21 +346,16 @@ extern "C" int ab_conv2d_stem_wgrad(const void* xpad, const void* dy, float* dw,
                                     int Cout, void* workspace, void* stream) {
     if (!xpad || !dy || !dw || !workspace) return AB_EINVAL;
     if ((H & 1) || (W & 1) || Cout % 64) return AB_ESHAPE;
+    float* const slabs = (float*)workspace;
+    const hipStream_t st = as_stream(stream);
     if (dtype == AB_DT_BF16) {
-        int ns = wgrad_gemm2_stem_slices(N, H, W, Cout);
-        if (ns > 0) {
-            int rc = wgrad_gemm2_stem_run(xpad, dy, (float*)workspace, N, H, W, Cout, as_stream(stream));
-            if (rc) return rc;
-            return launch_reduce((float*)workspace, ns, (long)Cout * 256, 256, 7 * 32, dw, 0, 1, as_stream(stream));
-        }
+        if (int ns = wgrad_gemm2_stem_slices(N, H, W, Cout))
+            return wgrad_then_reduce([&] { return wgrad_gemm2_stem_run(xpad, dy, slabs, N, H, W, Cout, st); }, slabs, ns, Cout, 256, 7 * 32,
+                                     dw, 0, 1, st);
     }
     WgradArgs g = {};
-    g.X = xpad; g.DY = dy; g.slabs = (float*)workspace;
-    g.N = N; g.Ha = H + 6; g.Wa = W + 8; g.Ca = 4;
-    g.P = H / 2; g.Q = W / 2; g.Cout = Cout; g.a_sh = g.a_sw = 2;
-    g.ntaps = 8; g.seglen = 32; g.jtot = 256; g.M = N * g.P * g.Q;      // tap 7 is padding (in-bounds row, dropped below)
-    for (int i = 0; i < 8; ++i) { g.dh[i] = (int8_t)i; g.dw[i] = 0; }
-    return run_wgrad(g, dtype, dw, 7 * 32, 0, as_stream(stream), 1);
+    wgrad_fill_stem(g, xpad, dy, slabs, N, H, W, Cout);
+    return run_wgrad(g, dtype, dw, 7 * 32, 0, st, 1);
 }
 
 extern "C" long ab_conv2d_stem_wgrad_workspace(int N, int H, int W, int Cout) {
@@ -438,51 +366,35 @@ extern "C" long ab_conv2d_stem_wgrad_workspace(int N, int H, int W, int Cout) {
     return a > b ? a : b;
 }
 
-// As ab_conv2d_wgrad / ab_conv2d_stem_wgrad, but the final slab reduction is recorded in *pending instead of launched
-// (pending->nslices == 0 if the path had nothing to reduce).  `workspace` must stay untouched until ab_wgrad_reduce_batch
-// has consumed the descriptor -- one workspace per deferred call.
-extern "C" int ab_conv2d_wgrad_deferred(const void* x, const void* dy, float* dw, int dtype, int N, int H, int W, int Cin,
-                                        int Cout, int kh, int kw, int stride, int pad, void* workspace, int accumulate,
-                                        ab_wgrad_reduce_desc* pending, void* stream) {
+// As ab_conv2d_wgrad / ab_conv2d_stem_wgrad and their split-bf16 forms (conv_x3.hip), but the final slab reduction is recorded in
+// *pending instead of launched (pending->nslices == 0 if the path had nothing to reduce).  `workspace` must stay untouched until
+// ab_wgrad_reduce_batch has consumed the descriptor -- one workspace per deferred call.
+template <class Call>
+static int deferred(ab_wgrad_reduce_desc* pending, Call&& call) {
     if (!pending) return AB_EINVAL;
     *pending = ab_wgrad_reduce_desc{};
     g_reduce_sink = pending;
-    int rc = ab_conv2d_wgrad(x, dy, dw, dtype, N, H, W, Cin, Cout, kh, kw, stride, pad, workspace, accumulate, stream);
+    int rc = call();
     g_reduce_sink = nullptr;
     return rc;
 }
-// ... and of the split-bf16 weight gradients (conv_x3.hip)
-extern "C" int ab_conv2d_wgrad_x3(const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo, float* dw, int N,
-                                  int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, void* workspace,
-                                  int accumulate, void* stream);
-extern "C" int ab_conv2d_stem_wgrad_x3(const void* xpad_hi, const void* xpad_lo, const void* dy_hi, const void* dy_lo, float* dw,
-                                       int N, int H, int W, int Cout, void* workspace, void* stream);
+extern "C" int ab_conv2d_wgrad_deferred(const void* x, const void* dy, float* dw, int dtype, int N, int H, int W, int Cin,
+                                        int Cout, int kh, int kw, int stride, int pad, void* workspace, int accumulate,
+                                        ab_wgrad_reduce_desc* pending, void* stream) {
+    return deferred(pending, [&] { return ab_conv2d_wgrad(x, dy, dw, dtype, N, H, W, Cin, Cout, kh, kw, stride, pad, workspace, accumulate, stream); });
+}
 extern "C" int ab_conv2d_wgrad_x3_deferred(const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo, float* dw, int N,
                                            int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, void* workspace,
                                            int accumulate, ab_wgrad_reduce_desc* pending, void* stream) {
-    if (!pending) return AB_EINVAL;
-    *pending = ab_wgrad_reduce_desc{};
-    g_reduce_sink = pending;
-    int rc = ab_conv2d_wgrad_x3(x_hi, x_lo, dy_hi, dy_lo, dw, N, H, W, Cin, Cout, kh, kw, stride, pad, workspace, accumulate, stream);
-    g_reduce_sink = nullptr;
-    return rc;
+    return deferred(pending, [&] { return ab_conv2d_wgrad_x3(x_hi, x_lo, dy_hi, dy_lo, dw, N, H, W, Cin, Cout, kh, kw, stride, pad, workspace, accumulate, stream); });
 }
 extern "C" int ab_conv2d_stem_wgrad_x3_deferred(const void* xpad_hi, const void* xpad_lo, const void* dy_hi, const void* dy_lo,
                                                 float* dw, int N, int H, int W, int Cout, void* workspace,
                                                 ab_wgrad_reduce_desc* pending, void* stream) {
-    if (!pending) return AB_EINVAL;
-    *pending = ab_wgrad_reduce_desc{};
-    g_reduce_sink = pending;
-    int rc = ab_conv2d_stem_wgrad_x3(xpad_hi, xpad_lo, dy_hi, dy_lo, dw, N, H, W, Cout, workspace, stream);
-    g_reduce_sink = nullptr;
-    return rc;
+    return deferred(pending, [&] { return ab_conv2d_stem_wgrad_x3(xpad_hi, xpad_lo, dy_hi, dy_lo, dw, N, H, W, Cout, workspace, stream); });
 }
 extern "C" int ab_conv2d_stem_wgrad_deferred(const void* xpad, const void* dy, float* dw, int dtype, int N, int H, int W,
                                              int Cout, void* workspace, ab_wgrad_reduce_desc* pending, void* stream) {
-    if (!pending) return AB_EINVAL;
-    *pending = ab_wgrad_reduce_desc{};
-    g_reduce_sink = pending;
-    int rc = ab_conv2d_stem_wgrad(xpad, dy, dw, dtype, N, H, W, Cout, workspace, stream);
-    g_reduce_sink = nullptr;
-    return rc;
+    return deferred(pending, [&] { return ab_conv2d_stem_wgrad(xpad, dy, dw, dtype, N, H, W, Cout, workspace, stream); });
 }
+

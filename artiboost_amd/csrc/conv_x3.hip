@@ -8,6 +8,7 @@
 // residual addends, BatchNorm partials and weight-gradient slabs in fp32.  The kernels are the X3 instantiations of
 // conv3x3.hip / conv_gemm2.hip (forward, data gradient) and wgrad3x3.hip / wgrad_gemm2.hip (weight gradient).
 #include "conv_common.h"
+#include "wgrad.h"
 
 int conv3x3_x3_tiles(int N, int H, int W, int C, int Cn);
 int conv3x3_x3_tiles_bnr(int N, int H, int W, int C, int Cn);
@@ -17,20 +18,8 @@ int conv3x3_x3_run(const void* x_hi, const void* x_lo, const void* wt_hi, const 
                    const void* bn_out_hi = nullptr, const float* bnp = nullptr, float* bn_part = nullptr, const C3EvalBn* ev = nullptr);
 int conv_gemm2_x3_mtiles(int M, int Cn, int nsteps, int nclass);
 int conv_gemm2_x3_run(ConvGemmArgs& g, hipStream_t st);
-int wgrad3x3_x3_slices(int N, int H, int W, int Cin, int Cout);
-int wgrad3x3_x3_run(const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo, float* slabs, int N, int H, int W,
-                    int Cin, int Cout, hipStream_t st);
-int wgrad3x3_x3_group_slices(int G, int N, int H, int W, int Cin, int Cout);
-int wgrad3x3_x3_group_run(int G, const void* const* x_hi, const void* const* x_lo, const void* const* dy_hi, const void* const* dy_lo,
-                          float* const* slabs, int N, int H, int W, int Cin, int Cout, hipStream_t st);
-int wgrad_gemm2_x3_slices(int M, int Cout, int Cin, int ntaps);
-int wgrad_gemm2_x3_run(const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo, float* slabs, int N, int H, int W,
-                       int Cin, int Cout, int kh, int kw, int stride, int pad, hipStream_t st);
 int conv_gemm2_x3_stem_mtiles(int M);
 int conv_gemm2_x3_stem_run(ConvGemmArgs& g, hipStream_t st);
-int wgrad_gemm2_stem_slices(int N, int H, int W, int Cout);
-int wgrad_gemm2_x3_stem_run(const void* xpad_hi, const void* xpad_lo, const void* dy_hi, const void* dy_lo, float* slabs, int N,
-                            int H, int W, int Cout, hipStream_t st);
 int stem_halo_x3_tiles(int N, int H, int W);                   // stem_halo.hip
 int stem_halo_x3_run(const void* xpad_hi, const void* xpad_lo, const void* w_hi, const void* w_lo, float* y, int N, int H, int W,
                      int Cout, float* stats, hipStream_t st);
@@ -54,9 +43,6 @@ struct GemmRwSam { float* part; int C, D, H, W; };              // gemm_rw.hip
 int gemm_rw_ok(long M, int N, int K);
 int gemm_rw_run(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias, float* out, long M, int N,
                 int K, const GemmRwSam* sam, hipStream_t st);
-int wgrad_launch_reduce(const float* slabs, int ns, long slab_elems, int src_j, int dst_j, float* dst, int accumulate,
-                           int stem_mask, hipStream_t st);      // conv_wgrad.hip
-void wgrad_reduce_now();                                        // conv_wgrad.hip: a *_deferred call in progress reduces immediately instead
 
 // ---------------------------------------------------------------- fp32 -> (hi, lo) bf16 planes
 __global__ __launch_bounds__(256) void split_f32_kernel(const float* __restrict__ src, long nvec, bf16_t* __restrict__ hi,
@@ -364,7 +350,7 @@ extern "C" long ab_conv2d_wgrad_x3_workspace(int N, int H, int W, int Cin, int C
     if (kh * kw > 16 || Cin % 64 || Cout % 64) return 0;
     const long slab = (long)Cout * kh * kw * Cin * 4;
     if (x3_is_c3(kh, kw, stride, pad)) {
-        int ns = wgrad3x3_x3_slices(N, H, W, Cin, Cout);
+        int ns = wgrad3x3_x3_group_slices(1, N, H, W, Cin, Cout);
         if (ns > 0) return ns * slab;
     }
     const long Mi = (long)((H + 2 * pad - kh) / stride + 1) * ((W + 2 * pad - kw) / stride + 1);
@@ -416,14 +402,12 @@ extern "C" int ab_conv2d_wgrad_x3(const void* x_hi, const void* x_lo, const void
     // (same branch order as ab_conv2d_wgrad_x3_workspace: the all-taps 3x3 kernel where it applies, else the generic kernel --
     // split into half-batches beyond 2^21 output pixels, 3x3/s1 shapes the all-taps kernel declined included)
     hipStream_t st = as_stream(stream);
-    const long slab = (long)Cout * kh * kw * Cin;
+    float* const slabs = (float*)workspace;
+    const int jtot = kh * kw * Cin;
     if (x3_is_c3(kh, kw, stride, pad)) {
-        int ns = wgrad3x3_x3_slices(N, H, W, Cin, Cout);
-        if (ns > 0) {
-            int rc = wgrad3x3_x3_run(x_hi, x_lo, dy_hi, dy_lo, (float*)workspace, N, H, W, Cin, Cout, st);
-            if (rc) return rc;
-            return wgrad_launch_reduce((float*)workspace, ns, slab, 9 * Cin, 9 * Cin, dw, accumulate, 0, st);
-        }
+        if (int ns = wgrad3x3_x3_group_slices(1, N, H, W, Cin, Cout))       // the grouped launch with one problem
+            return wgrad_then_reduce([&] { return wgrad3x3_x3_group_run(1, &x_hi, &x_lo, &dy_hi, &dy_lo, &slabs, N, H, W, Cin, Cout, st); },
+                                     slabs, ns, Cout, jtot, jtot, dw, accumulate, 0, st);
     }
     {
         const long Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
@@ -440,9 +424,8 @@ extern "C" int ab_conv2d_wgrad_x3(const void* x_hi, const void* x_lo, const void
     const int M = N * ((H + 2 * pad - kh) / stride + 1) * ((W + 2 * pad - kw) / stride + 1);
     int ns = wgrad_gemm2_x3_slices(M, Cout, Cin, kh * kw);
     if (ns <= 0) return AB_ESHAPE;
-    int rc = wgrad_gemm2_x3_run(x_hi, x_lo, dy_hi, dy_lo, (float*)workspace, N, H, W, Cin, Cout, kh, kw, stride, pad, st);
-    if (rc) return rc;
-    return wgrad_launch_reduce((float*)workspace, ns, slab, kh * kw * Cin, kh * kw * Cin, dw, accumulate, 0, st);
+    return wgrad_then_reduce([&] { return wgrad_gemm2_x3_run(x_hi, x_lo, dy_hi, dy_lo, slabs, N, H, W, Cin, Cout, kh, kw, stride, pad, st); },
+                             slabs, ns, Cout, jtot, jtot, dw, accumulate, 0, st);
 }
 
 // ---------------------------------------------------------------- stem 7x7/2 (resnet.py:154) on split planes
@@ -479,9 +462,8 @@ static int stem_wgrad_x3_impl(const bf16_t* xpad_hi, const bf16_t* xpad_lo, cons
     }
     int ns = wgrad_gemm2_stem_slices(N, H, W, Cout);
     if (ns <= 0) return AB_ESHAPE;
-    int rc = wgrad_gemm2_x3_stem_run(xpad_hi, xpad_lo, dy_hi, dy_lo, (float*)workspace, N, H, W, Cout, st);
-    if (rc) return rc;
-    return wgrad_launch_reduce((float*)workspace, ns, (long)Cout * 256, 256, 7 * 32, dw, accumulate, 1, st);
+    return wgrad_then_reduce([&] { return wgrad_gemm2_x3_stem_run(xpad_hi, xpad_lo, dy_hi, dy_lo, (float*)workspace, N, H, W, Cout, st); },
+                             (float*)workspace, ns, Cout, 256, 7 * 32, dw, accumulate, 1, st);
 }
 
 extern "C" int ab_conv2d_stem_wgrad_x3(const void* xpad_hi, const void* xpad_lo, const void* dy_hi, const void* dy_lo, float* dw,

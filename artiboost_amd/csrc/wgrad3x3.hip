@@ -9,20 +9,14 @@
 // shifting the fragment address.  Both MFMA operands are reduction-major in HBM, so fragments come through the
 // gfx950 transpose read ds_read_b64_tr_b16 (4 pixels x 16 channels per 16-lane group), as in conv_wgrad.hip.
 //
-// LDS images (lane-linear LDS-DMA fills; swizzle on the source side): pixel q at byte q*128, logical 16-byte chunk c at
-// slot c ^ (((q >> 1) & 1) << 2)  -- swapping the 64-byte halves of every other pixel pair puts the four consecutive
-// pixels a transpose read touches on four distinct 64-byte bank groups.  The patch row pitch is W+4 pixels (a multiple
-// of 4) so that tap / k-slice displacements never change bit 1 of the pixel index: every fragment read is then
-// "lane base register + compile-time immediate".
+// LDS images (lane-linear LDS-DMA fills; swizzle on the source side): pixel q at byte q*128, its 16-byte chunks placed by
+// swz_chunk<128> (wgrad_common.h).  The patch row pitch is W+4 pixels (a multiple of 4) so that tap / k-slice displacements
+// never change bit 1 of the pixel index: every fragment read is then "lane base register + compile-time immediate".
 //
 // Partial results of the pixel slices go to separate slabs and are summed in fixed order by wgrad_reduce (no atomics).
-#include "conv_common.h"
+#include "wgrad_common.h"
+#include "wgrad.h"
 #include <type_traits>
-
-typedef short short4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) short4_t lds_short4;
-
-static __device__ uint4 wg3_zero_page[2];
 
 struct Wg3Args {
     const void* X; const void* DY; float* slabs;
@@ -37,13 +31,6 @@ struct Wg3Args {
     int ns_per;                 // 0: one problem
     const void* Xg[7]; const void* Xg_lo[7]; const void* DYg[7]; const void* DYg_lo[7]; float* slabsg[7];
 };
-
-__device__ __forceinline__ uint4 tr_pair(unsigned addr_lo, unsigned addr_hi) {
-    short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4*)(size_t)addr_lo);
-    short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4*)(size_t)addr_hi);
-    uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-    return make_uint4(l2.x, l2.y, h2.x, h2.y);
-}
 
 // NW = 4: every wave (2 co-halves x 2 ci-halves) accumulates all nine taps.  NW = 8: the taps are split 5 + 4 over two
 // groups of four waves -- twice the waves issue the band / patch DMA (the L2->LDS fill rate scales with the number of
@@ -89,7 +76,7 @@ __global__ __launch_bounds__(64 * NW) void wgrad3x3_kernel(Wg3Args g) {
     const bf16_t* __restrict__ DY = (const bf16_t*)pDY;
     const bf16_t* __restrict__ Xl = (const bf16_t*)pXl;
     const bf16_t* __restrict__ DYl = (const bf16_t*)pDYl;
-    const bf16_t* zp = (const bf16_t*)wg3_zero_page;
+    const bf16_t* zp = (const bf16_t*)wg_zero_page;
 
     // ---- per-lane fill assignment
     long a_off[LA]; bool a_ok[LA];
@@ -98,8 +85,7 @@ __global__ __launch_bounds__(64 * NW) void wgrad3x3_kernel(Wg3Args g) {
         int ii = wave * LA + j;
         int p = ii * 8 + (lane >> 3);
         a_ok[j] = ii < IA;
-        int c = (lane & 7) ^ (((p >> 1) & 1) << 2);
-        a_off[j] = (long)p * g.Cout + co0 + c * 8;                 // + band pixel base * Cout
+        a_off[j] = (long)p * g.Cout + co0 + swz_chunk<128>(p, lane & 7) * 8;                 // + band pixel base * Cout
     }
     int x_pr[LX], x_pc[LX], x_c[LX]; bool x_in[LX];
 #pragma unroll
@@ -108,7 +94,7 @@ __global__ __launch_bounds__(64 * NW) void wgrad3x3_kernel(Wg3Args g) {
         int q = ii * 8 + (lane >> 3);
         x_pr[j] = q / PW; x_pc[j] = q - x_pr[j] * PW;
         x_in[j] = (ii < IX) && (q < NPIX) && x_pc[j] >= 1 && x_pc[j] <= W;
-        x_c[j] = ((lane & 7) ^ (((q >> 1) & 1) << 2)) * 8;
+        x_c[j] = swz_chunk<128>(q, lane & 7) * 8;
     }
     auto issue_band = [&](int band, int buf) {
         const int img = band / bands_per_img, y0 = (band - img * bands_per_img) * TH;
@@ -141,10 +127,7 @@ __global__ __launch_bounds__(64 * NW) void wgrad3x3_kernel(Wg3Args g) {
     // dy band: pixel p = 16*s + krow (+4); chunk / byte inside the pixel
     unsigned a_base[2];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        int p = krow + h * 4, col = wco + csub;
-        a_base[h] = p * 128 + (((col >> 3) ^ (((p >> 1) & 1) << 2)) << 4) + (col & 7) * 2;
-    }
+    for (int h = 0; h < 2; ++h) a_base[h] = frag_addr<128>(krow + h * 4, wco + csub);
     // patch: pixel q = (ty + kh)*PW + tx + kw + 1  with (ty, tx) of band pixel p; the lane part is q_lane = krow (+4) mapped
     // through the row layout below; bit 1 of q depends only on (tx + kw + 1): three variants per read half
     unsigned x_base[3][2];
@@ -154,11 +137,7 @@ __global__ __launch_bounds__(64 * NW) void wgrad3x3_kernel(Wg3Args g) {
 #pragma unroll
     for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            int q = ty_l[h] * PW + tx_l[h] + kw;                    // patch column = (tx + 1) + (kw - 1)
-            int col = wci + csub;
-            x_base[kw][h] = q * 128 + (((col >> 3) ^ (((q >> 1) & 1) << 2)) << 4) + (col & 7) * 2;
-        }
+        for (int h = 0; h < 2; ++h) x_base[kw][h] = frag_addr<128>(ty_l[h] * PW + tx_l[h] + kw, wci + csub);    // patch column = (tx + 1) + (kw - 1)
 
     f32x16 acc[NACC];
 #pragma unroll
@@ -197,11 +176,9 @@ __global__ __launch_bounds__(64 * NW) void wgrad3x3_kernel(Wg3Args g) {
                     rd_b(sl2, tt2, fb[(st + 1) & 1], fbl[(st + 1) & 1]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                const bf16x8 a = __builtin_bit_cast(bf16x8, fa[sl & 1]), al = __builtin_bit_cast(bf16x8, fal[sl & 1]);
-                const bf16x8 b = __builtin_bit_cast(bf16x8, fb[st & 1]), bl = __builtin_bit_cast(bf16x8, fbl[st & 1]);
-                acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[tt], 0, 0, 0);
-                acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bl, acc[tt], 0, 0, 0);
-                acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, b, acc[tt], 0, 0, 0);
+                mfma16(acc[tt], fa[sl & 1], fb[st & 1]);
+                mfma16(acc[tt], fa[sl & 1], fbl[st & 1]);
+                mfma16(acc[tt], fal[sl & 1], fb[st & 1]);
                 __builtin_amdgcn_sched_barrier(0);
             }
             return;
@@ -220,14 +197,11 @@ __global__ __launch_bounds__(64 * NW) void wgrad3x3_kernel(Wg3Args g) {
                 const int oy = p0 / W, ox = p0 % W;
                 const int disp = ((oy + kh) * PW + ox) * 128;
                 uint4 fb = tr_pair(x_cur[kw][0] + disp, x_cur[kw][1] + disp);
-                acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa), __builtin_bit_cast(bf16x8, fb),
-                                                                  acc[tt], 0, 0, 0);
+                mfma16(acc[tt], fa, fb);
                 if constexpr (X3) {
                     uint4 fbl = tr_pair(x_cur[kw][0] + XBYTES + disp, x_cur[kw][1] + XBYTES + disp);
-                    acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa), __builtin_bit_cast(bf16x8, fbl),
-                                                                      acc[tt], 0, 0, 0);
-                    acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fal), __builtin_bit_cast(bf16x8, fb),
-                                                                      acc[tt], 0, 0, 0);
+                    mfma16(acc[tt], fa, fbl);
+                    mfma16(acc[tt], fal, fb);
                 }
             }
         }
@@ -252,17 +226,9 @@ __global__ __launch_bounds__(64 * NW) void wgrad3x3_kernel(Wg3Args g) {
     }
     // ---- slab write: dW[co][tap][ci] (row length 9*Cin)
     float* out = pslabs + (long)by * g.Cout * 9 * g.Cin;
-    const int jt = 9 * g.Cin;
 #pragma unroll
-    for (int tt = 0; tt < NACC; ++tt) {
-        if (tt >= ntap) continue;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            int row = co0 + wco + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            int col = (t0 + tt) * g.Cin + ci0 + wci + (lane & 31);
-            out[(long)row * jt + col] = acc[tt][r];
-        }
-    }
+    for (int tt = 0; tt < NACC; ++tt)
+        if (tt < ntap) store_acc_tile(out, 9 * g.Cin, co0 + wco, (t0 + tt) * g.Cin + ci0 + wci, acc[tt]);
 }
 
 template <int W, int TH, int NW, int X3 = 0>
@@ -292,87 +258,29 @@ static int wg3_launch(Wg3Args& g, int tiles, int nslices, hipStream_t st) {
     return e == hipSuccess ? 0 : (int)e;
 }
 
-static int wg3_th(int H, int W) {
-    if (W == 64 && H % 2 == 0) return 2;
-    if (W == 32 && H % 4 == 0) return 4;
-    if (W == 16 && H % 8 == 0) return 8;
-    if (W == 8 && H % 8 == 0) return 8;
-    return 0;
+// band rows: bands of 128 pixels, 64 on split-bf16 planes (two stages of both planes fit in LDS); a W = 8 band is the whole 8 x 8 map
+static constexpr int wg3_band_rows(int W, int x3) { return W == 8 ? 8 : (x3 ? 64 : 128) / W; }
+static int wg3_th(int H, int W, int x3) {
+    if (W != 64 && W != 32 && W != 16 && W != 8) return 0;
+    const int th = wg3_band_rows(W, x3);
+    return H % th == 0 ? th : 0;
 }
 
-// returns the number of slabs (pixel slices) this kernel will write, 0 when the shape is not handled here
-int wgrad3x3_slices(int N, int H, int W, int Cin, int Cout) {
-    int th = wg3_th(H, W);
-    if (!th || Cin % 64 || Cout % 64 || getenv("AB_WGRAD3_OFF")) return 0;
-    int nbands = N * (H / th);
-    int tiles = (Cin / 64) * (Cout / 64);
-    static int target = getenv("AB_WG3_TARGET") ? atoi(getenv("AB_WG3_TARGET")) : 256;
-    int want = (target + tiles - 1) / tiles;
-    int ns = want < 1 ? 1 : want;
-    if (ns > nbands / 2) ns = nbands / 2 > 0 ? nbands / 2 : 1;      // at least two bands per slice (double buffering)
-    if (ns > 256) ns = 256;
-    int bps = (nbands + ns - 1) / ns;
-    return (nbands + bps - 1) / bps;
+template <int NW, int X3>
+static int wg3_dispatch(int W, Wg3Args& g, int nslices, hipStream_t st) {
+    const int tiles = (g.Cin / 64) * (g.Cout / 64);
+    if (W == 64) return wg3_launch<64, wg3_band_rows(64, X3), NW, X3>(g, tiles, nslices, st);
+    if (W == 32) return wg3_launch<32, wg3_band_rows(32, X3), NW, X3>(g, tiles, nslices, st);
+    if (W == 16) return wg3_launch<16, wg3_band_rows(16, X3), NW, X3>(g, tiles, nslices, st);
+    return wg3_launch<8, 8, NW, X3>(g, tiles, nslices, st);
 }
 
-int wgrad3x3_run(const void* x, const void* dy, float* slabs, int N, int H, int W, int Cin, int Cout, hipStream_t st) {
-    int ns = wgrad3x3_slices(N, H, W, Cin, Cout);
-    if (!ns) return AB_ESHAPE;
-    int th = wg3_th(H, W);
-    Wg3Args g = {};
-    g.X = x; g.DY = dy; g.slabs = slabs; g.N = N; g.H = H; g.Cin = Cin; g.Cout = Cout;
-    g.nbands = N * (H / th);
-    g.bands_per_slice = (g.nbands + ns - 1) / ns;
-    int tiles = (Cin / 64) * (Cout / 64);
-    static const int w8 = getenv("AB_WG3_W8") ? atoi(getenv("AB_WG3_W8")) : 1;
-    if (w8) {
-        if (W == 64) return wg3_launch<64, 2, 8>(g, tiles, ns, st);
-        if (W == 32) return wg3_launch<32, 4, 8>(g, tiles, ns, st);
-        if (W == 16) return wg3_launch<16, 8, 8>(g, tiles, ns, st);
-        return wg3_launch<8, 8, 8>(g, tiles, ns, st);
-    }
-    if (W == 64) return wg3_launch<64, 2, 4>(g, tiles, ns, st);
-    if (W == 32) return wg3_launch<32, 4, 4>(g, tiles, ns, st);
-    if (W == 16) return wg3_launch<16, 8, 4>(g, tiles, ns, st);
-    return wg3_launch<8, 8, 4>(g, tiles, ns, st);
-}
-
-// ---- split-bf16 ("bf16x3") launches: bands of 64 pixels (two stages of both planes fit in LDS)
-static int wg3x_th(int H, int W) {
-    if (W == 64) return 1;
-    if (W == 32 && H % 2 == 0) return 2;
-    if (W == 16 && H % 4 == 0) return 4;
-    if (W == 8 && H % 8 == 0) return 8;
-    return 0;
-}
-
-int wgrad3x3_x3_slices(int N, int H, int W, int Cin, int Cout) {
-    int th = wg3x_th(H, W);
-    if (!th || Cin % 64 || Cout % 64) return 0;
-    int nbands = N * (H / th);
-    int tiles = (Cin / 64) * (Cout / 64);
-    // (AB_WG3X_TARGET: workgroups per launch the slice count aims at; 256 = one per CU.  512 was tried for review item 7 -- launches that lose
-    // a CU to a collective's kernel then lose 1/512 of their work instead of running a second round: see DESIGN 14.3)
-    static const int target = getenv("AB_WG3X_TARGET") ? atoi(getenv("AB_WG3X_TARGET")) : 256;
-    int want = (target + tiles - 1) / tiles;
-    int ns = want < 1 ? 1 : want;
-    if (ns > nbands / 2) ns = nbands / 2 > 0 ? nbands / 2 : 1;
-    if (ns > 256) ns = 256;
-    int bps = (nbands + ns - 1) / ns;
-    return (nbands + bps - 1) / bps;
-}
-
-// slices PER PROBLEM of a grouped launch over G same-shape layers (0: shape not handled): the single-launch rule with the workgroup target
-// divided by G -- and at least two bands per slice, as there
-int wgrad3x3_x3_group_slices(int G, int N, int H, int W, int Cin, int Cout) {
-    int th = wg3x_th(H, W);
-    if (!th || Cin % 64 || Cout % 64 || G < 1 || G > 8) return 0;
-    int nbands = N * (H / th);
-    int tiles = (Cin / 64) * (Cout / 64);
-    static const int target = getenv("AB_WG3X_TARGET") ? atoi(getenv("AB_WG3X_TARGET")) : 256;
-    // floor, not the single launch's ceil: 16 tiles x 3 problems x ceil(256 / 48) = 288 workgroups ran as a second round on 32 CUs
-    // (measured: the step 0.45 ms SLOWER with groups of three than ungrouped); x 5 = 240 fill 94 % of the chip in one round
-    if (G > 1 && tiles * G > target) return 0;          // (more problems than one round of workgroups holds: the caller groups fewer)
+// Slices per problem for G same-shape problems in one grid: `target` workgroups over the tiles, at least two bands per slice (double
+// buffering), at most 256 slices.  G > 1 rounds the share of a problem down, not up as the single launch does: 16 tiles x 3 problems x
+// ceil(256 / 48) = 288 workgroups ran as a second round on 32 CUs (measured: the step 0.45 ms SLOWER with groups of three than ungrouped);
+// x 5 = 240 fill 94 % of the chip in one round.  0: more problems than one round of workgroups holds (the caller groups fewer).
+static int wg3_slice_rule(int nbands, int tiles, int target, int G) {
+    if (G > 1 && tiles * G > target) return 0;
     int want = G > 1 ? target / (tiles * G) : (target + tiles - 1) / tiles;
     int ns = want < 1 ? 1 : want;
     if (ns > nbands / 2) ns = nbands / 2 > 0 ? nbands / 2 : 1;
@@ -381,12 +289,9 @@ int wgrad3x3_x3_group_slices(int G, int N, int H, int W, int Cin, int Cout) {
     return (nbands + bps - 1) / bps;
 }
 
-// G <= 8 same-shape problems in one grid; slabs[p]: problem p's [ns][Cout][9][Cin] partials
-int wgrad3x3_x3_group_run(int G, const void* const* x_hi, const void* const* x_lo, const void* const* dy_hi, const void* const* dy_lo,
-                          float* const* slabs, int N, int H, int W, int Cin, int Cout, hipStream_t st) {
-    int ns = wgrad3x3_x3_group_slices(G, N, H, W, Cin, Cout);
-    if (!ns) return AB_ESHAPE;
-    int th = wg3x_th(H, W);
+// G problems of ns slices each over bands of th rows; problem p's planes and slabs are entry p of the arrays
+static Wg3Args wg3_args(int G, const void* const* x_hi, const void* const* x_lo, const void* const* dy_hi, const void* const* dy_lo,
+                        float* const* slabs, int N, int H, int Cin, int Cout, int th, int ns) {
     Wg3Args g = {};
     g.X = x_hi[0]; g.X_lo = x_lo[0]; g.DY = dy_hi[0]; g.DY_lo = dy_lo[0]; g.slabs = slabs[0];
     for (int p = 1; p < G; ++p) { g.Xg[p - 1] = x_hi[p]; g.Xg_lo[p - 1] = x_lo[p]; g.DYg[p - 1] = dy_hi[p]; g.DYg_lo[p - 1] = dy_lo[p]; g.slabsg[p - 1] = slabs[p]; }
@@ -394,25 +299,39 @@ int wgrad3x3_x3_group_run(int G, const void* const* x_hi, const void* const* x_l
     g.N = N; g.H = H; g.Cin = Cin; g.Cout = Cout;
     g.nbands = N * (H / th);
     g.bands_per_slice = (g.nbands + ns - 1) / ns;
-    int tiles = (Cin / 64) * (Cout / 64);
-    if (W == 64) return wg3_launch<64, 1, 8, 1>(g, tiles, ns * G, st);
-    if (W == 32) return wg3_launch<32, 2, 8, 1>(g, tiles, ns * G, st);
-    if (W == 16) return wg3_launch<16, 4, 8, 1>(g, tiles, ns * G, st);
-    return wg3_launch<8, 8, 8, 1>(g, tiles, ns * G, st);
+    return g;
 }
 
-int wgrad3x3_x3_run(const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo, float* slabs, int N, int H, int W,
-                    int Cin, int Cout, hipStream_t st) {
-    int ns = wgrad3x3_x3_slices(N, H, W, Cin, Cout);
-    if (!ns) return AB_ESHAPE;
-    int th = wg3x_th(H, W);
-    Wg3Args g = {};
-    g.X = x_hi; g.X_lo = x_lo; g.DY = dy_hi; g.DY_lo = dy_lo; g.slabs = slabs; g.N = N; g.H = H; g.Cin = Cin; g.Cout = Cout;
-    g.nbands = N * (H / th);
-    g.bands_per_slice = (g.nbands + ns - 1) / ns;
-    int tiles = (Cin / 64) * (Cout / 64);
-    if (W == 64) return wg3_launch<64, 1, 8, 1>(g, tiles, ns, st);
-    if (W == 32) return wg3_launch<32, 2, 8, 1>(g, tiles, ns, st);
-    if (W == 16) return wg3_launch<16, 4, 8, 1>(g, tiles, ns, st);
-    return wg3_launch<8, 8, 8, 1>(g, tiles, ns, st);
+int wgrad3x3_slices(int N, int H, int W, int Cin, int Cout) {
+    int th = wg3_th(H, W, 0);
+    if (!th || Cin % 64 || Cout % 64 || getenv("AB_WGRAD3_OFF")) return 0;
+    static int target = getenv("AB_WG3_TARGET") ? atoi(getenv("AB_WG3_TARGET")) : 256;
+    return wg3_slice_rule(N * (H / th), (Cin / 64) * (Cout / 64), target, 1);
 }
+
+int wgrad3x3_run(const void* x, const void* dy, float* slabs, int N, int H, int W, int Cin, int Cout, hipStream_t st) {
+    int ns = wgrad3x3_slices(N, H, W, Cin, Cout);
+    if (!ns) return AB_ESHAPE;
+    const void* no_lo = nullptr;
+    Wg3Args g = wg3_args(1, &x, &no_lo, &dy, &no_lo, &slabs, N, H, Cin, Cout, wg3_th(H, W, 0), ns);
+    static const int w8 = getenv("AB_WG3_W8") ? atoi(getenv("AB_WG3_W8")) : 1;
+    return w8 ? wg3_dispatch<8, 0>(W, g, ns, st) : wg3_dispatch<4, 0>(W, g, ns, st);
+}
+
+int wgrad3x3_x3_group_slices(int G, int N, int H, int W, int Cin, int Cout) {
+    int th = wg3_th(H, W, 1);
+    if (!th || Cin % 64 || Cout % 64 || G < 1 || G > 8) return 0;
+    // (AB_WG3X_TARGET: workgroups per launch the slice count aims at; 256 = one per CU.  512 was tried for review item 7 -- launches that lose
+    // a CU to a collective's kernel then lose 1/512 of their work instead of running a second round: see DESIGN 14.3)
+    static const int target = getenv("AB_WG3X_TARGET") ? atoi(getenv("AB_WG3X_TARGET")) : 256;
+    return wg3_slice_rule(N * (H / th), (Cin / 64) * (Cout / 64), target, G);
+}
+
+int wgrad3x3_x3_group_run(int G, const void* const* x_hi, const void* const* x_lo, const void* const* dy_hi, const void* const* dy_lo,
+                          float* const* slabs, int N, int H, int W, int Cin, int Cout, hipStream_t st) {
+    int ns = wgrad3x3_x3_group_slices(G, N, H, W, Cin, Cout);
+    if (!ns) return AB_ESHAPE;
+    Wg3Args g = wg3_args(G, x_hi, x_lo, dy_hi, dy_lo, slabs, N, H, Cin, Cout, wg3_th(H, W, 1), ns);
+    return wg3_dispatch<8, 1>(W, g, ns * G, st);
+}
+

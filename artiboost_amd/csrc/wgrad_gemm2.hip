@@ -9,16 +9,11 @@
 // A workgroup owns BI output channels x BJ columns of ONE tap (BJ | Cin) over a slice of the pixels; slices write
 // separate fp32 slabs that wgrad_reduce sums in fixed order.
 //
-// LDS image of a tile: row r (a pixel) at byte r*P, P = 2*B (128 or 256 bytes, lane-linear DMA so no padding); the
-// 16-byte chunk c of a row is stored at slot c ^ (f(r) << 2) with f(r) = (r >> 1) & 1 for P = 128 and r & 3 for P = 256:
-// the four consecutive rows x 64 bytes a transpose read touches then sit on four distinct 64-byte bank groups.
+// LDS image of a tile: row r (a pixel) at byte r*P, P = 2*B (128 bytes or more, lane-linear DMA so no padding), its 16-byte
+// chunks placed by swz_chunk<P> (wgrad_common.h).
 // Pixel -> (image, row, col) uses host-made multiply-shift reciprocals (exact and overflow-free for m < 2^21).
-#include "conv_common.h"
-
-typedef short short4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) short4_t lds_short4;
-
-static __device__ uint4 wg2_zero_page[2];
+#include "wgrad_common.h"
+#include "wgrad.h"
 
 struct Wg2Args {
     const void* X; const void* DY; float* slabs;
@@ -35,15 +30,6 @@ struct Wg2Args {
 
 __device__ __forceinline__ int fastdiv(int n, unsigned long long magic) {
     return (int)(((unsigned long long)(unsigned)n * magic) >> 42);
-}
-
-template <int B> __device__ __forceinline__ int swz(int row) { return (B == 64) ? ((row >> 1) & 1) : (row & 3); }
-
-__device__ __forceinline__ uint4 wg2_tr_pair(unsigned lo_addr, unsigned hi_addr) {
-    short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4*)(size_t)lo_addr);
-    short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4*)(size_t)hi_addr);
-    uint2 l2 = __builtin_bit_cast(uint2, lo), h2 = __builtin_bit_cast(uint2, hi);
-    return make_uint4(l2.x, l2.y, h2.x, h2.y);
 }
 
 // STEM: x is the zero-bordered NHWC4 image and a dW row is [8 kernel rows (7 + 1 pad)][8 px][4 ch] = 256 columns (see
@@ -89,7 +75,7 @@ __global__ __launch_bounds__(64 * WI * WJ) void wgrad_gemm2_kernel(Wg2Args g) {
     const bf16_t* __restrict__ DY = (const bf16_t*)g.DY;
     const bf16_t* __restrict__ Xl = (const bf16_t*)g.X_lo;
     const bf16_t* __restrict__ DYl = (const bf16_t*)g.DY_lo;
-    const bf16_t* zp = (const bf16_t*)wg2_zero_page;
+    const bf16_t* zp = (const bf16_t*)wg_zero_page;
 
     // per-lane DMA assignment: instruction ii covers rows ii*R .. ii*R+R-1; lane -> (row in instr, slot); the lane fetches
     // the logical chunk that belongs in its slot
@@ -101,7 +87,7 @@ __global__ __launch_bounds__(64 * WI * WJ) void wgrad_gemm2_kernel(Wg2Args g) {
         const int ii = wave * LA + j;
         a_pl[j] = ii >= IA1;
         int r = (ii % IA1) * RA + lane / LPR, slot = lane % LPR;
-        a_row[j] = r; a_col[j] = (slot ^ (swz<BI>(r) << 2)) * 8;
+        a_row[j] = r; a_col[j] = swz_chunk<PA>(r, slot) * 8;
     }
 #pragma unroll
     for (int j = 0; j < LB; ++j) {
@@ -109,7 +95,7 @@ __global__ __launch_bounds__(64 * WI * WJ) void wgrad_gemm2_kernel(Wg2Args g) {
         const int ii = wave * LB + j;
         b_pl[j] = ii >= IB1;
         int r = (ii % IB1) * RB + lane / LPR, slot = lane % LPR;
-        int c = slot ^ (swz<BJ>(r) << 2);
+        int c = swz_chunk<PB>(r, slot);
         b_row[j] = r; b_col[j] = STEM ? (c >> 2) * g.Wa * 4 + (c & 3) * 8 : c * 8;
     }
     // The pixel -> input-offset arithmetic (two divisions per row) is done ONCE per row by the first wave and handed to the
@@ -151,15 +137,9 @@ __global__ __launch_bounds__(64 * WI * WJ) void wgrad_gemm2_kernel(Wg2Args g) {
     for (int h = 0; h < 2; ++h) {
         const int r = krow + 4 * h;
 #pragma unroll
-        for (int a = 0; a < TI; ++a) {
-            int col = (wave_i * TI + a) * 32 + csub;
-            a_base[a][h] = lds0 + r * PA + (((col >> 3) ^ (swz<BI>(r) << 2)) << 4) + (col & 7) * 2;
-        }
+        for (int a = 0; a < TI; ++a) a_base[a][h] = lds0 + frag_addr<PA>(r, (wave_i * TI + a) * 32 + csub);
 #pragma unroll
-        for (int b = 0; b < TJ; ++b) {
-            int col = (wave_j * TJ + b) * 32 + csub;
-            b_base[b][h] = lds0 + ABYTES + r * PB + (((col >> 3) ^ (swz<BJ>(r) << 2)) << 4) + (col & 7) * 2;
-        }
+        for (int b = 0; b < TJ; ++b) b_base[b][h] = lds0 + ABYTES + frag_addr<PB>(r, (wave_j * TJ + b) * 32 + csub);
     }
 
     f32x16 acc[TI][TJ];
@@ -195,39 +175,27 @@ __global__ __launch_bounds__(64 * WI * WJ) void wgrad_gemm2_kernel(Wg2Args g) {
         for (int s = 0; s < BR / 16; ++s) {
             uint4 fa[TI], fb[TJ];
 #pragma unroll
-            for (int a = 0; a < TI; ++a) fa[a] = wg2_tr_pair(a_base[a][0] + so + s * 16 * PA, a_base[a][1] + so + s * 16 * PA);
+            for (int a = 0; a < TI; ++a) fa[a] = tr_pair(a_base[a][0] + so + s * 16 * PA, a_base[a][1] + so + s * 16 * PA);
 #pragma unroll
-            for (int b = 0; b < TJ; ++b) fb[b] = wg2_tr_pair(b_base[b][0] + so + s * 16 * PB, b_base[b][1] + so + s * 16 * PB);
+            for (int b = 0; b < TJ; ++b) fb[b] = tr_pair(b_base[b][0] + so + s * 16 * PB, b_base[b][1] + so + s * 16 * PB);
 #pragma unroll
             for (int a = 0; a < TI; ++a)
 #pragma unroll
-                for (int b = 0; b < TJ; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[a]),
-                                                                       __builtin_bit_cast(bf16x8, fb[b]), acc[a][b], 0, 0, 0);
-            if constexpr (X3 == 2) {
-                uint4 fal[TI];
-#pragma unroll
-                for (int a = 0; a < TI; ++a) fal[a] = wg2_tr_pair(a_base[a][0] + so + APL + s * 16 * PA, a_base[a][1] + so + APL + s * 16 * PA);
-#pragma unroll
-                for (int a = 0; a < TI; ++a)
-#pragma unroll
-                    for (int b = 0; b < TJ; ++b)
-                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fal[a]),
-                                                                           __builtin_bit_cast(bf16x8, fb[b]), acc[a][b], 0, 0, 0);
-            } else if constexpr (X3) {
+                for (int b = 0; b < TJ; ++b) mfma16(acc[a][b], fa[a], fb[b]);
+            if constexpr (X3) {                              // hi*hi above for every tile of the wave, then hi*lo (X3 = 1) and lo*hi per tile
                 uint4 fal[TI], fbl[TJ];
 #pragma unroll
-                for (int a = 0; a < TI; ++a) fal[a] = wg2_tr_pair(a_base[a][0] + so + APL + s * 16 * PA, a_base[a][1] + so + APL + s * 16 * PA);
+                for (int a = 0; a < TI; ++a) fal[a] = tr_pair(a_base[a][0] + so + APL + s * 16 * PA, a_base[a][1] + so + APL + s * 16 * PA);
+                if constexpr (X3 == 1) {
 #pragma unroll
-                for (int b = 0; b < TJ; ++b) fbl[b] = wg2_tr_pair(b_base[b][0] + so + BPL + s * 16 * PB, b_base[b][1] + so + BPL + s * 16 * PB);
+                    for (int b = 0; b < TJ; ++b) fbl[b] = tr_pair(b_base[b][0] + so + BPL + s * 16 * PB, b_base[b][1] + so + BPL + s * 16 * PB);
+                }
 #pragma unroll
                 for (int a = 0; a < TI; ++a)
 #pragma unroll
                     for (int b = 0; b < TJ; ++b) {
-                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[a]),
-                                                                           __builtin_bit_cast(bf16x8, fbl[b]), acc[a][b], 0, 0, 0);
-                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fal[a]),
-                                                                           __builtin_bit_cast(bf16x8, fb[b]), acc[a][b], 0, 0, 0);
+                        if constexpr (X3 == 1) mfma16(acc[a][b], fa[a], fbl[b]);
+                        mfma16(acc[a][b], fal[a], fb[b]);
                     }
             }
         }
@@ -238,15 +206,25 @@ __global__ __launch_bounds__(64 * WI * WJ) void wgrad_gemm2_kernel(Wg2Args g) {
     for (int a = 0; a < TI; ++a)
 #pragma unroll
         for (int b = 0; b < TJ; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int row = i0 + (wave_i * TI + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                int col = j0 + (wave_j * TJ + b) * 32 + (lane & 31);
-                if (!PARTIAL_I || row < g.Cout) out[(long)row * g.jtot + col] = X3 == 2 ? acc[a][b][r] * (1.0f / 510.0f) : acc[a][b][r];
-            }
+            store_acc_tile<PARTIAL_I, X3 == 2>(out, g.jtot, i0 + (wave_i * TI + a) * 32, j0 + (wave_j * TJ + b) * 32, acc[a][b], g.Cout, 1.0f / 510.0f);
 }
 
-static int wg2_xcd_map() { static const int v = getenv("AB_WG_XCD") ? atoi(getenv("AB_WG_XCD")) : 1; return v; }
+// what the kernel needs beside the problem (wgrad.h): the lo planes, the reciprocals of the pixel decomposition, the slice length
+static void wg2_finish(Wg2Args& g, const void* x_lo, const void* dy_lo, int rows_per_slice) {
+    static const int xcd = getenv("AB_WG_XCD") ? atoi(getenv("AB_WG_XCD")) : 1;
+    g.X_lo = x_lo; g.DY_lo = dy_lo;
+    g.magic_pq = (1ull << 42) / (unsigned long long)(g.P * g.Q) + 1;
+    g.magic_q = (1ull << 42) / (unsigned long long)g.Q + 1;
+    g.rows_per_slice = rows_per_slice;
+    g.xcd_map = xcd;
+}
+
+template <int BI, int BJ, bool STEM = false, int WI = 2, int WJ = 2, int X3 = 0, int NBUF = 3>
+static int wg2_launch(const Wg2Args& g, dim3 grid, hipStream_t st) {
+    wgrad_gemm2_kernel<BI, BJ, STEM, WI, WJ, X3, NBUF><<<grid, 64 * WI * WJ, 0, st>>>(g);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
 
 static void wg2_pick(int M, int Cout, int Cin, int jtot, int* bi, int* bj, int* ns, int* rows) {
     *bi = (Cout % 128 == 0) ? 128 : 64;
@@ -259,8 +237,8 @@ static void wg2_pick(int M, int Cout, int Cin, int jtot, int* bi, int* bj, int* 
     int want = (int)((target + tiles - 1) / tiles);
     int maxs = (M + 511) / 512;                              // at least 512 pixels (8 steps) per slice
     int n = want < 1 ? 1 : want; if (n > maxs) n = maxs; if (n < 1) n = 1; if (n > 512) n = 512;
-    int r = (M + n - 1) / n; r = (r + 63) / 64 * 64;
-    *ns = (M + r - 1) / r; *rows = r;
+    *rows = wgrad_rows_per_slice(M, n, 64);
+    *ns = (M + *rows - 1) / *rows;
 }
 
 // slabs needed (0: shape not handled by this kernel)
@@ -273,27 +251,18 @@ int wgrad_gemm2_slices(int M, int Cout, int Cin, int ntaps) {
 int wgrad_gemm2_run(const void* x, const void* dy, float* slabs, int N, int H, int W, int Cin, int Cout, int kh, int kw,
                     int stride, int pad, hipStream_t st) {
     Wg2Args g = {};
-    g.X = x; g.DY = dy; g.slabs = slabs;
-    g.N = N; g.Ha = H; g.Wa = W; g.Ca = Cin;
-    g.P = (H + 2 * pad - kh) / stride + 1; g.Q = (W + 2 * pad - kw) / stride + 1; g.Cout = Cout;
-    g.stride = stride; g.ntaps = kh * kw; g.Cin = Cin; g.jtot = kh * kw * Cin; g.M = N * g.P * g.Q;
+    wgrad_fill_conv(g, x, dy, slabs, N, H, W, Cin, Cout, kh, kw, stride, pad);
     if (!wgrad_gemm2_slices(g.M, Cout, Cin, g.ntaps)) return AB_ESHAPE;
-    for (int i = 0; i < kh; ++i) for (int j = 0; j < kw; ++j) { g.dh[i * kw + j] = (int8_t)(i - pad); g.dw[i * kw + j] = (int8_t)(j - pad); }
-    g.magic_pq = (1ull << 42) / (unsigned long long)(g.P * g.Q) + 1;
-    g.magic_q = (1ull << 42) / (unsigned long long)g.Q + 1;
     int bi, bj, ns, rows; wg2_pick(g.M, Cout, Cin, g.jtot, &bi, &bj, &ns, &rows);
-    g.rows_per_slice = rows;
-    g.xcd_map = wg2_xcd_map();
+    wg2_finish(g, nullptr, nullptr, rows);
     dim3 grid((Cout / bi) * (g.jtot / bj), ns);
     static const int w8 = getenv("AB_WG2_W8") ? atoi(getenv("AB_WG2_W8")) : 1;
-    if (bi == 128 && bj == 256) { if (w8) wgrad_gemm2_kernel<128, 256, false, 2, 4><<<grid, 512, 0, st>>>(g); else wgrad_gemm2_kernel<128, 256><<<grid, 256, 0, st>>>(g); }
-    else if (bi == 64 && bj == 256) wgrad_gemm2_kernel<64, 256><<<grid, 256, 0, st>>>(g);
-    else if (bi == 128 && bj == 128) { if (w8) wgrad_gemm2_kernel<128, 128, false, 2, 4><<<grid, 512, 0, st>>>(g); else wgrad_gemm2_kernel<128, 128><<<grid, 256, 0, st>>>(g); }
-    else if (bi == 128 && bj == 64) { if (w8) wgrad_gemm2_kernel<128, 64, false, 4, 2><<<grid, 512, 0, st>>>(g); else wgrad_gemm2_kernel<128, 64><<<grid, 256, 0, st>>>(g); }
-    else if (bi == 64 && bj == 128) { if (w8) wgrad_gemm2_kernel<64, 128, false, 2, 4><<<grid, 512, 0, st>>>(g); else wgrad_gemm2_kernel<64, 128><<<grid, 256, 0, st>>>(g); }
-    else wgrad_gemm2_kernel<64, 64><<<grid, 256, 0, st>>>(g);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    if (bi == 128 && bj == 256) return w8 ? wg2_launch<128, 256, false, 2, 4>(g, grid, st) : wg2_launch<128, 256>(g, grid, st);
+    if (bi == 64 && bj == 256) return wg2_launch<64, 256>(g, grid, st);
+    if (bi == 128 && bj == 128) return w8 ? wg2_launch<128, 128, false, 2, 4>(g, grid, st) : wg2_launch<128, 128>(g, grid, st);
+    if (bi == 128 && bj == 64) return w8 ? wg2_launch<128, 64, false, 4, 2>(g, grid, st) : wg2_launch<128, 64>(g, grid, st);
+    if (bi == 64 && bj == 128) return w8 ? wg2_launch<64, 128, false, 2, 4>(g, grid, st) : wg2_launch<64, 128>(g, grid, st);
+    return wg2_launch<64, 64>(g, grid, st);
 }
 
 // upper bound of the slab count for a (M, Cout, jtot) problem whatever its tap split (workspace sizing)
@@ -315,28 +284,25 @@ int wgrad_gemm2_stem_slices(int N, int H, int W, int Cout) {
     int n = (int)((256 + tiles - 1) / tiles);
     int maxs = (int)((M + 1023) / 1024);
     if (n > maxs) n = maxs; if (n < 1) n = 1;
-    int r = (int)((M + n - 1) / n); r = (r + 63) / 64 * 64;
+    const int r = wgrad_rows_per_slice((int)M, n, 64);
     return (int)((M + r - 1) / r);
 }
 
+// the stem problem in ns slices (dim3(Cout / 64, ns) workgroups); false: not handled
+static bool wg2_stem_args(Wg2Args& g, int& ns, const void* xpad_hi, const void* xpad_lo, const void* dy_hi, const void* dy_lo, float* slabs,
+                          int N, int H, int W, int Cout) {
+    ns = wgrad_gemm2_stem_slices(N, H, W, Cout);
+    if (!ns) return false;
+    wgrad_fill_stem(g, xpad_hi, dy_hi, slabs, N, H, W, Cout);
+    wg2_finish(g, xpad_lo, dy_lo, wgrad_rows_per_slice(g.M, ns, 64));
+    return true;
+}
+
 int wgrad_gemm2_stem_run(const void* xpad, const void* dy, float* slabs, int N, int H, int W, int Cout, hipStream_t st) {
-    int ns = wgrad_gemm2_stem_slices(N, H, W, Cout);
-    if (!ns) return AB_ESHAPE;
-    Wg2Args g = {};
-    g.X = xpad; g.DY = dy; g.slabs = slabs;
-    g.N = N; g.Ha = H + 6; g.Wa = W + 8; g.Ca = 4;
-    g.P = H / 2; g.Q = W / 2; g.Cout = Cout; g.stride = 2; g.ntaps = 8; g.Cin = 256; g.jtot = 256; g.M = N * g.P * g.Q;
-    g.magic_pq = (1ull << 42) / (unsigned long long)(g.P * g.Q) + 1;
-    g.magic_q = (1ull << 42) / (unsigned long long)g.Q + 1;
-    int r = (g.M + ns - 1) / ns; r = (r + 63) / 64 * 64;
-    g.rows_per_slice = r;
-    g.xcd_map = wg2_xcd_map();
-    dim3 grid(Cout / 64, ns);
+    Wg2Args g = {}; int ns;
+    if (!wg2_stem_args(g, ns, xpad, nullptr, dy, nullptr, slabs, N, H, W, Cout)) return AB_ESHAPE;
     static const int w8 = getenv("AB_WG2_W8") ? atoi(getenv("AB_WG2_W8")) : 1;
-    if (w8) wgrad_gemm2_kernel<64, 256, true, 2, 4><<<grid, 512, 0, st>>>(g);
-    else wgrad_gemm2_kernel<64, 256, true><<<grid, 256, 0, st>>>(g);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return w8 ? wg2_launch<64, 256, true, 2, 4>(g, dim3(Cout / 64, ns), st) : wg2_launch<64, 256, true>(g, dim3(Cout / 64, ns), st);
 }
 
 // ---- split-bf16 ("bf16x3") launches (x / dy as bf16 plane pairs).  Tiles up to 128 x 128: three ring stages of both
@@ -362,12 +328,12 @@ static void wg2x_pick(int M, int Cout, int Cin, int jtot, int* bi, int* bj, int*
     int n = 1; long best = -1;
     if (legacy) { n = (int)((256 + tiles - 1) / tiles); if (n > maxs) n = maxs; if (n < 1) n = 1; }
     else for (int c = 1; c <= maxs && tiles * c <= 2048; ++c) {
-        long r = ((M + c - 1) / c + 31) / 32 * 32, rounds = (tiles * c + 255) / 256;
+        long r = wgrad_rows_per_slice(M, c, 32), rounds = (tiles * c + 255) / 256;
         long cost = rounds * (r + WG_ROWS);
         if (best < 0 || cost * 100 < best * 98) { best = cost; n = c; }     // more slices only for 2 % or more
     }
-    int r = (M + n - 1) / n; r = (r + 31) / 32 * 32;
-    *ns = (M + r - 1) / r; *rows = r;
+    *rows = wgrad_rows_per_slice(M, n, 32);
+    *ns = (M + *rows - 1) / *rows;
 }
 
 int wgrad_gemm2_x3_slices(int M, int Cout, int Cin, int ntaps) {
@@ -379,46 +345,25 @@ int wgrad_gemm2_x3_slices(int M, int Cout, int Cin, int ntaps) {
 int wgrad_gemm2_x3_run(const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo, float* slabs, int N, int H, int W,
                        int Cin, int Cout, int kh, int kw, int stride, int pad, hipStream_t st) {
     Wg2Args g = {};
-    g.X = x_hi; g.X_lo = x_lo; g.DY = dy_hi; g.DY_lo = dy_lo; g.slabs = slabs;
-    g.N = N; g.Ha = H; g.Wa = W; g.Ca = Cin;
-    g.P = (H + 2 * pad - kh) / stride + 1; g.Q = (W + 2 * pad - kw) / stride + 1; g.Cout = Cout;
-    g.stride = stride; g.ntaps = kh * kw; g.Cin = Cin; g.jtot = kh * kw * Cin; g.M = N * g.P * g.Q;
+    wgrad_fill_conv(g, x_hi, dy_hi, slabs, N, H, W, Cin, Cout, kh, kw, stride, pad);
     if (!wgrad_gemm2_x3_slices(g.M, Cout, Cin, g.ntaps)) return AB_ESHAPE;
-    for (int i = 0; i < kh; ++i) for (int j = 0; j < kw; ++j) { g.dh[i * kw + j] = (int8_t)(i - pad); g.dw[i * kw + j] = (int8_t)(j - pad); }
-    g.magic_pq = (1ull << 42) / (unsigned long long)(g.P * g.Q) + 1;
-    g.magic_q = (1ull << 42) / (unsigned long long)g.Q + 1;
     int bi, bj, ns, rows; wg2x_pick(g.M, Cout, Cin, g.jtot, &bi, &bj, &ns, &rows);
-    g.rows_per_slice = rows;
-    g.xcd_map = wg2_xcd_map();
+    wg2_finish(g, x_lo, dy_lo, rows);
     dim3 grid(((Cout + bi - 1) / bi) * (g.jtot / bj), ns);
-    if (bi == 256 && bj == 256) wgrad_gemm2_kernel<256, 256, false, 4, 2, 1, 2><<<grid, 512, 0, st>>>(g);
-    else if (bi == 256 && bj == 128) wgrad_gemm2_kernel<256, 128, false, 4, 2, 1><<<grid, 512, 0, st>>>(g);
-    else if (bi == 128 && bj == 128 && wg2x_mode() == 1) wgrad_gemm2_kernel<128, 128, false, 2, 2, 1><<<grid, 256, 0, st>>>(g);
-    else if (bi == 128 && bj == 128) wgrad_gemm2_kernel<128, 128, false, 2, 4, 1><<<grid, 512, 0, st>>>(g);
-    else if (bi == 128 && bj == 64) wgrad_gemm2_kernel<128, 64, false, 4, 2, 1><<<grid, 512, 0, st>>>(g);
-    else if (bi == 64 && bj == 128) wgrad_gemm2_kernel<64, 128, false, 2, 4, 1><<<grid, 512, 0, st>>>(g);
-    else wgrad_gemm2_kernel<64, 64, false, 2, 2, 1><<<grid, 256, 0, st>>>(g);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    if (bi == 256 && bj == 256) return wg2_launch<256, 256, false, 4, 2, 1, 2>(g, grid, st);
+    if (bi == 256 && bj == 128) return wg2_launch<256, 128, false, 4, 2, 1>(g, grid, st);
+    if (bi == 128 && bj == 128 && wg2x_mode() == 1) return wg2_launch<128, 128, false, 2, 2, 1>(g, grid, st);
+    if (bi == 128 && bj == 128) return wg2_launch<128, 128, false, 2, 4, 1>(g, grid, st);
+    if (bi == 128 && bj == 64) return wg2_launch<128, 64, false, 4, 2, 1>(g, grid, st);
+    if (bi == 64 && bj == 128) return wg2_launch<64, 128, false, 2, 4, 1>(g, grid, st);
+    return wg2_launch<64, 64, false, 2, 2, 1>(g, grid, st);
 }
 
 // split-bf16 stem weight gradient (image and dy as plane pairs); slabs as wgrad_gemm2_stem_run
 int wgrad_gemm2_x3_stem_run(const void* xpad_hi, const void* xpad_lo, const void* dy_hi, const void* dy_lo, float* slabs, int N,
                             int H, int W, int Cout, hipStream_t st) {
-    int ns = wgrad_gemm2_stem_slices(N, H, W, Cout);
-    if (!ns) return AB_ESHAPE;
-    Wg2Args g = {};
-    g.X = xpad_hi; g.X_lo = xpad_lo; g.DY = dy_hi; g.DY_lo = dy_lo; g.slabs = slabs;
-    g.N = N; g.Ha = H + 6; g.Wa = W + 8; g.Ca = 4;
-    g.P = H / 2; g.Q = W / 2; g.Cout = Cout; g.stride = 2; g.ntaps = 8; g.Cin = 256; g.jtot = 256; g.M = N * g.P * g.Q;
-    g.magic_pq = (1ull << 42) / (unsigned long long)(g.P * g.Q) + 1;
-    g.magic_q = (1ull << 42) / (unsigned long long)g.Q + 1;
-    int r = (g.M + ns - 1) / ns; r = (r + 63) / 64 * 64;
-    g.rows_per_slice = r;
-    g.xcd_map = wg2_xcd_map();
-    dim3 grid(Cout / 64, ns);
-    if (!xpad_lo) wgrad_gemm2_kernel<64, 256, true, 2, 4, 2><<<grid, 512, 0, st>>>(g);      // the integer image plane (AB_DT_U8N)
-    else wgrad_gemm2_kernel<64, 256, true, 2, 4, 1><<<grid, 512, 0, st>>>(g);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    Wg2Args g = {}; int ns;
+    if (!wg2_stem_args(g, ns, xpad_hi, xpad_lo, dy_hi, dy_lo, slabs, N, H, W, Cout)) return AB_ESHAPE;
+    if (!xpad_lo) return wg2_launch<64, 256, true, 2, 4, 2>(g, dim3(Cout / 64, ns), st);      // the integer image plane (AB_DT_U8N)
+    return wg2_launch<64, 256, true, 2, 4, 1>(g, dim3(Cout / 64, ns), st);
 }

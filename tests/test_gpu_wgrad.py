@@ -27,6 +27,8 @@ Section 2: everything else on wgrad_gemm2_kernel / wgrad_kernel<float>, every ti
            the 16-, 32- and 64-row steps and a short last slice in every multi-slice case.
 Section 3: accumulate onto a slice of a larger flat buffer, and the workspace bound with a guarded 4 KiB tail, once per kernel family.
 Section 4: a split-bf16 launch of 2^21 or more output pixels through the deferred entry point (two half-batches over one workspace).
+Section 5: the grouped launch (ab_conv2d_wgrad_x3_group) on the split exact class, different operands per problem: the problem select, the
+           per-problem slab pointers and the ragged last slice of every problem; and G = 1 through it bit-equal to ab_conv2d_wgrad_x3.
 
 Observed on an MI355X.
   Exact class: all 105 (case, route) pairs of sections 1 and 2, the five accumulate cases and the six exact-size workspaces are bit-equal
@@ -40,6 +42,7 @@ Observed on an MI355X.
   of the 75.8 MB ab_conv2d_wgrad_workspace promises.
   Section 4: immediate vs the float64 sum of the halves 2.4e-4 (bound 5.7e-2).  Before the fix in conv_x3.hip / conv_wgrad.hip the deferred
   call differed from the immediate one by 3.8e+3 at max|dw| = 5.7e+3 (it kept out's contents plus the second half only).
+  Section 5: all seven problems of the three grouped cases and both groups of one are bit-equal to float64; nothing was found.
 """
 import ctypes
 import functools
@@ -159,11 +162,12 @@ def _seed(case, salt):
 
 
 @functools.lru_cache(maxsize=None)
-def _exact(case, cls):
-    """cls 'int': integers from {-3..3}, q = 1.  cls 'split': a + b * 2^-8, q = 2^-8, with the planes split() must return."""
+def _exact(case, cls, salt=1):
+    """cls 'int': integers from {-3..3}, q = 1.  cls 'split': a + b * 2^-8, q = 2^-8, with the planes split() must return.
+    salt: another draw of the same class (the problems of a grouped launch)."""
     N, H, W, Cin, Cout, k, s, p = case
     Ho, Wo, M = _geom(case)
-    g = torch.Generator().manual_seed(_seed(case, 1))
+    g = torch.Generator().manual_seed(_seed(case, salt))
     o = types.SimpleNamespace(cls=cls)
 
     def draw(shape):
@@ -403,3 +407,54 @@ def test_wgrad_x3_deferred_beyond_2p21_pixels():
     deferred = K.conv2d_wgrad_x3(x, dy, 1, 1, 1, 0, out=out, defer=pend)
     pend.flush()
     assert torch.equal(deferred, dw), f"deferred != immediate: max diff {float((deferred - dw).abs().max()):.3e} (max|dw| {scale:.3e})"
+
+
+# ---------------------------------------------------------------- 5. the grouped launch of wgrad3x3_kernel
+# (N, H, W, Cin, Cout), G, then (nbands, bands_per_slice, slices PER PROBLEM): wgrad3x3_x3_group_slices aims at 256 / (tiles * G) slices, which
+# the two-bands-per-slice clamp (nbands / 2) cuts to the single launch's count at these sizes
+GROUP_CASES = [((7, 8, 8, 64, 64), 2, (7, 3, 3)), ((7, 8, 8, 64, 64), 3, (7, 3, 3)),      # 3 + 3 + 1 bands per problem
+               ((5, 8, 8, 128, 192), 2, (5, 3, 2))]                                         # 2 x 3 tiles
+
+
+@pytest.mark.parametrize("shape,G,expect", [pytest.param(s, G, e, id=f"G{G}-" + "x".join(map(str, s))) for s, G, e in GROUP_CASES])
+def test_wgrad3x3_group_exact(shape, G, expect):
+    """Every problem of a grouped launch bit-equal to float64 on its own operands, the slot behind the last problem untouched, a second call
+    bit-equal to the first."""
+    from artiboost_amd import _lib as L
+    from artiboost_amd import kernels as K
+    case = shape + (3, 1, 1)
+    N, H, W, Cin, Cout = shape
+    ns = _expected_slices(case, X3, expect)
+    assert _geom(case)[2] <= SPLIT_MAX_M
+    nbytes = L.lib().ab_conv2d_wgrad_x3_group_workspace(L.i(G), L.i(N), L.i(H), L.i(W), L.i(Cin), L.i(Cout))
+    assert nbytes == G * ns * Cout * 9 * Cin * 4, f"route: workspace of {nbytes} bytes, the table has {G} x {ns} slabs"
+    flat = torch.full((G + 1, Cout, 3, 3, Cin), 7.0, device="cuda")
+    es = [_exact(case, "split", salt=3 + i) for i in range(G)]
+    assert not torch.equal(es[0].x, es[1].x) and not torch.equal(es[0].dy, es[1].dy)
+    items = []
+    for i, e in enumerate(es):
+        assert e.mass <= 2.0 ** 22 * e.q, f"exactness condition: sum |dy||x| = {e.mass:g} > 2^22 q"
+        xd, dd = _device_operands(X3, e.x, e.dy, (e.xh, e.xl, e.dh, e.dl))
+        items.append((xd, dd, flat[i]))
+    K.conv2d_wgrad_x3_group(items)
+    for i, e in enumerate(es):
+        _assert_exact(f"group of {G}, problem {i}, {case}", flat[i], e.ref, e.q)
+    assert bool((flat[G] == 7.0).all()), "wrote behind the last problem"
+    again = torch.full_like(flat, 7.0)
+    K.conv2d_wgrad_x3_group([(a, b, again[i]) for i, (a, b, _) in enumerate(items)])
+    assert torch.equal(again, flat), "a second grouped call differs"
+
+
+@pytest.mark.parametrize("shape", [(3, 2, 64, 64, 64), (7, 8, 16, 64, 128)], ids=lambda s: "x".join(map(str, s)))
+def test_wgrad3x3_group_of_one_equals_the_single_launch(shape):
+    """G = 1 through ab_conv2d_wgrad_x3_group gives ab_conv2d_wgrad_x3's bits (and float64's) on the same operands."""
+    from artiboost_amd import kernels as K
+    case = shape + (3, 1, 1)
+    e = _exact(case, "split")
+    assert e.mass <= 2.0 ** 22 * e.q, f"exactness condition: sum |dy||x| = {e.mass:g} > 2^22 q"
+    xd, dd = _device_operands(X3, e.x, e.dy, (e.xh, e.xl, e.dh, e.dl))
+    single = _call(X3, xd, dd, case)
+    out = torch.full_like(single, 7.0)
+    K.conv2d_wgrad_x3_group([(xd, dd, out)])
+    _assert_exact(f"group of one {case}", out, e.ref, e.q)
+    assert torch.equal(out, single), "a group of one differs from the single launch"
