@@ -12,10 +12,8 @@
 // addresses rebuilt each time.  Here -- the loop of conv3x3.hip with four taps -- a (sub-)patch of 17 x 18 pixels is DMA'd once per
 // 32-channel chunk and serves its four taps by shifting the fragment address (a quarter of the activation fill), only the weights stream
 // per tap (ring of four stages, two steps ahead, counted vmcnt + raw s_barrier), and every address in the K loop is a lane constant plus
-// an immediate.  LDS image, swizzles and the fp32 epilogue are those of conv3x3.hip (TW = 16, patch pitch 18).
+// an immediate.  LDS image, split-bf16 step and fp32 epilogue are conv_tile.h's (TW = 16, patch pitch 18).
 #include "conv3x3.h"
-
-static __device__ uint4 c22_zero_page[2];
 
 struct C22Unit { int oy0, ox0, sy, sx; int koff[4]; };      // patch origin (base units), input parity (stride-2 input), K offset of tap (t >> 1, t & 1)
 struct C22Args {
@@ -32,25 +30,33 @@ struct C22Args {
     const float* ep_scale; const float* ep_shift; int ep_relu; void* out_hi; void* out_lo;
 };
 
-// G8 = false: base grid 16 x 16, a tile is one image (BM = 256), patch 17 rows x 18 (17 used), swizzle key (px >> 1) & 7.
+// Tile geometry and LDS budget, read by the kernel and by c22_launch.
+// G8 = false: base grid 16 x 16, a tile is one image (BM = 256), patch 17 rows x 18 (17 used), 16-wide swizzle key.
 // G8 = true : base grid 8 x 8, a tile is NI = BM / 64 consecutive images, each with its own 9 x 9 patch (pitch 9: consecutive rows alternate
-//             the 128-byte half), swizzle key ((px >> 1) & 3) | ((py & 1) << 2) -- conv3x3.hip's TW = 8 layout: a ds_read_b128 lane group
-//             spans four patch rows there.
+//             the 128-byte half), 8-wide swizzle key: a ds_read_b128 lane group spans four patch rows there.
+template <int BM, int BN, bool G8> struct C22Geom {
+    static constexpr int TW = G8 ? 8 : 16, TH = G8 ? 8 : 16, NI = BM / (TW * TH), PW = G8 ? 9 : 18, PH = G8 ? 9 : 17, IPIX = PH * PW;
+    static_assert(BM == NI * TW * TH && (G8 || NI == 1), "tile = whole images");
+    static constexpr int WM = 4, WN = 2, NW = 8;
+    using L = PatchTileLds<NI * IPIX, NW, BM, BN>;
+    static constexpr int NRING = 4, NPATCH = 2, PATCH0 = NRING * L::BBYTES;      // LDS: [weight ring x4][patch 0][patch 1]
+    static constexpr int LDS = L::x3_lds(NRING, NPATCH);
+    static_assert(LDS <= 160 * 1024, "K-loop image, staging tile and partials fit a CU's 160 KB of LDS");
+};
+
 template <int BM, int BN, int NSUB, bool G8>
 __global__ __launch_bounds__(512) void conv2x2_kernel(C22Args g) {
-    constexpr int TW = G8 ? 8 : 16, TH = G8 ? 8 : 16, NI = BM / (TW * TH), PW = G8 ? 9 : 18, PH = G8 ? 9 : 17, IPIX = PH * PW, NPIX = NI * IPIX;
-    static_assert(BM == NI * TW * TH && (G8 || NI == 1), "tile = whole images");
-    constexpr int WM = 4, WN = 2, NW = 8, NT = 512;
-    constexpr int PI = (NPIX + 7) / 8, LP = (PI + NW - 1) / NW, PATCH_BYTES = LP * NW * 1024;
-    constexpr int IB = BN / 8, LB = IB / NW, BBYTES = BN * 128;
+    using G = C22Geom<BM, BN, G8>;
+    constexpr int TW = G::TW, TH = G::TH, NI = G::NI, PW = G::PW, IPIX = G::IPIX, NPIX = G::L::NPIX;
+    constexpr int WM = G::WM, WN = G::WN, NW = G::NW, NT = G::L::NT;
+    constexpr int PI = G::L::PI, LP = G::L::LP, PATCH_BYTES = G::L::PATCH_BYTES;
+    constexpr int IB = BN / 8, LB = IB / NW, BBYTES = G::L::BBYTES;
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-    constexpr int PATCH0 = 4 * BBYTES;                        // LDS: [weight ring x4][patch 0][patch 1]
+    constexpr int PATCH0 = G::PATCH0;
     extern __shared__ __attribute__((aligned(256))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wave_m = wave / WN, wave_n = wave % WN;
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, within = bid >> 3;
-    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + within;
+    const int logical = xcd_logical(blockIdx.x, gridDim.x);
     const int tiles_n = g.Cn / BN;
     const int tile_sp = logical / tiles_n, tile_n = logical - tile_sp * tiles_n;      // tile_sp = image group * nclass + class: the BatchNorm partial row
     const int img = (tile_sp / g.nclass) * NI, cls = tile_sp % g.nclass;                 // first image of the tile
@@ -58,7 +64,7 @@ __global__ __launch_bounds__(512) void conv2x2_kernel(C22Args g) {
     const bf16_t* __restrict__ X = (const bf16_t*)g.X;
     const bf16_t* __restrict__ Xlo = (const bf16_t*)g.X_lo;
     const bf16_t* __restrict__ Wt = (const bf16_t*)g.Wt;
-    const bf16_t* zp = (const bf16_t*)c22_zero_page;
+    const bf16_t* zp = (const bf16_t*)zero_page;
     const int nchunks = g.C / 32;
     const unsigned lds0 = lds_addr_of(smem);
 
@@ -81,26 +87,24 @@ __global__ __launch_bounds__(512) void conv2x2_kernel(C22Args g) {
         const int rem = pp - p_il[j] * IPIX;
         p_py[j] = rem / PW; p_px[j] = rem - p_py[j] * PW;
         p_in[j] = ii < PI && pp < NPIX && p_px[j] < TW + 1;
-        const int c = (lane & 7) ^ (G8 ? (((p_px[j] >> 1) & 3) | ((p_py[j] & 1) << 2)) : ((p_px[j] >> 1) & 7));
-        p_lo[j] = (c & 4) != 0; p_coff[j] = (unsigned)((c & 3) * 8);
+        const int c = fill_chunk(lane, patch_key<TW>(p_py[j], p_px[j]));
+        p_lo[j] = chunk_lo(c); p_coff[j] = (unsigned)chunk_elem(c);
     }
     unsigned b_voff[LB];
 #pragma unroll
     for (int j = 0; j < LB; ++j) {
         const int ii = wave * LB + j, r = ii * 8 + (lane >> 3);
-        int c = (lane & 7) ^ ((r >> 1) & 7);
-        const unsigned pl = (c & 4) ? g.wlo_delta : 0u;
-        c &= 3;
-        b_voff[j] = (unsigned)(((long)(n0 + r) * g.ktot + c * 8) * 2) + pl;
+        const int c = fill_chunk(lane, wrow_key(r));
+        b_voff[j] = (unsigned)(((long)(n0 + r) * g.ktot + chunk_elem(c)) * 2) + (chunk_lo(c) ? g.wlo_delta : 0u);
     }
     // ---- per-lane fragment addresses
     const int l32 = lane & 31, fhalf = lane >> 5;
-    unsigned b_rel[TN][4], a_rel[TM][2][4];
+    unsigned b_rel[TN][4], a_rel[2][TM][4];            // [weight tile][k-slice]; [tap column][pixel tile][k-slice]
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int r = (wave_n * TN + j) * 32 + l32;
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) b_rel[j][kk] = lds0 + r * 128 + (((kk * 2 + fhalf) ^ ((r >> 1) & 7)) << 4);
+        for (int kk = 0; kk < 4; ++kk) b_rel[j][kk] = lds0 + frag_off(r, kk * 2 + fhalf, wrow_key(r));
     }
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -109,9 +113,8 @@ __global__ __launch_bounds__(512) void conv2x2_kernel(C22Args g) {
         for (int d = 0; d < 2; ++d) {
             const int px = ox + d;
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk)      // (G8: the patch row's bit of the key is flipped below for the second tap row)
-                a_rel[i][d][kk] = lds0 + PATCH0 + (il * IPIX + oy * PW + px) * 128 +
-                                  (((kk * 2 + fhalf) ^ (G8 ? (((px >> 1) & 3) | ((oy & 1) << 2)) : ((px >> 1) & 7))) << 4);
+            for (int kk = 0; kk < 4; ++kk)      // (the key of patch row oy: the second tap row is tap_row_flip's business)
+                a_rel[d][i][kk] = lds0 + PATCH0 + frag_off(il * IPIX + oy * PW + px, kk * 2 + fhalf, patch_key<TW>(oy, px));
         }
     }
 
@@ -134,19 +137,12 @@ __global__ __launch_bounds__(512) void conv2x2_kernel(C22Args g) {
 #pragma unroll
         for (int j = 0; j < LB; ++j) {
             const int ii = wave * LB + j;
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(b_voff[j]), "s"(base), "s"(__builtin_amdgcn_readfirstlane(lds0 + slot * BBYTES + ii * 1024)) : "memory");
+            glds16_s(b_voff[j], base, __builtin_amdgcn_readfirstlane(lds0 + slot * BBYTES + ii * 1024));
         }
     };
 
     f32x16 acc[TM][TN], accx[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; accx[i][j][r] = 0.f; }
+    zero_acc(acc); zero_acc(accx);
 
     // ---- software pipeline (conv3x3.hip's, with four taps per patch): P(0) B(0) B(1) | per step after its barrier: B(step + 2), and at tap 0
     // of super-chunk sc also P(sc + 1).  All loads are inline asm: the waits below are exact.
@@ -176,58 +172,20 @@ __global__ __launch_bounds__(512) void conv2x2_kernel(C22Args g) {
                 if (t == 0 && more) issue_patch(sc + 1, (sc + 1) & 1);
                 const int dh = t >> 1, dw = t & 1;
                 const unsigned aoff = pbase + dh * PW * 128;
-                const unsigned aflip = (G8 && dh) ? 64u : 0u;      // the (py & 1) bit of the G8 key: patch row = oy + dh (bases are 128-byte aligned)
                 u32x4 fa[4][TM], fb[4][TN];
-#pragma unroll
-                for (int k2 = 0; k2 < 2; ++k2) {
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-#pragma unroll
-                        for (int i = 0; i < TM; ++i) fa[k2 + 2 * h][i] = *(const lds_u32x4*)((a_rel[i][dw][k2 + 2 * h] ^ aflip) + aoff);
-#pragma unroll
-                        for (int j = 0; j < TN; ++j) fb[k2 + 2 * h][j] = *(const lds_u32x4*)(b_rel[j][k2 + 2 * h] + t * BBYTES);
-                    }
-                }
-#pragma unroll
-                for (int k2 = 0; k2 < 2; ++k2) {
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j) {
-                            const bf16x8 bh = __builtin_bit_cast(bf16x8, fb[k2][j]), bl = __builtin_bit_cast(bf16x8, fb[k2 + 2][j]);
-                            const bf16x8 ah = __builtin_bit_cast(bf16x8, fa[k2][i]), al = __builtin_bit_cast(bf16x8, fa[k2 + 2][i]);
-                            // weights as the first operand: the accumulator is the TRANSPOSED tile (a lane owns one pixel, see the epilogue)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh, ah, acc[i][j], 0, 0, 0);
-                            accx[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh, al, accx[i][j], 0, 0, 0);
-                            accx[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl, ah, accx[i][j], 0, 0, 0);
-                        }
-                }
+                x3_read_frags(fa, fb, a_rel[dw], tap_row_flip<TW>(dh), aoff, b_rel, t * BBYTES);
+                x3_mfma_step(acc, accx, fa, fb);
             }
         }
     }
     __syncthreads();
 
-    // ---- fp32 epilogue (conv3x3.hip's): a lane owns ONE pixel and per register quad four consecutive channels = one 16-byte LDS store into
-    // the pixel-major staging tile; rows leave as 16-byte vectors to their (strided) output pixels; BatchNorm partials of the tile as stored.
-    constexpr int SPF = BN * 4 + 16;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int row = (wave_m * TM + i) * 32 + l32;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const int cl = (wave_n * TN + j) * 32 + 8 * q4 + 4 * fhalf;
-                float4 w;
-                w.x = acc[i][j][q4 * 4] + accx[i][j][q4 * 4]; w.y = acc[i][j][q4 * 4 + 1] + accx[i][j][q4 * 4 + 1];
-                w.z = acc[i][j][q4 * 4 + 2] + accx[i][j][q4 * 4 + 2]; w.w = acc[i][j][q4 * 4 + 3] + accx[i][j][q4 * 4 + 3];
-                *(float4*)(smem + row * SPF + cl * 4) = w;
-            }
-        }
-    }
+    // ---- fp32 epilogue (conv_tile.h): staging tile; rows leave as 16-byte vectors to their (strided) output pixels; BatchNorm partials of
+    // the tile as stored.
+    constexpr int SPF = stage_pitch_f32<BN>();
+    stage_store_f32<BN>(smem, acc, accx, wave_m, wave_n, lane);
     __syncthreads();
     constexpr int CPRF = BN / 4;
-    static_assert(NT % CPRF == 0, "a thread keeps one channel group over all its rows");
     const int coy = g.cls_oy[cls], cox = g.cls_ox[cls];
     float fs[4] = {0.f, 0.f, 0.f, 0.f}, fq[4] = {0.f, 0.f, 0.f, 0.f};
     for (int id = tid; id < BM * CPRF; id += NT) {
@@ -236,53 +194,20 @@ __global__ __launch_bounds__(512) void conv2x2_kernel(C22Args g) {
         const int yy = (rr / TW) * g.out_stride + coy, xx = (rr % TW) * g.out_stride + cox, col = n0 + c4 * 4;
         float4 v = *(const float4*)(smem + row * SPF + c4 * 16);
         const long o = (((long)(img + il) * g.Ho + yy) * g.Wo + xx) * g.Cn + col;
-        if (g.ep_scale) {
-            const float4 sc = *(const float4*)(g.ep_scale + col), sh = *(const float4*)(g.ep_shift + col);
-            v.x = v.x * sc.x + sh.x; v.y = v.y * sc.y + sh.y; v.z = v.z * sc.z + sh.z; v.w = v.w * sc.w + sh.w;
-            if (g.ep_relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-        }
-        if (g.out_hi) {
-            uint2 h, l;
-            h.x = pack_bf16x2(v.x, v.y); h.y = pack_bf16x2(v.z, v.w);
-            l.x = pack_bf16x2(v.x - __uint_as_float(h.x << 16), v.y - __uint_as_float(h.x & 0xffff0000u));
-            l.y = pack_bf16x2(v.z - __uint_as_float(h.y << 16), v.w - __uint_as_float(h.y & 0xffff0000u));
-            *(uint2*)((bf16_t*)g.out_hi + o) = h; *(uint2*)((bf16_t*)g.out_lo + o) = l;
-        } else *(float4*)(g.Out + o) = v;
-        fs[0] += v.x; fq[0] += v.x * v.x; fs[1] += v.y; fq[1] += v.y * v.y;
-        fs[2] += v.z; fq[2] += v.z * v.z; fs[3] += v.w; fq[3] += v.w * v.w;
+        if (g.ep_scale) affine_relu4(v, g.ep_scale + col, g.ep_shift + col, g.ep_relu);
+        if (g.out_hi) store_planes4(g.out_hi, g.out_lo, o, v);
+        else *(float4*)(g.Out + o) = v;
+        stat4(fs, fq, v);
     }
     __syncthreads();
-    if (g.stats) {
-        float* sp = (float*)smem;                          // [NT / CPRF][BN][2], over the consumed staging tile
-        const int rg = tid / CPRF, cb = (tid % CPRF) * 4;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { sp[(rg * BN + cb + k) * 2] = fs[k]; sp[(rg * BN + cb + k) * 2 + 1] = fq[k]; }
-        __syncthreads();
-        for (int c = tid; c < BN; c += NT) {
-            float s2 = 0.f, q2 = 0.f;
-            for (int r = 0; r < NT / CPRF; ++r) { s2 += sp[(r * BN + c) * 2]; q2 += sp[(r * BN + c) * 2 + 1]; }
-            g.stats[((long)tile_sp * g.Cn + n0 + c) * 2] = s2;
-            g.stats[((long)tile_sp * g.Cn + n0 + c) * 2 + 1] = q2;
-        }
-    }
+    if (g.stats) reduce_partial_rows<4, BN, NT>((float*)smem, fs, fq, g.stats, tile_sp, g.Cn, n0);      // over the consumed staging tile
 }
 
 template <int BM, int BN, int NSUB, bool G8>
 static int c22_launch(C22Args& g, hipStream_t st) {
-    constexpr int NI = BM / (G8 ? 64 : 256), NPIX = NI * (G8 ? 81 : 17 * 18), LP = ((NPIX + 7) / 8 + 7) / 8;
-    const size_t ring = (size_t)4 * BN * 128 + 2 * LP * 8 * 1024, stage = (size_t)BM * (BN * 4 + 16), part = (size_t)(512 / (BN / 4)) * BN * 8;
-    size_t lds = ring > stage ? ring : stage;
-    if (part > lds) lds = part;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv2x2_kernel<BM, BN, NSUB, G8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    const int blocks = (g.N / NI) * g.nclass * (g.Cn / BN);
-    conv2x2_kernel<BM, BN, NSUB, G8><<<blocks, 512, lds, st>>>(g);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    using G = C22Geom<BM, BN, G8>;
+    const int blocks = (g.N / G::NI) * g.nclass * (g.Cn / BN);
+    return launch_dyn_lds<conv2x2_kernel<BM, BN, NSUB, G8>>(g, blocks, G::L::NT, G::LDS, G::LDS, st);
 }
 
 static int c22_bn(int Cn) {

@@ -1,9 +1,6 @@
 // Shared by conv3x3.hip (LDS weight ring) and conv3x3r.hip (weights resident in registers).
 #pragma once
-#include "conv_common.h"
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
+#include "conv_tile.h"
 
 struct Conv3Args {
     const void* X; const void* Wt; void* Out; const void* addend; float* stats;

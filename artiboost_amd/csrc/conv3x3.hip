@@ -6,23 +6,34 @@
 // 128 bytes per pixel) and serves all 9 taps from it by shifting the fragment read address; only the weights stream
 // per tap (3-deep LDS ring, counted vmcnt, raw s_barrier).  Activation traffic drops ~9x and the bytes loaded per
 // FLOP are set by the weight stream alone: BN x 128 B per (BM x BN x 64) MACs.
-//
-// LDS image (both operands are lane-linear global_load_lds fills, so the swizzle sits on the source address):
-//   patch : pixel pp = py*(TW+2) + px at byte pp*128, logical chunk c stored at slot c ^ ((px >> 1) & 7)
-//           (TW = 8, where a ds_read_b128 lane group spans four patch rows: c ^ (((px >> 1) & 3) | ((py & 1) << 2)), row pitch TW + 3 --
-//           with the px-only mask every fragment read of that tile was a 2-way bank conflict: SQ_LDS_BANK_CONFLICT 0.33 of the LDS cycles)
-//   weight: row r (output channel) at byte r*128, logical chunk c at slot c ^ ((r >> 1) & 7)
-// Both are conflict-free for the 16-lane groups of ds_read_b128 (for TW = 16 two half-rows complement each other).
+// The LDS image of both operands (swizzle keys, fill side, fragment side) is the format conv_tile.h documents.  This kernel spells its
+// address blocks, accumulator zeroing, split-bf16 step and fp32 epilogue out in place: through conv_tile.h's helpers -- zero_acc and
+// reduce_partial_rows<4> are enough -- the compiler schedules the first and last K steps differently, and the X3 = 1 / 2 forms measured
+// 0.4 - 1.4 % slower (profiles/conv_bodies.md).  As written every instantiation compiles to the code it had before conv_tile.h existed.
 #include "conv3x3.h"
 
-static __device__ uint4 c3_zero_page[2];     // zero-initialised: source of every out-of-image chunk
-
-// saddr-form LDS-DMA: per-lane 32-bit byte offset + wave-uniform 64-bit base (no VALU 64-bit address arithmetic)
-__device__ __forceinline__ void glds16_s(unsigned voff, const void* sbase, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_byte_addr) : "memory");
-}
+// Tile geometry and LDS budget of one instantiation, read by the kernel and by c3_launch.
+template <int BM, int TW, int BN, int WM, int WN, int X3> struct C3Geom {
+    // STACK (BM = 128 on TW = 8): the tile is TWO whole 8 x 8 images, handed over by the launch as one 16-row image (the same bytes); the
+    // patch holds each image with its own zero halo rows (2 x 10 rows), so no tap of one image reads the other.  Layer 4: a 128-pixel x
+    // 64-channel tile streams half the weight bytes per product of the 64 x 128 one at the same 256 workgroups (the launch waits on its
+    // L2 -> LDS weight stream: SQ_WAIT_ANY 0.61 of the wave cycles, tools/pmc_conv.sh).
+    static constexpr bool STACK = (TW == 8 && BM == 128);
+    // patch row pitch: TW + 2, or TW + 3 for TW = 8 so that consecutive patch rows alternate LDS half (pixel parity) --
+    // a 16-lane fragment read then spans two image rows with the same px set and would otherwise hit the same banks
+    static constexpr int NW = WM * WN, TH = BM / TW, PW = (TW == 8) ? TW + 3 : TW + 2, PH = STACK ? TH + 4 : TH + 2;
+    using L = PatchTileLds<PH * PW, NW, BM, BN>;
+    static constexpr int NRING = 3;
+    static constexpr int PATCH0 = NRING * L::BBYTES;              // LDS: [weight ring x3][patch 0][patch 1][stats]
+    // bf16 epilogue: staging tile of BN * 2 + 16 byte rows (+ 16 spreads rows over banks), then the partials [NT / (BN / 8)][BN][2];
+    // split-bf16: the fp32 staging tile, whose space the partials reuse
+    static constexpr int SPITCH = BN * 2 + 16, PART_OFF = (BM * SPITCH + 15) / 16 * 16, PART_BF16 = (L::NT / (BN / 8)) * BN * 8;
+    static constexpr int EPILOGUE = X3 ? (L::STAGE_F32 > L::PART_F32 ? L::STAGE_F32 : L::PART_F32) : PART_OFF + PART_BF16;
+    static constexpr size_t lds(int nchunks) {                   // one patch buffer for a single-chunk K loop, else two
+        const size_t loop = (size_t)(nchunks > 1 ? 2 : 1) * L::PATCH_BYTES + NRING * L::BBYTES + WM * BN * 8;
+        return loop > (size_t)EPILOGUE ? loop : (size_t)EPILOGUE;
+    }
+};
 
 // X3 = 1: split-bf16 operands ("bf16x3").  Every fp32 value v is held as two bf16 planes hi = bf16(v), lo = bf16(v - hi)
 // (v = hi + lo to 2^-17 relative) and the product is hi*hi + hi*lo + lo*hi on the bf16 MFMA with fp32 accumulation:
@@ -49,31 +60,19 @@ __global__ __launch_bounds__(64 * WM * WN) void conv3x3_kernel(Conv3Args g) {
     // whatever its queue depth, and a CU's fill rate scales with the number of waves issuing loads (4 waves 10 TB/s
     // chip-wide, 8 waves 20, 16 waves 30) -- so the same tile is worked by 8 waves where the fill is the limit.
     constexpr int NW = WM * WN, NT = 64 * NW;
-    // patch row pitch: TW + 2, or TW + 3 for TW = 8 so that consecutive patch rows alternate LDS half (pixel parity) --
-    // a 16-lane fragment read then spans two image rows with the same px set and would otherwise hit the same banks
-    // STACK (BM = 128 on TW = 8): the tile is TWO whole 8 x 8 images, handed over by the launch as one 16-row image (the same bytes); the
-    // patch holds each image with its own zero halo rows (2 x 10 rows), so no tap of one image reads the other.  Layer 4: a 128-pixel x
-    // 64-channel tile streams half the weight bytes per product of the 64 x 128 one at the same 256 workgroups (the launch waits on its
-    // L2 -> LDS weight stream: SQ_WAIT_ANY 0.61 of the wave cycles, tools/pmc_conv.sh).
-    constexpr bool STACK = (TW == 8 && BM == 128);
-    constexpr int TH = BM / TW, PW = (TW == 8) ? TW + 3 : TW + 2, PH = STACK ? TH + 4 : TH + 2;
-    constexpr int NPIX = PH * PW;
-    constexpr int PI = (NPIX + 7) / 8;                 // 1-KiB instructions per patch
-    constexpr int LP = (PI + NW - 1) / NW;             // per wave
-    constexpr int PATCH_BYTES = LP * NW * 1024;        // every wave issues exactly LP fills; the tail past NPIX is slack
+    using G = C3Geom<BM, TW, BN, WM, WN, X3>;
+    constexpr bool STACK = G::STACK;
+    constexpr int TH = G::TH, PW = G::PW, NPIX = G::L::NPIX, PI = G::L::PI, LP = G::L::LP, PATCH_BYTES = G::L::PATCH_BYTES;
     constexpr int IB = BN / 8, LB = IB / NW;           // weight-tile instructions: total / per wave
     static_assert(IB % NW == 0, "weight tile rows must split evenly over the waves");
-    constexpr int BBYTES = BN * 128;
+    constexpr int BBYTES = G::L::BBYTES;
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-    constexpr int NRING = 3;
-    constexpr int PATCH0 = NRING * BBYTES;             // LDS: [weight ring x3][patch 0][patch 1][stats]
+    constexpr int PATCH0 = G::PATCH0;
     extern __shared__ __attribute__((aligned(256))) unsigned char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wave_m = wave / WN, wave_n = wave % WN;
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, within = bid >> 3;
-    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + within;
+    const int logical = xcd_logical(blockIdx.x, gridDim.x);
     const int tiles_n = (g.Cn + BN - 1) / BN;
     const int tile_sp = logical / tiles_n, tile_n = logical - tile_sp * tiles_n;
     const int tpi = g.tiles_x * g.tiles_y;
@@ -83,7 +82,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv3x3_kernel(Conv3Args g) {
     const bf16_t* __restrict__ X = (const bf16_t*)g.X;
     const bf16_t* __restrict__ Xlo = (const bf16_t*)g.X_lo;
     const bf16_t* __restrict__ Wt = (const bf16_t*)g.Wt;
-    const bf16_t* zp = (const bf16_t*)c3_zero_page;
+    const bf16_t* zp = (const bf16_t*)zero_page;
     const int nchunks = g.C / CK;
     const unsigned lds0 = lds_addr_of(smem);
 
@@ -298,7 +297,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv3x3_kernel(Conv3Args g) {
         // consecutive channels = one 16-byte LDS store into the pixel-major fp32 staging tile; rows leave as 16-byte vectors.
         float* __restrict__ OutF = (float*)g.Out;
         const float* __restrict__ AddF = (const float*)g.addend;
-        constexpr int SPF = BN * 4 + 16;
+        constexpr int SPF = stage_pitch_f32<BN>();
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int row = (wave_m * TM + i) * 32 + l32;
@@ -355,11 +354,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv3x3_kernel(Conv3Args g) {
                         for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
                     }
                     uint32_t h[4], l[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        h[k] = pack_bf16x2(v[2 * k], v[2 * k + 1]);
-                        l[k] = pack_bf16x2(v[2 * k] - __uint_as_float(h[k] << 16), v[2 * k + 1] - __uint_as_float(h[k] & 0xffff0000u));
-                    }
+                    split_planes<8>(v, h, l);
                     *(uint4*)(OutHi + o) = make_uint4(h[0], h[1], h[2], h[3]);
                     *(uint4*)(OutLo + o) = make_uint4(l[0], l[1], l[2], l[3]);
                     if (g.OutF) {
@@ -417,7 +412,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv3x3_kernel(Conv3Args g) {
         }
         __syncthreads();
         float* part_out = BNR ? g.bn_part : g.stats;
-        if (part_out) {
+        if (part_out) {      // (reduce_partial_rows' text in place: through the call the X3 = 2 forms' last step and epilogue were scheduled differently)
             float* sp = (float*)smem;                          // [NT / CPRF][BN][2], over the consumed staging tile
             const int rg = tid / CPRF, cb = (tid % CPRF) * 4;
 #pragma unroll
@@ -442,7 +437,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv3x3_kernel(Conv3Args g) {
     // which HBM sees whole 16-byte vectors / full lines.
     bf16_t* __restrict__ Out = (bf16_t*)g.Out;
     const bf16_t* __restrict__ Add = (const bf16_t*)g.addend;
-    constexpr int SPITCH = BN * 2 + 16;                   // staging row pitch (bytes): +16 spreads rows over banks
+    constexpr int SPITCH = G::SPITCH;
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         const int row = (wave_m * TM + i) * 32 + l32;
@@ -529,37 +524,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv3x3_kernel(Conv3Args g) {
     __syncthreads();
     if (BnY || g.stats) {
         float* part_out = BnY ? g.bn_part : g.stats;
-        constexpr int PART_OFF = (BM * SPITCH + 15) / 16 * 16;
-        float* sp = (float*)(smem + PART_OFF);             // [NT / CPR][BN][2]
-        const int rg = tid / CPR, cb = (tid % CPR) * 8;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { sp[(rg * BN + cb + k) * 2] = bs[k]; sp[(rg * BN + cb + k) * 2 + 1] = bq[k]; }
-        __syncthreads();
-        for (int c = tid; c < BN; c += NT) {
-            int col = n0 + c;
-            if (col < g.Cn) {
-                float s = 0.f, q = 0.f;
-                for (int r = 0; r < NT / CPR; ++r) { s += sp[(r * BN + c) * 2]; q += sp[(r * BN + c) * 2 + 1]; }
-                part_out[((long)tile_sp * g.Cn + col) * 2] = s;
-                part_out[((long)tile_sp * g.Cn + col) * 2 + 1] = q;
-            }
-        }
+        reduce_partial_rows<8, BN, NT>((float*)(smem + G::PART_OFF), bs, bq, part_out, tile_sp, g.Cn, n0);      // behind the staging tile
     }
-}
-
-template <int BM, int TW, int BN, int WM, int WN, int X3 = 0>
-static size_t c3_lds(int nchunks) {
-    constexpr int NW = WM * WN;
-    constexpr int TH = BM / TW, NPIX = ((TW == 8 && BM == 128) ? TH + 4 : TH + 2) * ((TW == 8) ? TW + 3 : TW + 2), PI = (NPIX + 7) / 8, LP = (PI + NW - 1) / NW;
-    size_t need = (size_t)(nchunks > 1 ? 2 : 1) * LP * NW * 1024 + 3 * BN * 128 + WM * BN * 8;
-    size_t stage = ((size_t)BM * (BN * 2 + 16) + 15) / 16 * 16;      // epilogue staging tile
-    stage += (size_t)(64 * NW / (BN / 8)) * BN * 8;                    // + fused BN-backward partials [NT/CPR][BN][2]
-    if (X3) {                                                          // fp32 staging tile; the partials reuse it
-        stage = (size_t)BM * (BN * 4 + 16);
-        const size_t part = (size_t)(64 * NW / (BN / 4)) * BN * 8;
-        if (part > stage) stage = part;
-    }
-    return need > stage ? need : stage;
 }
 
 // config choice: 0 = unsupported, 1 = <128,32,64,2,2>, 2 = <256,32,128,2,2>, 3 = <128,16,128,2,2>, 4 = <128,16,64,2,2>,
@@ -619,21 +585,47 @@ int conv3x3_tiles(int N, int H, int W, int C, int Cn) {
 
 template <int BM, int TW, int BN, int WM, int WN, int FLIP, int X3 = 0>
 static int c3_launch(Conv3Args& g, hipStream_t st) {
-    constexpr int TH = BM / TW;
-    if constexpr (TW == 8 && BM == 128) { g.N /= 2; g.H = 16; }        // two 8 x 8 images as one 16-row image: the same bytes
-    g.tiles_x = (g.W + TW - 1) / TW; g.tiles_y = (g.H + TH - 1) / TH;
+    using G = C3Geom<BM, TW, BN, WM, WN, X3>;
+    static_assert(G::lds(2) <= 160 * 1024, "K-loop image, staging tile and partials fit a CU's 160 KB of LDS");
+    if constexpr (G::STACK) { g.N /= 2; g.H = 16; }        // two 8 x 8 images as one 16-row image: the same bytes
+    g.tiles_x = (g.W + TW - 1) / TW; g.tiles_y = (g.H + G::TH - 1) / G::TH;
     int blocks = g.N * g.tiles_x * g.tiles_y * ((g.Cn + BN - 1) / BN);
-    size_t lds = c3_lds<BM, TW, BN, WM, WN, X3>(g.C / (X3 ? 32 : 64));
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_kernel<BM, TW, BN, WM, WN, FLIP, X3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)c3_lds<BM, TW, BN, WM, WN, X3>(2));
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
+    return launch_dyn_lds<conv3x3_kernel<BM, TW, BN, WM, WN, FLIP, X3>>(g, blocks, 64 * WM * WN, G::lds(g.C / (X3 ? 32 : 64)), G::lds(2), st);
+}
+
+// geometry (c3_config's cfg) -> tile.  bf16 operands: w8 = 0: 4 waves, 1: 8 waves, 2: 8 (16 for the 256-pixel x 128-channel tile)
+template <int FLIP> static int c3_dispatch(int cfg, int w8, Conv3Args& g, hipStream_t st) {
+    if (cfg == 7) return c3_launch<256, 32, 64, 4, 2, FLIP>(g, st);
+    if (w8 == 2) {
+        if (cfg == 1) return c3_launch<128, 32, 64, 4, 2, FLIP>(g, st);
+        if (cfg == 2) return c3_launch<256, 32, 128, 4, 4, FLIP>(g, st);
+        if (cfg == 5) return c3_launch<64, 8, 128, 2, 4, FLIP>(g, st);
     }
-    conv3x3_kernel<BM, TW, BN, WM, WN, FLIP, X3><<<blocks, 64 * WM * WN, lds, st>>>(g);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    if (w8) {
+        if (cfg == 1) return c3_launch<128, 32, 64, 4, 2, FLIP>(g, st);
+        if (cfg == 2) return c3_launch<256, 32, 128, 4, 2, FLIP>(g, st);
+        if (cfg == 3) return c3_launch<128, 16, 128, 4, 2, FLIP>(g, st);
+        if (cfg == 5) return c3_launch<64, 8, 128, 2, 4, FLIP>(g, st);
+        if (cfg == 6) return c3_launch<256, 16, 64, 4, 2, FLIP>(g, st);
+        return c3_launch<128, 16, 64, 4, 2, FLIP>(g, st);
+    }
+    if (cfg == 1) return c3_launch<128, 32, 64, 2, 2, FLIP>(g, st);
+    if (cfg == 2) return c3_launch<256, 32, 128, 2, 2, FLIP>(g, st);
+    if (cfg == 3) return c3_launch<128, 16, 128, 2, 2, FLIP>(g, st);
+    if (cfg == 5) return c3_launch<64, 8, 128, 2, 2, FLIP>(g, st);
+    if (cfg == 6) return c3_launch<256, 16, 64, 4, 1, FLIP>(g, st);
+    return c3_launch<128, 16, 64, 2, 2, FLIP>(g, st);
+}
+// split-bf16 operands: always 8 waves (the accumulators of both chains need the registers)
+template <int FLIP, int X3> static int c3x_dispatch(int cfg, Conv3Args& g, hipStream_t st) {
+    if (cfg == 1) return c3_launch<128, 32, 64, 4, 2, FLIP, X3>(g, st);
+    if (cfg == 2) return c3_launch<256, 32, 128, 4, 2, FLIP, X3>(g, st);
+    if (cfg == 3) return c3_launch<128, 16, 128, 4, 2, FLIP, X3>(g, st);
+    if (cfg == 5) return c3_launch<64, 8, 128, 2, 4, FLIP, X3>(g, st);
+    if (cfg == 6) return c3_launch<256, 16, 64, 4, 2, FLIP, X3>(g, st);
+    if (cfg == 7) return c3_launch<256, 32, 64, 4, 2, FLIP, X3>(g, st);
+    if (cfg == 8) return c3_launch<128, 8, 64, 4, 2, FLIP, X3>(g, st);
+    return c3_launch<128, 16, 64, 4, 2, FLIP, X3>(g, st);
 }
 
 // x [N,H,W,C] -> out [N,H,W,Cn]; wt rows of length 9*C; flip = 0: forward weights OHWI, taps (kh-1, kw-1);
@@ -649,37 +641,11 @@ int conv3x3_run(const void* x, const void* wt, void* out, int N, int H, int W, i
     g.N = N; g.H = H; g.W = W; g.C = C; g.Cn = Cn; g.ktot = 9 * C;
     g.flip = flip;
     g.bn_y = bn_y; g.bn_out = bn_out; g.bnp = bnp; g.bn_part = bn_part;
-    static const int w8 = getenv("AB_C3_W8") ? atoi(getenv("AB_C3_W8")) : 2;     // 0: 4 waves, 1: 8 waves, 2: 8 (16 for the 256-pixel tile)
-#define C3_GO(FL) \
-    do { \
-        if (cfg == 7) return c3_launch<256, 32, 64, 4, 2, FL>(g, st); \
-        if (w8 == 2) { \
-            if (cfg == 1) return c3_launch<128, 32, 64, 4, 2, FL>(g, st); \
-            if (cfg == 2) return c3_launch<256, 32, 128, 4, 4, FL>(g, st); \
-            if (cfg == 5) return c3_launch<64, 8, 128, 2, 4, FL>(g, st); \
-        } \
-        if (w8) { \
-            if (cfg == 1) return c3_launch<128, 32, 64, 4, 2, FL>(g, st); \
-            if (cfg == 2) return c3_launch<256, 32, 128, 4, 2, FL>(g, st); \
-            if (cfg == 3) return c3_launch<128, 16, 128, 4, 2, FL>(g, st); \
-            if (cfg == 5) return c3_launch<64, 8, 128, 2, 4, FL>(g, st); \
-            if (cfg == 6) return c3_launch<256, 16, 64, 4, 2, FL>(g, st); \
-            return c3_launch<128, 16, 64, 4, 2, FL>(g, st); \
-        } \
-        if (cfg == 1) return c3_launch<128, 32, 64, 2, 2, FL>(g, st); \
-        if (cfg == 2) return c3_launch<256, 32, 128, 2, 2, FL>(g, st); \
-        if (cfg == 3) return c3_launch<128, 16, 128, 2, 2, FL>(g, st); \
-        if (cfg == 5) return c3_launch<64, 8, 128, 2, 2, FL>(g, st); \
-        if (cfg == 6) return c3_launch<256, 16, 64, 4, 1, FL>(g, st); \
-        return c3_launch<128, 16, 64, 2, 2, FL>(g, st); \
-    } while (0)
-    if (flip) C3_GO(1);
-    C3_GO(0);
-#undef C3_GO
+    static const int w8 = getenv("AB_C3_W8") ? atoi(getenv("AB_C3_W8")) : 2;
+    return flip ? c3_dispatch<1>(cfg, w8, g, st) : c3_dispatch<0>(cfg, w8, g, st);
 }
 
-// ---- split-bf16 ("bf16x3") launches: x / wt given as (hi, lo) bf16 planes, out / addend / stats fp32.
-// Tile shapes are those of the bf16 path, always on 8 waves (the accumulators of both chains need the registers).
+// ---- split-bf16 ("bf16x3") launches: x / wt given as (hi, lo) bf16 planes, out / addend / stats fp32.  Tile shapes are those of the bf16 path.
 static int c3_tiles_of(int cfg, int N, int H, int W) {
     if (!cfg) return 0;
     if (cfg == 8) return N / 2;                    // two stacked 8 x 8 images per tile
@@ -729,38 +695,7 @@ int conv3x3_x3_run(const void* x_hi, const void* x_lo, const void* wt_hi, const 
     g.N = N; g.H = H; g.W = W; g.C = C; g.Cn = Cn; g.ktot = 9 * C; g.flip = flip;
     g.bn_y = bn_y; g.bn_out = bn_out_hi; g.bnp = bnp; g.bn_part = bn_part;
     if (ev) { g.Out = ev->out_hi; g.Out_lo = ev->out_lo; g.OutF = ev->out_f32; g.res_hi = ev->res_hi; g.res_lo = ev->res_lo; g.ep_relu = ev->relu; }
-    if (bn_y) {      // masked gradient + BatchNorm-backward partials from the epilogue
-        if (cfg == 1) return c3_launch<128, 32, 64, 4, 2, 1, 2>(g, st);
-        if (cfg == 2) return c3_launch<256, 32, 128, 4, 2, 1, 2>(g, st);
-        if (cfg == 3) return c3_launch<128, 16, 128, 4, 2, 1, 2>(g, st);
-        if (cfg == 5) return c3_launch<64, 8, 128, 2, 4, 1, 2>(g, st);
-        if (cfg == 6) return c3_launch<256, 16, 64, 4, 2, 1, 2>(g, st);
-        if (cfg == 7) return c3_launch<256, 32, 64, 4, 2, 1, 2>(g, st);
-        if (cfg == 8) return c3_launch<128, 8, 64, 4, 2, 1, 2>(g, st);
-        return c3_launch<128, 16, 64, 4, 2, 1, 2>(g, st);
-    }
-    if (g.Out_lo) {      // eval-mode forward with the following BatchNorm folded in (conv3x3_x3_evalbn_run fills these fields)
-        if (cfg == 1) return c3_launch<128, 32, 64, 4, 2, 0, 3>(g, st);
-        if (cfg == 2) return c3_launch<256, 32, 128, 4, 2, 0, 3>(g, st);
-        if (cfg == 3) return c3_launch<128, 16, 128, 4, 2, 0, 3>(g, st);
-        if (cfg == 5) return c3_launch<64, 8, 128, 2, 4, 0, 3>(g, st);
-        if (cfg == 6) return c3_launch<256, 16, 64, 4, 2, 0, 3>(g, st);
-        if (cfg == 7) return c3_launch<256, 32, 64, 4, 2, 0, 3>(g, st);
-        if (cfg == 8) return c3_launch<128, 8, 64, 4, 2, 0, 3>(g, st);
-        return c3_launch<128, 16, 64, 4, 2, 0, 3>(g, st);
-    }
-#define C3X_GO(FL) \
-    do { \
-        if (cfg == 1) return c3_launch<128, 32, 64, 4, 2, FL, 1>(g, st); \
-        if (cfg == 2) return c3_launch<256, 32, 128, 4, 2, FL, 1>(g, st); \
-        if (cfg == 3) return c3_launch<128, 16, 128, 4, 2, FL, 1>(g, st); \
-        if (cfg == 5) return c3_launch<64, 8, 128, 2, 4, FL, 1>(g, st); \
-        if (cfg == 6) return c3_launch<256, 16, 64, 4, 2, FL, 1>(g, st); \
-        if (cfg == 7) return c3_launch<256, 32, 64, 4, 2, FL, 1>(g, st); \
-        if (cfg == 8) return c3_launch<128, 8, 64, 4, 2, FL, 1>(g, st); \
-        return c3_launch<128, 16, 64, 4, 2, FL, 1>(g, st); \
-    } while (0)
-    if (flip) C3X_GO(1);
-    C3X_GO(0);
-#undef C3X_GO
+    if (bn_y) return c3x_dispatch<1, 2>(cfg, g, st);          // masked gradient + BatchNorm-backward partials from the epilogue
+    if (g.Out_lo) return c3x_dispatch<0, 3>(cfg, g, st);      // eval-mode forward with the following BatchNorm folded in (`ev`)
+    return flip ? c3x_dispatch<1, 1>(cfg, g, st) : c3x_dispatch<0, 1>(cfg, g, st);
 }

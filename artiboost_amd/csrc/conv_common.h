@@ -1,4 +1,5 @@
-// Shared by conv_gemm.hip (register-staged, any dtype) and conv_gemm2.hip (direct-to-LDS bf16 fast path).
+// Shared by every convolution kernel: the implicit-GEMM arguments (conv_gemm.hip, conv_gemm2.hip), the LDS-DMA loads, the zero page and
+// the XCD renumbering.
 #pragma once
 #include "common.h"
 
@@ -58,6 +59,31 @@ __device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_byte_addr)
 __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
     return (unsigned)(size_t)(const __attribute__((address_space(3))) void*)p;
 }
+// saddr form: per-lane 32-bit byte offset + wave-uniform 64-bit base in SGPRs (no VALU 64-bit address arithmetic; one constant VGPR per
+// access pattern).  16 bytes per lane (1 KiB per wave instruction), and 4 bytes per lane (256 B per instruction: bf16 pairs).
+__device__ __forceinline__ void glds16_s(unsigned voff, const void* sbase, unsigned lds_byte_addr) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_byte_addr) : "memory");
+}
+__device__ __forceinline__ void glds4_s(unsigned voff, const void* sbase, unsigned lds_byte_addr) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_byte_addr) : "memory");
+}
+__device__ __forceinline__ const char* uniform_ptr(const void* p) {      // a wave-uniform pointer, spelled out for an asm SGPR operand
+    const unsigned long long u = (unsigned long long)p;
+    return (const char*)(((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(u >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((unsigned)u));
+}
+
+static __device__ uint4 zero_page[2];      // zero-initialised: the source of every DMA lane that fills padding or an out-of-range chunk
+
+// Workgroup `bid` of `nblk`, renumbered so that each XCD (dispatch order mod 8) owns a contiguous range of logical ids: neighbouring tiles
+// re-read each other's halo pixels and the same weight rows from that XCD's L2.  Bijective for any grid size.
+__device__ __forceinline__ int xcd_logical(int bid, int nblk) {
+    const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, within = bid >> 3;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + within;
+}
 
 // (tile, slice) of a workgroup in a (tiles, slices) grid, renumbered so that each XCD (dispatch order mod 8) owns a contiguous
 // range of slices with all their tiles: the tiles of a slice stream the same operand rows, which then come out of that XCD's L2
@@ -68,9 +94,7 @@ __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
 __device__ __forceinline__ void xcd_slice_major(int on, int& tile, int& slice) {
     tile = blockIdx.x; slice = blockIdx.y;
     if (on) {
-        const int nx = gridDim.x, nblk = nx * gridDim.y, bid = slice * nx + tile;
-        const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, within = bid >> 3;
-        const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + within;
+        const int nx = gridDim.x, logical = xcd_logical(slice * nx + tile, nx * gridDim.y);
         slice = logical / nx; tile = logical - slice * nx;
     }
 }

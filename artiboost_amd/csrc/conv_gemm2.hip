@@ -14,9 +14,7 @@
 //     with counted s_waitcnt vmcnt(N) + a raw s_barrier per step (see the loop);
 //   * 4 or 8 waves per workgroup (WM x WN): the L2->LDS fill rate scales with the number of waves issuing loads;
 //   * nclass > 1: the four output-parity classes of a stride-2 data gradient share one grid.
-#include "conv_common.h"
-
-__device__ uint4 ab_zero_page[2];    // zero-initialised device memory: source of every out-of-range chunk
+#include "conv_tile.h"      // the fp32 row bodies of the split-bf16 epilogue and its partial-row reduction
 
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
@@ -49,10 +47,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm2_kernel(ConvGemmArgs g
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wave_m = wave / WN, wave_n = wave % WN;
-    // XCD-aware renumbering (bijective for any grid size): XCD x = bid % 8 gets logical ids [start_x, start_x + cnt_x)
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, within = bid >> 3;
-    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + within;
+    const int logical = xcd_logical(blockIdx.x, gridDim.x);
     const int tiles_n = (g.Cn + BN - 1) / BN, tiles_mc = (g.M + BM - 1) / BM;      // M tiles per parity class
     const int tiles_m = tiles_mc * (g.nclass > 1 ? g.nclass : 1);
     int tile_m, tile_n;
@@ -82,7 +77,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm2_kernel(ConvGemmArgs g
     const bf16_t* __restrict__ Bw2lo = (const bf16_t*)g.Bw2_lo;
     const int alt_t = ALT ? g.alt_tap1 - 1 - tap0 : -1;       // class-local index of the tap that reads the second operand pair
     const int PQ = g.P * g.Q;
-    const bf16_t* zp = (const bf16_t*)ab_zero_page;
+    const bf16_t* zp = (const bf16_t*)zero_page;
 
     // ---- per-lane load assignment: instruction ii (0..IA-1 over the 4 waves) covers rows ii*8 .. ii*8+7
     const int lrow = lane >> 3, lslot = lane & 7;
@@ -161,21 +156,9 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm2_kernel(ConvGemmArgs g
     };
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
     f32x16 accx[X3 ? TM : 1][X3 ? TN : 1];                  // X3: the two cross products hi*lo + lo*hi (second chain)
-    if constexpr (X3) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) accx[i][j][r] = 0.f;
-    }
+    if constexpr (X3) zero_acc(accx);
 
     // ring with counted waits (raw s_barrier: __syncthreads() would drain vmcnt to 0 and kill the overlap):
     //   step s:  wait until only the loads of steps s+1 .. s+PD-1 are in flight -> barrier (step-s tile visible to all
@@ -257,7 +240,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm2_kernel(ConvGemmArgs g
         // ---- fp32 epilogue of the split-bf16 launches (same flow as below, 4-byte elements, 16-byte row vectors)
         float* __restrict__ OutF = (float*)g.Out;
         const float* __restrict__ AddF = (const float*)g.addend;
-        constexpr int SPF = BN * 4 + 16;
+        constexpr int SPF = stage_pitch_f32<BN>();      // (this accumulator is NOT transposed: the staging store below is element-wise)
         static_assert(BM * SPF <= RINGSZ, "fp32 staging tile must fit in the K-loop buffers");
         float csum[TN], csq[TN];
 #pragma unroll
@@ -284,12 +267,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm2_kernel(ConvGemmArgs g
         }
         __syncthreads();
         float bfs[4] = {0.f, 0.f, 0.f, 0.f}, bfq[4] = {0.f, 0.f, 0.f, 0.f};
-        float e_sc[4] = {}, e_sh[4] = {}, e_mean[4] = {}, e_istd[4] = {};
-        if (g.bn_y) {
-            const int ccol = n0 + (tid % (BN / 4)) * 4;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { e_sc[k] = g.bnp[ccol + k]; e_sh[k] = g.bnp[g.Cn + ccol + k]; e_mean[k] = g.bnp[2 * g.Cn + ccol + k]; e_istd[k] = g.bnp[3 * g.Cn + ccol + k]; }
-        }
+        BnBwdCh4 e_bn = {};
+        if (g.bn_y) e_bn.load(g.bnp, g.Cn, n0 + (tid % (BN / 4)) * 4);
         {
             constexpr int CPRF = BN / 4;
             const bool vec_ok = (g.Cn & 3) == 0;
@@ -300,22 +279,9 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm2_kernel(ConvGemmArgs g
                 const long o = (long)op * g.Cn + col;
                 float4 v = *(const float4*)(smem + row * SPF + c4 * 16);
                 if (g.out_hi) {          // eval-mode fold: the next convolution's operand planes, no fp32 tensor (Cn % 4 == 0 checked by the host)
-                    uint2 h, l;
-                    h.x = pack_bf16x2(v.x, v.y); h.y = pack_bf16x2(v.z, v.w);
-                    l.x = pack_bf16x2(v.x - __uint_as_float(h.x << 16), v.y - __uint_as_float(h.x & 0xffff0000u));
-                    l.y = pack_bf16x2(v.z - __uint_as_float(h.y << 16), v.w - __uint_as_float(h.y & 0xffff0000u));
-                    *(uint2*)((bf16_t*)g.out_hi + o) = h; *(uint2*)((bf16_t*)g.out_lo + o) = l;
-                } else if (g.bn_y) {     // (host: Cn % 4 == 0, BN divides Cn, no addend -- a thread keeps its four channels: NT % CPRF == 0)
-                    const float4 y4 = *(const float4*)(g.bn_y + o);
-                    float vv[4] = {v.x, v.y, v.z, v.w};
-                    const float yy[4] = {y4.x, y4.y, y4.z, y4.w};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const bool dead = !(yy[k] * e_sc[k] + e_sh[k] > 0.f);
-                        vv[k] = dead ? 0.f : vv[k];
-                        bfs[k] += vv[k]; bfq[k] += vv[k] * ((yy[k] - e_mean[k]) * e_istd[k]);
-                    }
-                    *(float4*)(OutF + o) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+                    store_planes4(g.out_hi, g.out_lo, o, v);
+                } else if (g.bn_y) {     // (host: Cn % 4 == 0, BN divides Cn, no addend, no stored mask -- a thread keeps its four channels)
+                    *(float4*)(OutF + o) = bn_bwd_mask4(v, *(const float4*)(g.bn_y + o), make_uint2(0u, 0u), false, e_bn, bfs, bfq);
                 } else if (vec_ok) {
                     if (AddF) { const float4 a = *(const float4*)(AddF + o); v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w; }
                     *(float4*)(OutF + o) = v;
@@ -328,21 +294,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_gemm2_kernel(ConvGemmArgs g
         __syncthreads();
         if (g.bn_y) {
             constexpr int CPRF = BN / 4;
-            static_assert(NT % CPRF == 0 && (NT / CPRF) * BN * 8 <= RINGSZ, "BatchNorm-backward partials: one channel group per thread, scratch over the staging tile");
-            float* sp = (float*)smem;                          // [NT / CPRF][BN][2]
-            const int rg = tid / CPRF, cb = (tid % CPRF) * 4;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { sp[(rg * BN + cb + k) * 2] = bfs[k]; sp[(rg * BN + cb + k) * 2 + 1] = bfq[k]; }
-            __syncthreads();
-            for (int c = tid; c < BN; c += NT) {
-                const int col = n0 + c;
-                if (col < g.Cn) {
-                    float s2 = 0.f, q2 = 0.f;
-                    for (int r = 0; r < NT / CPRF; ++r) { s2 += sp[(r * BN + c) * 2]; q2 += sp[(r * BN + c) * 2 + 1]; }
-                    g.bn_part[((long)stat_row * g.Cn + col) * 2] = s2;
-                    g.bn_part[((long)stat_row * g.Cn + col) * 2 + 1] = q2;
-                }
-            }
+            static_assert((NT / CPRF) * BN * 8 <= RINGSZ, "BatchNorm-backward partials: scratch over the staging tile");
+            reduce_partial_rows<4, BN, NT>((float*)smem, bfs, bfq, g.bn_part, stat_row, g.Cn, n0);
             return;
         }
         if (g.stats) {

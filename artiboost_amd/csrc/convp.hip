@@ -25,8 +25,6 @@
 #define CP_ABL 0      // tools/probe_cp.hip: knock-outs (1 no MFMAs, 2 no patch requests in the loop, 4 no weight requests in the loop, 8 no fragment reads)
 #endif
 
-static __device__ uint4 cp_zero_page[2];
-
 // fields of a unit in the table (ints): 0 src, 1 wsrc, 2 oy0, 3 ox0, 4 sy, 5 sx, 6 ntap, 7 program code (CPProg), 8..11 koff[tap], 12..15 (dh << 1 | dw)[tap]
 // (the kernel reads the code of a class's first unit and the koff entries; the rest documents what the compile-time programs assume and is
 // checked against them on the host)
@@ -112,33 +110,42 @@ __device__ __forceinline__ void cp_wait_dyn(int n) {      // n is a constant aft
     }
 }
 
-// G8 = false: base tile 16 x 16 of one image (BM = 256), patch 17 rows x 18 (17 used), swizzle key (px >> 1) & 7.
+// Tile geometry and LDS budget, read by the kernel and by cp_launch.
+// G8 = false: base tile 16 x 16 of one image (BM = 256), patch 17 rows x 18 (17 used), 16-wide swizzle key.
 // G8 = true : base grid 8 x 8, a tile is NI = BM / 64 consecutive images with a 9 x 9 patch each (conv2x2.hip's layout).
 // NPB = 3 patch buffers + ring of four weight stages: one workgroup per CU.  NPB = 2 (+ ring of three, BM = 128): 72 KB of LDS and <= 128 VGPRs, TWO
 // workgroups per CU -- one's epilogue (fp32 store, BatchNorm operands of the fused reduction) runs under the other's K loop.
+template <int BM, int BN, bool G8, int NPB> struct CPGeom {
+    static constexpr int TW = G8 ? 8 : 16, TH = G8 ? 8 : BM / 16, NI = G8 ? BM / 64 : 1, PW = G8 ? 9 : 18, PH = TH + 1, IPIX = PH * PW;
+    static_assert(BM == NI * TW * TH && (BM == 128 || BM == 256), "tile = whole base tiles");
+    static constexpr int WM = 4, WN = 2, NW = 8;
+    using L = PatchTileLds<NI * IPIX, NW, BM, BN>;
+    static constexpr int NRING = NPB == 2 ? 3 : 4, PATCH0 = NRING * L::BBYTES;      // LDS: [weight ring][patch 0][patch 1]([patch 2])
+    static constexpr int LDS = L::x3_lds(NRING, NPB);
+    static_assert(LDS <= 160 * 1024, "K-loop image, staging tile and partials fit a CU's 160 KB of LDS");
+};
+
 template <int BM, int BN, bool G8, int MODE, int NPB>
 __global__ __launch_bounds__(512, NPB == 2 ? 4 : 2) void convp_kernel(CPArgs g) {
-    constexpr int TW = G8 ? 8 : 16, TH = G8 ? 8 : BM / 16, NI = G8 ? BM / 64 : 1, PW = G8 ? 9 : 18, PH = TH + 1, IPIX = PH * PW, NPIX = NI * IPIX;
-    constexpr int PL = NPB - 1, NRING = NPB == 2 ? 3 : 4;
-    static_assert(BM == NI * TW * TH && (BM == 128 || BM == 256), "tile = whole base tiles");
-    constexpr int WM = 4, WN = 2, NW = 8, NT = 512;
-    constexpr int PI = (NPIX + 7) / 8, LP = (PI + NW - 1) / NW, PATCH_BYTES = LP * NW * 1024;
-    constexpr int IB = BN / 8, LB = IB / NW, BBYTES = BN * 128;
+    using G = CPGeom<BM, BN, G8, NPB>;
+    constexpr int TW = G::TW, TH = G::TH, NI = G::NI, PW = G::PW, IPIX = G::IPIX, NPIX = G::L::NPIX;
+    constexpr int PL = NPB - 1, NRING = G::NRING;
+    constexpr int WM = G::WM, WN = G::WN, NW = G::NW, NT = G::L::NT;
+    constexpr int PI = G::L::PI, LP = G::L::LP, PATCH_BYTES = G::L::PATCH_BYTES;
+    constexpr int IB = BN / 8, LB = IB / NW, BBYTES = G::L::BBYTES;
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-    constexpr int PATCH0 = NRING * BBYTES;                    // LDS: [weight ring][patch 0][patch 1]([patch 2])
+    constexpr int PATCH0 = G::PATCH0;
     extern __shared__ __attribute__((aligned(256))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wave_m = wave / WN, wave_n = wave % WN;
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7, within = bid >> 3;
-    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + within;
+    const int logical = xcd_logical(blockIdx.x, gridDim.x);
     const int tiles_n = g.Cn / BN;
     const int row_id = logical / tiles_n, tile_n = logical - row_id * tiles_n;        // row_id = base tile * nclass + class: the BatchNorm partial row
     const int tile_sp = row_id / g.nclass, cls = row_id - tile_sp * g.nclass;
     const int ntile = g.tiles_y * g.tiles_x, grp = tile_sp / ntile, tt = tile_sp - grp * ntile;
     const int by = (tt / g.tiles_x) * TH, bx = (tt % g.tiles_x) * TW, img = grp * NI;
     const int n0 = tile_n * BN;
-    const bf16_t* zp = (const bf16_t*)cp_zero_page;
+    const bf16_t* zp = (const bf16_t*)zero_page;
     const int nch = g.C / 32;
     const unsigned lds0 = lds_addr_of(smem);
     const int nunit = g.nunit[cls];
@@ -154,26 +161,26 @@ __global__ __launch_bounds__(512, NPB == 2 ? 4 : 2) void convp_kernel(CPArgs g) 
         const int rem = pp - p_il[j] * IPIX;
         p_py[j] = rem / PW; p_px[j] = rem - p_py[j] * PW;
         p_in[j] = ii < PI && pp < NPIX && p_px[j] < TW + 1;
-        const int c = (lane & 7) ^ (G8 ? (((p_px[j] >> 1) & 3) | ((p_py[j] & 1) << 2)) : ((p_px[j] >> 1) & 7));
-        p_lo[j] = (c & 4) != 0; p_coff[j] = (unsigned)((c & 3) * 8);
+        const int c = fill_chunk(lane, patch_key<TW>(p_py[j], p_px[j]));
+        p_lo[j] = chunk_lo(c); p_coff[j] = (unsigned)chunk_elem(c);
     }
     unsigned b_voff[2][LB];
 #pragma unroll
     for (int j = 0; j < LB; ++j) {
         const int ii = wave * LB + j, r = ii * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((r >> 1) & 7);
+        const int c = fill_chunk(lane, wrow_key(r));
 #pragma unroll
         for (int w = 0; w < 2; ++w)
-            b_voff[w][j] = (unsigned)(((long)(n0 + r) * g.ktot[w] + (c & 3) * 8) * 2) + ((c & 4) ? g.wlo_delta[w] : 0u);
+            b_voff[w][j] = (unsigned)(((long)(n0 + r) * g.ktot[w] + chunk_elem(c)) * 2) + (chunk_lo(c) ? g.wlo_delta[w] : 0u);
     }
     // ---- per-lane fragment addresses
     const int l32 = lane & 31, fhalf = lane >> 5;
-    unsigned b_rel[TN][4], a_rel[TM][2][4];
+    unsigned b_rel[TN][4], a_rel[2][TM][4];            // [weight tile][k-slice]; [tap column][pixel tile][k-slice]
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int r = (wave_n * TN + j) * 32 + l32;
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) b_rel[j][kk] = lds0 + r * 128 + (((kk * 2 + fhalf) ^ ((r >> 1) & 7)) << 4);
+        for (int kk = 0; kk < 4; ++kk) b_rel[j][kk] = lds0 + frag_off(r, kk * 2 + fhalf, wrow_key(r));
     }
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -183,8 +190,7 @@ __global__ __launch_bounds__(512, NPB == 2 ? 4 : 2) void convp_kernel(CPArgs g) 
             const int px = ox + d;
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk)
-                a_rel[i][d][kk] = lds0 + PATCH0 + (il * IPIX + oy * PW + px) * 128 +
-                                  (((kk * 2 + fhalf) ^ (G8 ? (((px >> 1) & 3) | ((oy & 1) << 2)) : ((px >> 1) & 7))) << 4);
+                a_rel[d][i][kk] = lds0 + PATCH0 + frag_off(il * IPIX + oy * PW + px, kk * 2 + fhalf, patch_key<TW>(oy, px));
         }
     }
 
@@ -216,19 +222,12 @@ __global__ __launch_bounds__(512, NPB == 2 ? 4 : 2) void convp_kernel(CPArgs g) 
         for (int j = 0; j < LB; ++j) {
             const int ii = wave * LB + j;
             const unsigned vo = wsrc ? b_voff[1][j] : b_voff[0][j];
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(vo), "s"(base), "s"(__builtin_amdgcn_readfirstlane(lds0 + slot * BBYTES + ii * 1024)) : "memory");
+            glds16_s(vo, base, __builtin_amdgcn_readfirstlane(lds0 + slot * BBYTES + ii * 1024));
         }
     };
 
     f32x16 acc[TM][TN], accx[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; accx[i][j][r] = 0.f; }
+    zero_acc(acc); zero_acc(accx);
 
     // ---- the step sequence of a chunk is a compile-time PROGRAM (units x taps), unrolled; the unit parameters are scalars fetched once.
     // Requests run ahead of the executing step: the weight stage of step k + 2 (ring of four), the patch of unit instance sc + 2 at the first tap of
@@ -273,36 +272,9 @@ __global__ __launch_bounds__(512, NPB == 2 ? 4 : 2) void convp_kernel(CPArgs g) 
                 }
                 const int dh = P::dh(u, t), dw = P::dw(u, t);
                 const unsigned aoff = pb_e * PATCH_BYTES + dh * PW * 128;
-                const unsigned aflip = (G8 && dh) ? 64u : 0u;
-                const unsigned boff = st * BBYTES;
                 u32x4 fa[4][TM] = {}, fb[4][TN] = {};
-#pragma unroll
-                for (int k2 = 0; k2 < 2; ++k2) {
-                    if (CP_ABL & 8) break;
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-#pragma unroll
-                        for (int ii = 0; ii < TM; ++ii)
-                            fa[k2 + 2 * h][ii] = *(const lds_u32x4*)(((dw ? a_rel[ii][1][k2 + 2 * h] : a_rel[ii][0][k2 + 2 * h]) ^ aflip) + aoff);
-#pragma unroll
-                        for (int jj = 0; jj < TN; ++jj) fb[k2 + 2 * h][jj] = *(const lds_u32x4*)(b_rel[jj][k2 + 2 * h] + boff);
-                    }
-                }
-#pragma unroll
-                for (int k2 = 0; k2 < 2; ++k2) {
-                    if (CP_ABL & 1) break;
-#pragma unroll
-                    for (int ii = 0; ii < TM; ++ii)
-#pragma unroll
-                        for (int jj = 0; jj < TN; ++jj) {
-                            const bf16x8 bh = __builtin_bit_cast(bf16x8, fb[k2][jj]), bl = __builtin_bit_cast(bf16x8, fb[k2 + 2][jj]);
-                            const bf16x8 ah = __builtin_bit_cast(bf16x8, fa[k2][ii]), al = __builtin_bit_cast(bf16x8, fa[k2 + 2][ii]);
-                            // weights as the first operand: the accumulator is the TRANSPOSED tile (a lane owns one pixel, see the epilogue)
-                            acc[ii][jj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh, ah, acc[ii][jj], 0, 0, 0);
-                            accx[ii][jj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh, al, accx[ii][jj], 0, 0, 0);
-                            accx[ii][jj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl, ah, accx[ii][jj], 0, 0, 0);
-                        }
-                }
+                if (!(CP_ABL & 8)) x3_read_frags(fa, fb, a_rel[dw], tap_row_flip<TW>(dh), aoff, b_rel, st * BBYTES);
+                if (!(CP_ABL & 1)) x3_mfma_step(acc, accx, fa, fb);
                 st = st == NRING - 1 ? 0 : st + 1;
                 if (t + 1 == P::ntap(u)) pb_e = pb_e == NPB - 1 ? 0 : pb_e + 1;
             }
@@ -328,36 +300,17 @@ __global__ __launch_bounds__(512, NPB == 2 ? 4 : 2) void convp_kernel(CPArgs g) 
 #undef CPU_
     __syncthreads();
 
-    // ---- fp32 epilogue (conv2x2.hip's): a lane owns ONE pixel and per register quad four consecutive channels = one 16-byte LDS store into
-    // the pixel-major staging tile; rows leave as 16-byte vectors to their (strided) output pixels; BatchNorm partials of the tile as stored.
-    constexpr int SPF = BN * 4 + 16;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int row = (wave_m * TM + i) * 32 + l32;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const int cl = (wave_n * TN + j) * 32 + 8 * q4 + 4 * fhalf;
-                float4 w;
-                w.x = acc[i][j][q4 * 4] + accx[i][j][q4 * 4]; w.y = acc[i][j][q4 * 4 + 1] + accx[i][j][q4 * 4 + 1];
-                w.z = acc[i][j][q4 * 4 + 2] + accx[i][j][q4 * 4 + 2]; w.w = acc[i][j][q4 * 4 + 3] + accx[i][j][q4 * 4 + 3];
-                *(float4*)(smem + row * SPF + cl * 4) = w;
-            }
-        }
-    }
+    // ---- fp32 epilogue (conv_tile.h): staging tile; rows leave as 16-byte vectors to their (strided) output pixels; BatchNorm partials of
+    // the tile as stored, or the fused BatchNorm-backward mask and its partials.
+    constexpr int SPF = stage_pitch_f32<BN>();
+    stage_store_f32<BN>(smem, acc, accx, wave_m, wave_n, lane);
     __syncthreads();
     constexpr int CPRF = BN / 4;
-    static_assert(NT % CPRF == 0, "a thread keeps one channel group over all its rows");
     const int coy = g.cls_oy[cls], cox = g.cls_ox[cls];
     float fs[4] = {0.f, 0.f, 0.f, 0.f}, fq[4] = {0.f, 0.f, 0.f, 0.f};
     const bool bnr = MODE == 1 && g.bn_y != nullptr;
-    float e_sc[4] = {}, e_sh[4] = {}, e_mean[4] = {}, e_istd[4] = {};
-    if (bnr) {           // (a thread keeps one channel group: NT % CPRF == 0)
-        const int col = n0 + (tid % CPRF) * 4;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { e_sc[k] = g.bnp[col + k]; e_sh[k] = g.bnp[g.Cn + col + k]; e_mean[k] = g.bnp[2 * g.Cn + col + k]; e_istd[k] = g.bnp[3 * g.Cn + col + k]; }
-    }
+    BnBwdCh4 e_bn = {};
+    if (bnr) e_bn.load(g.bnp, g.Cn, n0 + (tid % CPRF) * 4);           // (a thread keeps one channel group: NT % CPRF == 0)
     const bf16_t* __restrict__ BnM = (const bf16_t*)g.bn_out;
     for (int id = tid; id < BM * CPRF; id += NT) {
         const int row = id / CPRF, c4 = id - row * CPRF;
@@ -368,67 +321,25 @@ __global__ __launch_bounds__(512, NPB == 2 ? 4 : 2) void convp_kernel(CPArgs g) 
         if (bnr) {
             const float4 y4 = *(const float4*)(g.bn_y + o);
             const uint2 m2 = BnM ? *(const uint2*)(BnM + o) : make_uint2(0u, 0u);
-            float v[4] = {v4.x, v4.y, v4.z, v4.w};
-            const float y[4] = {y4.x, y4.y, y4.z, y4.w};
-            const float m[4] = {__uint_as_float(m2.x << 16), __uint_as_float(m2.x & 0xffff0000u), __uint_as_float(m2.y << 16), __uint_as_float(m2.y & 0xffff0000u)};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const bool dead = BnM ? !(m[k] > 0.f) : !(y[k] * e_sc[k] + e_sh[k] > 0.f);
-                v[k] = dead ? 0.f : v[k];
-                fs[k] += v[k]; fq[k] += v[k] * ((y[k] - e_mean[k]) * e_istd[k]);
-            }
-            *(float4*)(g.Out + o) = make_float4(v[0], v[1], v[2], v[3]);
+            *(float4*)(g.Out + o) = bn_bwd_mask4(v4, y4, m2, BnM != nullptr, e_bn, fs, fq);
             continue;
         }
         float4 v = v4;
-        if (MODE == 0 && g.ep_scale) {
-            const float4 sc = *(const float4*)(g.ep_scale + col), sh = *(const float4*)(g.ep_shift + col);
-            v.x = v.x * sc.x + sh.x; v.y = v.y * sc.y + sh.y; v.z = v.z * sc.z + sh.z; v.w = v.w * sc.w + sh.w;
-            if (g.ep_relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-        }
-        if (MODE == 0 && g.out_hi) {
-            uint2 h, l;
-            h.x = pack_bf16x2(v.x, v.y); h.y = pack_bf16x2(v.z, v.w);
-            l.x = pack_bf16x2(v.x - __uint_as_float(h.x << 16), v.y - __uint_as_float(h.x & 0xffff0000u));
-            l.y = pack_bf16x2(v.z - __uint_as_float(h.y << 16), v.w - __uint_as_float(h.y & 0xffff0000u));
-            *(uint2*)((bf16_t*)g.out_hi + o) = h; *(uint2*)((bf16_t*)g.out_lo + o) = l;
-        } else *(float4*)(g.Out + o) = v;
-        fs[0] += v.x; fq[0] += v.x * v.x; fs[1] += v.y; fq[1] += v.y * v.y;
-        fs[2] += v.z; fq[2] += v.z * v.z; fs[3] += v.w; fq[3] += v.w * v.w;
+        if (MODE == 0 && g.ep_scale) affine_relu4(v, g.ep_scale + col, g.ep_shift + col, g.ep_relu);
+        if (MODE == 0 && g.out_hi) store_planes4(g.out_hi, g.out_lo, o, v);
+        else *(float4*)(g.Out + o) = v;
+        stat4(fs, fq, v);
     }
     __syncthreads();
     float* part_out = bnr ? g.bn_part : g.stats;
-    if (part_out) {
-        float* sp = (float*)smem;                          // [NT / CPRF][BN][2], over the consumed staging tile
-        const int rg = tid / CPRF, cb = (tid % CPRF) * 4;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { sp[(rg * BN + cb + k) * 2] = fs[k]; sp[(rg * BN + cb + k) * 2 + 1] = fq[k]; }
-        __syncthreads();
-        for (int c = tid; c < BN; c += NT) {
-            float s2 = 0.f, q2 = 0.f;
-            for (int r = 0; r < NT / CPRF; ++r) { s2 += sp[(r * BN + c) * 2]; q2 += sp[(r * BN + c) * 2 + 1]; }
-            part_out[((long)row_id * g.Cn + n0 + c) * 2] = s2;
-            part_out[((long)row_id * g.Cn + n0 + c) * 2 + 1] = q2;
-        }
-    }
+    if (part_out) reduce_partial_rows<4, BN, NT>((float*)smem, fs, fq, part_out, row_id, g.Cn, n0);      // over the consumed staging tile
 }
 
 template <int BM, int BN, bool G8, int MODE, int NPB = 3>
 static int cp_launch(CPArgs& g, hipStream_t st) {
-    constexpr int NI = G8 ? BM / 64 : 1, NPIX = NI * (G8 ? 81 : (BM / 16 + 1) * 18), LP = ((NPIX + 7) / 8 + 7) / 8;
-    const size_t ring = (size_t)(NPB == 2 ? 3 : 4) * BN * 128 + NPB * LP * 8 * 1024, stage = (size_t)BM * (BN * 4 + 16), part = (size_t)(512 / (BN / 4)) * BN * 8;
-    size_t lds = ring > stage ? ring : stage;
-    if (part > lds) lds = part;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)convp_kernel<BM, BN, G8, MODE, NPB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    const int blocks = (g.N / NI) * g.tiles_y * g.tiles_x * g.nclass * (g.Cn / BN);
-    convp_kernel<BM, BN, G8, MODE, NPB><<<blocks, 512, lds, st>>>(g);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    using G = CPGeom<BM, BN, G8, NPB>;
+    const int blocks = (g.N / G::NI) * g.tiles_y * g.tiles_x * g.nclass * (g.Cn / BN);
+    return launch_dyn_lds<convp_kernel<BM, BN, G8, MODE, NPB>>(g, blocks, G::L::NT, G::LDS, G::LDS, st);
 }
 
 static bool cp_off() { static const int off = getenv("AB_CP_OFF") ? atoi(getenv("AB_CP_OFF")) : 0; return off != 0; }

@@ -44,11 +44,6 @@ struct GemmRwArgs {
     unsigned long long* dbg;                  // tools/probe_grw.hip: per wave {shader cycles, 100 MHz ticks} of its life (NULL: off)
 };
 
-__device__ __forceinline__ void grw_fill(unsigned voff, const void* sbase, unsigned lds_byte_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_byte_addr) : "memory");
-}
 // (no memory clobber: nothing in the kernel reads what it stores; asm volatile keeps its order among the fills / waits / stores)
 __device__ __forceinline__ void grw_store(unsigned voff, float v, const void* sbase) {
     asm volatile("global_store_dword %0, %1, %2" ::"v"(voff), "v"(v), "s"(sbase));
@@ -159,8 +154,8 @@ __global__ __launch_bounds__(512) void gemm_rw_kernel(GemmRwArgs g) {
 #pragma unroll
         for (int kc = 0; kc < KS; ++kc) {
             if constexpr (GRW_ABL & 8) break;
-            grw_fill(f_voff, ah + kc * 128, __builtin_amdgcn_readfirstlane(dst + kc * 16384));
-            grw_fill(f_voff, al + kc * 128, __builtin_amdgcn_readfirstlane(dst + kc * 16384 + 8192));
+            glds16_s(f_voff, ah + kc * 128, __builtin_amdgcn_readfirstlane(dst + kc * 16384));
+            glds16_s(f_voff, al + kc * 128, __builtin_amdgcn_readfirstlane(dst + kc * 16384 + 8192));
         }
     };
 
@@ -316,19 +311,11 @@ static int grw_launch(GemmRwArgs& g, hipStream_t st) {
         ncu = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
     }
     const size_t lds = (size_t)2 * KS * 16384 + (SAM ? 1536 : 0);
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_rw_kernel<KS, SAM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
     // one workgroup per CU, a multiple of 8 (the schedule is per XCD) and at least one tuple per XCD
     static const int wgs_env = getenv("AB_GRW_WGS") ? atoi(getenv("AB_GRW_WGS")) : 0;
     int grid = ((wgs_env > 0 ? wgs_env : ncu) / 8) * 8;
     if (grid < 8 * g.groups) grid = 8 * g.groups;
-    gemm_rw_kernel<KS, SAM><<<grid, 512, lds, st>>>(g);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launch_dyn_lds<gemm_rw_kernel<KS, SAM>>(g, grid, 512, lds, lds, st);
 }
 
 // Shapes this kernel takes: K in {64, 128, 192, 256}, N a multiple of 32, M a multiple of 64.  AB_ESHAPE otherwise (the caller falls back

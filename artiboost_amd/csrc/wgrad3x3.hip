@@ -76,7 +76,7 @@ __global__ __launch_bounds__(64 * NW) void wgrad3x3_kernel(Wg3Args g) {
     const bf16_t* __restrict__ DY = (const bf16_t*)pDY;
     const bf16_t* __restrict__ Xl = (const bf16_t*)pXl;
     const bf16_t* __restrict__ DYl = (const bf16_t*)pDYl;
-    const bf16_t* zp = (const bf16_t*)wg_zero_page;
+    const bf16_t* zp = (const bf16_t*)zero_page;
 
     // ---- per-lane fill assignment
     long a_off[LA]; bool a_ok[LA];

@@ -6,8 +6,6 @@
 typedef short short4_t __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) short4_t lds_short4;
 
-static __device__ uint4 wg_zero_page[2];          // source of the DMA lanes that fill padding
-
 // One 16 x 32 bf16 MFMA operand through ds_read_b64_tr_b16: k rows 0..3 (+8 for the upper lane groups) at addr_lo, rows 4..7 at addr_hi.
 __device__ __forceinline__ uint4 tr_pair(unsigned addr_lo, unsigned addr_hi) {
     short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4*)(size_t)addr_lo);

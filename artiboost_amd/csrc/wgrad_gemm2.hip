@@ -75,7 +75,7 @@ __global__ __launch_bounds__(64 * WI * WJ) void wgrad_gemm2_kernel(Wg2Args g) {
     const bf16_t* __restrict__ DY = (const bf16_t*)g.DY;
     const bf16_t* __restrict__ Xl = (const bf16_t*)g.X_lo;
     const bf16_t* __restrict__ DYl = (const bf16_t*)g.DY_lo;
-    const bf16_t* zp = (const bf16_t*)wg_zero_page;
+    const bf16_t* zp = (const bf16_t*)zero_page;
 
     // per-lane DMA assignment: instruction ii covers rows ii*R .. ii*R+R-1; lane -> (row in instr, slot); the lane fetches
     // the logical chunk that belongs in its slot
