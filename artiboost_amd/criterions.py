@@ -906,3 +906,252 @@ class ObjLoss(TensorLoss):
             final_loss = final_loss + self.lambda_obj_verts_3d * loss
         losses["obj_verts_3d_loss"] = loss
         return final_loss, losses
+
+
+# ---- contact loss: hand-object repulsion and attraction ------------------------------------------------------------------
+def contact_loss_torch(hand_verts, zone_id, n_zones, obj_verts, obj_faces, vert_off, face_off, obj_orient, obj_box, obj_row, rot, tsl, mask=None,
+                       rho=0.02, alpha=0.01, lambda_r=0.5, lambda_a=0.5, flags=0, want_grad=False, want_sdf=False, want_diag=False, medial=None):
+    """The definitions of ab_contact_loss (include/artiboost_hip.h) as torch ops in hand_verts' dtype: the route of CPU tensors, in float64
+    the reference of the tests, and what tools/bench_contact_loss.py times on device tensors.  Same arguments and the same dict as
+    kernels.contact_loss (`flags` is accepted and changes nothing: AB_CL_SCAN_ALL does not change a value).  `loss` [1] is differentiable by
+    autograd with respect to hand_verts, rot and tsl: the closest point cp' is found without a graph (the region form's v, w as computed,
+    the minimum over faces through gather, one [Q,F] block per sample: metrics._triangle_scan) and held fixed, and the distance is
+    stated again as d = |q - (R cp' + t)|.  want_grad: also g_hand, g_rot, g_tsl by the closed form of the header (no autograd).
+    want_diag (this route only): `diag` = {wind [B,Nh] (o w, NaN where it was not computed), inside bool [B,Nh], d [B,Nh] (NaN: no
+    candidate), winner int64 [B,max(Z,1)] (-1: none), box_margin [B,Nh] (distance of q' to the nearest face plane of the box) and, with
+    medial = (tol_d, tol_cp), medial bool [B,Nh]}."""
+    from .metrics import _triangle_scan
+    hv = hand_verts
+    dt, dev = hv.dtype, hv.device
+    B, Nh, Z = hv.shape[0], hv.shape[1], int(n_zones)
+    n_obj = int(obj_orient.numel())
+    R_all, t_all = rot.to(device=dev, dtype=dt).reshape(B, 3, 3), tsl.to(device=dev, dtype=dt).reshape(B, 3)
+    vo, fo = [int(x) for x in vert_off.cpu()], [int(x) for x in face_off.cpu()]
+    rows, orient = [int(r) for r in obj_row.cpu()], [float(x) for x in obj_orient.cpu()]
+    keep = [1.0] * B if mask is None else [float(x) for x in mask.cpu()]
+    zone = torch.full((Nh,), -1, dtype=torch.int64, device=dev)
+    if Z:
+        zi = zone_id.to(dev).long().reshape(Nh)
+        zone = torch.where((zi >= 0) & (zi < Z), zi, zone)
+    zero = torch.zeros((), dtype=dt, device=dev)
+    nan = float("nan")
+    rep, att = [], []
+    out = {"counts": torch.zeros((B, 2), dtype=torch.int32, device=dev)}
+    if want_sdf:
+        out["sdf"] = torch.full((B, Nh), nan, dtype=dt, device=dev)
+    if want_grad:
+        out["g_hand"], out["g_rot"], out["g_tsl"] = hv.new_zeros((B, Nh, 3)), hv.new_zeros((B, 3, 3)), hv.new_zeros((B, 3))
+    if want_diag:
+        out["diag"] = diag = {"wind": torch.full((B, Nh), nan, dtype=dt, device=dev), "inside": torch.zeros((B, Nh), dtype=torch.bool, device=dev),
+                              "d": torch.full((B, Nh), nan, dtype=dt, device=dev), "winner": torch.full((B, max(Z, 1)), -1, dtype=torch.int64, device=dev),
+                              "box_margin": torch.full((B, Nh), nan, dtype=dt, device=dev), "medial": torch.zeros((B, Nh), dtype=torch.bool, device=dev)}
+    w_rep, w_att = lambda_r / (B * Nh), lambda_a / (B * max(Z, 1))
+    for b in range(B):
+        r = rows[b]
+        if not 0 <= r < n_obj or keep[b] == 0.0:         # m_b = 0: nothing of the sample is scanned
+            rep.append(zero); att.append(zero)
+            continue
+        can = obj_verts[vo[r]:vo[r + 1]].to(device=dev, dtype=dt)
+        tri = can[obj_faces[fo[r]:fo[r + 1]].to(dev).long().reshape(-1, 3)]
+        R, t, q = R_all[b], t_all[b], hv[b]
+        with torch.no_grad():
+            qc = (q - t) @ R                                                       # q' = R^T (q - t)
+            box = obj_box.reshape(-1, 6)[r].to(device=dev, dtype=dt)
+            inbox = ((qc >= box[:3]) & (qc <= box[3:])).all(1)
+            idx = (inbox | (zone >= 0)).nonzero()[:, 0]                            # the candidates, ascending
+            if want_diag:
+                diag["box_margin"][b] = torch.minimum((qc - box[:3]).abs(), (qc - box[3:]).abs()).min(1)[0]
+        out["counts"][b, 1] = idx.numel()
+        if idx.numel() == 0:
+            rep.append(zero); att.append(zero)
+            continue
+        with torch.no_grad():
+            w, d2, cp = _triangle_scan(qc[idx], tri, True, want_cp=True, medial=medial)
+            ow = orient[r] * w
+            ins = inbox[idx] & (ow > 0.5)
+            ds = d2.sqrt()
+            cpc = qc[idx] + cp["r"]                                                # cp' = q' - r', r' = -(cp - q')
+        diff = q[idx] - (cpc @ R.T + t)                                           # cp' is held fixed: d = |q - (R cp' + t)|
+        s2 = (diff * diff).sum(-1)
+        nz = s2 > 0
+        d = torch.where(nz, torch.where(nz, s2, torch.ones_like(s2)).sqrt(), torch.zeros_like(s2))
+        rep.append((rho * torch.tanh(d / rho))[ins].sum() / Nh)
+        a, zc, winners = zero, zone[idx], []
+        for z in range(Z):
+            sel = ((zc == z) & ~ins).nonzero()[:, 0]
+            if sel.numel():
+                j = sel[ds[sel].min(0)[1]]                                         # the smallest d, the lowest index among equals
+                a = a + alpha * torch.tanh(d[j] / alpha)
+                winners.append(int(j))
+                if want_diag:
+                    diag["winner"][b, z] = idx[j]
+        att.append(a / max(Z, 1))
+        out["counts"][b, 0] = ins.sum().to(torch.int32)
+        if want_sdf:
+            out["sdf"][b, idx] = torch.where(ins, -d, d).detach()
+        if want_diag:
+            diag["wind"][b, idx] = torch.where(inbox[idx], ow, torch.full_like(ow, nan))
+            diag["inside"][b, idx], diag["d"][b, idx] = ins, ds
+            if medial is not None:
+                diag["medial"][b, idx] = cp["medial"]
+        if want_grad:
+            with torch.no_grad():
+                wgt, scale = torch.where(ins, torch.full_like(ds, w_rep), torch.zeros_like(ds)), torch.full_like(ds, rho)
+                for j in winners:
+                    wgt[j], scale[j] = w_att, alpha
+                safe = torch.where(ds > 0, ds, torch.ones_like(ds))
+                c = torch.where(ds > 0, wgt / torch.cosh(ds / scale) ** 2 / safe, torch.zeros_like(ds))
+                g = c[:, None] * ((-cp["r"]) @ R.T)                                # weight s n, n = R r' / d
+                out["g_hand"][b, idx] = g
+                out["g_tsl"][b] = -g.sum(0)
+                out["g_rot"][b] = -(g[:, :, None] * cpc[:, None, :]).sum(0)
+    out["rep"], out["att"] = torch.stack(rep), torch.stack(att)
+    out["loss"] = ((lambda_r * out["rep"].sum() + lambda_a * out["att"].sum()) / B).reshape(1)
+    return out
+
+
+class _ContactLossFn(torch.autograd.Function):
+    """ab_contact_loss (csrc/contact_loss.hip): ONE call in forward leaves the loss and its gradient with respect to the hand vertices, the
+    rotation entries and the translation; backward scales the kept buffers by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, hand, rot, tsl, args, kw):
+        from . import kernels as K
+        want = any(ctx.needs_input_grad[:3])
+        o = K.contact_loss(hand, args[0], args[1], *args[2:], rot, tsl, want_grad=want, **kw)
+        ctx.shapes = (hand.shape, rot.shape, tsl.shape)
+        if want:
+            ctx.save_for_backward(o["g_hand"], o["g_rot"], o["g_tsl"])
+        rep, att = o["rep"].mean(), o["att"].mean()
+        ctx.mark_non_differentiable(rep, att)
+        return o["loss"].reshape(()), rep, att
+
+    @staticmethod
+    def backward(ctx, g, g_rep, g_att):
+        return tuple((t * g).reshape(s) for t, s in zip(ctx.saved_tensors, ctx.shapes)) + (None, None)
+
+
+def tip_zones(v_template, tips, radius):
+    """zone_id int32 [Nh]: zone z holds the rest-template vertices within `radius` of vertex tips[z]; a vertex in two spheres goes to the
+    lower zone; -1 elsewhere."""
+    v = np.asarray(v_template, np.float64)
+    zone = np.full(len(v), -1, np.int32)
+    for z in reversed(range(len(tips))):
+        zone[np.linalg.norm(v - v[tips[z]], axis=1) <= radius] = z
+    return zone
+
+
+@LOSS.register_module
+class ContactLoss(TensorLoss):
+    """The contact loss of Hasson et al. (CVPR 2019) between the predicted hand mesh and the posed object mesh:
+    repulsion of the hand vertices inside the object, rho tanh(d / rho) with rho = REPULSE_MM, and attraction of the contact zones that do
+    not touch it, alpha tanh(d_z / alpha) with alpha = ATTRACT_MM.  The hand is preds[HAND_KEY]; the object is its canonical mesh
+    (OBJ_MESHES, the block of InteractionMetric, or `set_obj_meshes(table)`) chosen by targs[obj_idx] under preds[ROT_KEY] / preds[TSL_KEY]
+    (OBJ_POSE: pred) or under targs[obj_transf], which gets no gradient (OBJ_POSE: gt).  ZONES: `tips` (one zone per fingertip vertex
+    745, 317, 444, 556, 673 -- anakin/models/mano.py:26-30 -- holding the rest-template vertices within ZONE_RADIUS_MM of it), a list of
+    vertex index lists, or [].  MANO_ASSETS_ROOT (assets/mano_v1_2) names the hand model whose rest template the tip zones are cut from;
+    SCAN_ALL: true passes AB_CL_SCAN_ALL (every vertex scanned; the same bits).  A sample whose object the table lacks contributes 0 and
+    counts in the batch.  HIP tensors: ONE
+    ab_contact_loss call, loss and gradients; the eager route only (TrainStep refuses to capture a step that holds this loss).  CPU tensors:
+    contact_loss_torch in their dtype."""
+    TIPS = (745, 317, 444, 556, 673)
+
+    def __init__(self, **cfg):
+        super().__init__()
+        self.lambda_repulsion, self.lambda_attraction = float(cfg.get("LAMBDA_REPULSION", 0.5)), float(cfg.get("LAMBDA_ATTRACTION", 0.5))
+        self.rho, self.alpha = float(cfg.get("REPULSE_MM", 20)) / 1000.0, float(cfg.get("ATTRACT_MM", 10)) / 1000.0
+        self.zone_radius = float(cfg.get("ZONE_RADIUS_MM", 10)) / 1000.0
+        if not (self.rho > 0 and self.alpha > 0 and self.zone_radius >= 0):
+            raise ValueError("ContactLoss: REPULSE_MM > 0, ATTRACT_MM > 0 and ZONE_RADIUS_MM >= 0")
+        self.hand_key = cfg.get("HAND_KEY", "hand_verts_3d_abs")
+        self.rot_key, self.tsl_key = cfg.get("ROT_KEY", "box_rot_rotmat"), cfg.get("TSL_KEY", "boxroot_3d_abs")
+        self.obj_pose = str(cfg.get("OBJ_POSE", "pred"))
+        if self.obj_pose not in ("pred", "gt"):
+            raise ValueError(f"ContactLoss: OBJ_POSE must be 'pred' or 'gt', got {self.obj_pose!r}")
+        self.zones = cfg.get("ZONES", "tips")
+        if not (self.zones == "tips" or (isinstance(self.zones, (list, tuple)) and len(self.zones) <= 16 and
+                                          all(isinstance(z, (list, tuple)) for z in self.zones))):
+            raise ValueError("ContactLoss: ZONES must be 'tips' or a list of at most 16 vertex index lists")
+        self.mano_assets_root = cfg.get("MANO_ASSETS_ROOT", "assets/mano_v1_2")
+        self.scan_all = bool(cfg.get("SCAN_ALL", False))
+        self.table = None
+        src = cfg.get("OBJ_MESHES")
+        if src:
+            if str(src.get("SOURCE", "assets")) != "assets":
+                raise ValueError(f"ContactLoss: OBJ_MESHES.SOURCE must be 'assets' (or call set_obj_meshes), got {src.get('SOURCE')!r}")
+            from .assets import SceneAssets
+            from .metrics import ObjectMeshTable
+            self.table = ObjectMeshTable.from_assets(SceneAssets(src.get("DATASET", "HO3D"), seed=1))
+        self._zone = {}
+
+    def set_obj_meshes(self, table):
+        if table.hand_faces is None:
+            from .hpregnet import load_hand_model
+            table.set_hand(load_hand_model(self.mano_assets_root))
+        self.table = table
+        return self
+
+    def zone_ids(self, Nh):
+        """(zone_id int32 [Nh] numpy, Z) of the configured zones for a hand of Nh vertices."""
+        if Nh not in self._zone:
+            if self.zones == "tips":
+                from .hpregnet import load_hand_model
+                v = np.asarray(load_hand_model(self.mano_assets_root)["v_template"])
+                if len(v) != Nh:
+                    raise ValueError(f"ContactLoss: ZONES 'tips' needs the hand model's {len(v)} vertices, got {Nh}")
+                self._zone[Nh] = (tip_zones(v, self.TIPS, self.zone_radius), len(self.TIPS))
+            else:
+                zone = np.full(Nh, -1, np.int32)
+                for z in reversed(range(len(self.zones))):
+                    ids = np.asarray(self.zones[z], np.int64).reshape(-1)
+                    if ids.size and (ids.min() < 0 or ids.max() >= Nh):
+                        raise ValueError(f"ContactLoss: zone {z} holds a vertex index outside [0, {Nh})")
+                    zone[ids] = z                                                  # a vertex in two zones goes to the lower one
+                self._zone[Nh] = (zone, len(self.zones))
+        return self._zone[Nh]
+
+    def _zone_on(self, Nh, dev):
+        key = (Nh, str(dev))
+        if key not in self._zone:
+            zone, Z = self.zone_ids(Nh)
+            self._zone[key] = (torch.from_numpy(zone).to(dev), Z)
+        return self._zone[key]
+
+    def __call__(self, preds, targs, **kwargs):
+        final_loss, losses = super().__call__(preds, targs, **kwargs)
+        contact = rep = att = None
+        if self.lambda_repulsion or self.lambda_attraction:
+            if self.table is None:
+                raise RuntimeError("ContactLoss: no object meshes (OBJ_MESHES in the config, or set_obj_meshes)")
+            if targs.get(Queries.OBJ_IDX) is None:
+                raise KeyError(Queries.OBJ_IDX)
+            for k in (self.hand_key,) + ((self.rot_key, self.tsl_key) if self.obj_pose == "pred" else ()):
+                if preds.get(k) is None:
+                    raise KeyError(k)
+            hand = preds[self.hand_key]
+            dev, B, Nh = hand.device, hand.shape[0], hand.shape[1]
+            if self.obj_pose == "pred":
+                rot, tsl = preds[self.rot_key], preds[self.tsl_key]
+            else:
+                if targs.get(Queries.OBJ_TRANSF) is None:
+                    raise KeyError(Queries.OBJ_TRANSF)
+                T = targs[Queries.OBJ_TRANSF].detach().to(dev)
+                rot, tsl = T[:, :3, :3], T[:, :3, 3]
+            tb = self.table.on(dev)
+            zone, Z = self._zone_on(Nh, dev)
+            args = (zone if Z else None, Z, tb["obj_verts"], tb["obj_faces"], tb["vert_off"], tb["face_off"], tb["obj_orient"], tb["obj_box"],
+                    self.table.rows(targs[Queries.OBJ_IDX].to(dev)))
+            kw = dict(rho=self.rho, alpha=self.alpha, lambda_r=self.lambda_repulsion, lambda_a=self.lambda_attraction)
+            if dev.type == "cuda":      # one ab_contact_loss call, analytic backward (eager only, DESIGN.md section 26)
+                from . import kernels as K
+                kw["flags"] = K.CL_SCAN_ALL if self.scan_all else 0
+                contact, rep, att = _ContactLossFn.apply(_dev_f32(hand, dev), _dev_f32(rot, dev).reshape(B, 3, 3), _dev_f32(tsl, dev).reshape(B, 3), args, kw)
+            else:
+                o = contact_loss_torch(hand, args[0], args[1], *args[2:], rot.to(hand.dtype).reshape(B, 3, 3), tsl.to(hand.dtype).reshape(B, 3), **kw)
+                contact, rep, att = o["loss"].reshape(()), o["rep"].detach().mean(), o["att"].detach().mean()
+            final_loss = final_loss + contact
+        losses["contact_loss"] = contact
+        losses["repulsion_loss"] = rep if self.lambda_repulsion else None
+        losses["attraction_loss"] = att if self.lambda_attraction else None
+        losses[self.output_key] = final_loss
+        return final_loss, losses

@@ -1194,6 +1194,45 @@ def interaction(hand_verts, hand_faces, hand_orient, obj_verts, obj_faces, vert_
     return o
 
 
+CL_SCAN_ALL = 1                                 # AB_CL_SCAN_ALL: scan every vertex, not only the candidates (same bits; the A/B of the benchmark)
+CL_MAX_ZONES = 16
+CL_COUNTS = {"n_inside": 0, "n_candidates": 1}
+
+
+def contact_loss(hand_verts, zone_id, n_zones, obj_verts, obj_faces, vert_off, face_off, obj_orient, obj_box, obj_row, rot, tsl, mask=None,
+                 rho=0.02, alpha=0.01, lambda_r=0.5, lambda_a=0.5, flags=0, want_grad=True, want_sdf=False):
+    """ab_contact_loss (eager only, never under graph capture): repulsion of the hand vertices [B,Nh,3] inside the object rot[b] can + tsl[b]
+    of the packed table (the arguments of `interaction`, plus obj_box fp32 [n_obj,6]) and attraction of the zones zone_id int32 [Nh]
+    (-1 = none, 0 .. n_zones-1; None when n_zones == 0) that do not touch it; mask fp32 [B] or None (0 = the sample contributes nothing).
+    rho, alpha in metres.  -> dict: loss [1], rep [B], att [B], counts int32 [B,2] (CL_COUNTS); with want_grad g_hand [B,Nh,3], g_rot [B,3,3],
+    g_tsl [B,3] (the gradient of loss; the rotation's nine entries free); with want_sdf sdf [B,Nh] (NaN: no candidate, -d inside, +d outside)."""
+    B, Nh, n_obj = hand_verts.shape[0], hand_verts.shape[1], obj_orient.numel()
+    if not 0 <= int(n_zones) <= CL_MAX_ZONES:
+        raise ValueError(f"contact_loss: 0 <= n_zones <= {CL_MAX_ZONES}, got {n_zones}")
+    if (zone_id is None and n_zones) or not (float(rho) > 0 and float(alpha) > 0):
+        raise ValueError("contact_loss: zone_id is needed with n_zones > 0, and rho, alpha must be > 0")
+    for what, t, dt, numel in (("zone_id", zone_id, torch.int32, Nh), ("obj_faces", obj_faces, torch.int32, None), ("vert_off", vert_off, torch.int32, n_obj + 1),
+                               ("face_off", face_off, torch.int32, n_obj + 1), ("obj_row", obj_row, torch.int64, B), ("obj_verts", obj_verts, torch.float32, None)):
+        if t is not None and (t.dtype != dt or (t.numel() != numel if numel is not None else t.numel() < 3)):
+            raise ValueError(f"contact_loss: {what} must be {dt} with {numel if numel is not None else 'at least 3'} elements, got {t.dtype} {tuple(t.shape)}")
+    ins = {"hand_verts": _f32_of("contact_loss", "hand_verts", hand_verts, B * Nh * 3), "obj_orient": _f32_of("contact_loss", "obj_orient", obj_orient, n_obj),
+           "obj_box": _f32_of("contact_loss", "obj_box", obj_box, n_obj * 6), "rot": _f32_of("contact_loss", "rot", rot, B * 9),
+           "tsl": _f32_of("contact_loss", "tsl", tsl, B * 3), "mask": None if mask is None else _f32_of("contact_loss", "mask", mask, B)}
+    dev = hand_verts.device
+    z = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)      # noqa: E731
+    o = {"loss": z(1), "rep": z(B), "att": z(B), "counts": torch.empty((B, 2), dtype=torch.int32, device=dev)}
+    if want_grad:
+        o["g_hand"], o["g_rot"], o["g_tsl"] = z(B, Nh, 3), z(B, 3, 3), z(B, 3)
+    if want_sdf:
+        o["sdf"] = z(B, Nh)
+    ws = _workspace(L.lib().ab_contact_loss_workspace(L.i(B), L.i(Nh)), dev)
+    L.check(L.lib().ab_contact_loss(ins["hand_verts"], L.ptr(zone_id), L.i(Nh), L.i(n_zones), L.ptr(obj_verts), L.ptr(obj_faces), L.ptr(vert_off),
+                                    L.ptr(face_off), ins["obj_orient"], ins["obj_box"], L.i(n_obj), L.ptr(obj_row), ins["rot"], ins["tsl"], ins["mask"],
+                                    L.i(B), L.f(rho), L.f(alpha), L.f(lambda_r), L.f(lambda_a), L.i(flags), o["loss"], o["rep"], o["att"], o["counts"],
+                                    o.get("sdf"), o.get("g_hand"), o.get("g_rot"), o.get("g_tsl"), L.ptr(ws), L.stream()), "ab_contact_loss")
+    return o
+
+
 FIT_NP = 59             # parameters per hand of ab_mano_fit: so3 48 | beta 10 | bone 1
 
 

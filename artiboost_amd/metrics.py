@@ -871,14 +871,18 @@ def mesh_orientation(verts, faces):
     return -1.0 if vol < 0 else 1.0
 
 
-def _triangle_scan(q, tri, want_dist):
+def _triangle_scan(q, tri, want_dist, want_cp=False, medial=None):
     """q [Q,3] against tri [F,3,3] as [Q,F] blocks (at most 2^20 pairs at a time) -> (w [Q] = sum_f Omega_f / (4 pi), the smallest squared
-    distance [Q] or None), by the definitions of ab_interaction in the tensors' dtype."""
+    distance [Q] or None), by the definitions of ab_interaction in the tensors' dtype.  want_cp (with want_dist): a third value, the dict
+    {r [Q,3]: cp - q of the first face in face order that attains the minimum (through gather), face [Q]: its index} and, with
+    medial = (tol_d, tol_cp), also `medial` [Q]: whether a face whose distance is within tol_d of the smallest has its closest point more
+    than tol_cp away from the winner's (the query sits near the medial axis: the closest point is not stable under rounding)."""
     import math
     Q, F = q.shape[0], tri.shape[0]
     e1, e2 = (tri[:, 1] - tri[:, 0])[None], (tri[:, 2] - tri[:, 0])[None]
     dot = lambda x, y: (x * y).sum(-1)      # noqa: E731
     ws, ds = [], []
+    rs, fs, ms = [], [], []
     step = max(1, (1 << 20) // max(F, 1))
     for s in range(0, Q, step):
         qq = q[s:s + step, None]
@@ -907,6 +911,19 @@ def _triangle_scan(q, tri, want_dist):
         v, w = torch.where(ok, nv / safe, zero), torch.where(ok, nw / safe, zero)  # a zero denominator gives parameter 0
         r = A + v[..., None] * e1 + w[..., None] * e2
         ds.append(dot(r, r).min(1)[0])
+        if want_cp:
+            dd = dot(r, r)
+            j = dd.min(1)[1]                                                       # the first minimum in face order
+            rb = r.gather(1, j[:, None, None].expand(-1, 1, 3))[:, 0]
+            rs.append(rb); fs.append(j)
+            if medial is not None:
+                near = dd.sqrt() <= dd.min(1)[0].sqrt()[:, None] + medial[0]
+                ms.append((near & (((r - rb[:, None]) ** 2).sum(-1).sqrt() > medial[1])).any(1))
+    if want_dist and want_cp:
+        cp = {"r": torch.cat(rs), "face": torch.cat(fs)}
+        if medial is not None:
+            cp["medial"] = torch.cat(ms)
+        return torch.cat(ws), torch.cat(ds), cp
     return torch.cat(ws), (torch.cat(ds) if want_dist else None)
 
 
@@ -999,6 +1016,8 @@ class ObjectMeshTable:
         self.verts, self.faces = np.concatenate(vs), np.concatenate(fs)
         self.vert_off, self.face_off = np.asarray(vo, np.int32), np.asarray(fo, np.int32)
         self.orient = np.asarray(orient, np.float32)
+        # the closed axis-aligned box of each object's canonical vertices, lo xyz | hi xyz: minima and maxima of fp32 values, so exact in fp32
+        self.box = np.stack([np.concatenate([v.min(0), v.max(0)]) for v in vs]).astype(np.float32)
         self.obj_ids = [int(i) for i in obj_ids]
         self.row_of = {i: r for r, i in enumerate(self.obj_ids)}
         lut = np.full(max(self.obj_ids + [0]) + 1, -1, np.int64)      # an id the table lacks maps to -1 (the kernel clamps it to row 0)
@@ -1046,7 +1065,7 @@ class ObjectMeshTable:
                 raise RuntimeError("ObjectMeshTable: no hand faces (set_hand)")
             t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)      # noqa: E731
             self._dev[key] = dict(obj_verts=t(self.verts), obj_faces=t(self.faces), vert_off=t(self.vert_off), face_off=t(self.face_off),
-                                  obj_orient=t(self.orient), hand_faces=t(self.hand_faces), lut=t(self._lut))
+                                  obj_orient=t(self.orient), obj_box=t(self.box), hand_faces=t(self.hand_faces), lut=t(self._lut))
         return self._dev[key]
 
     def rows(self, obj_idx):

@@ -248,8 +248,12 @@ class TrainStep:
         torch.cuda.synchronize(self.dev)
 
     def _capture(self):
-        # ab_chamfer_rigid / ab_procrustes_loss are never captured: refused before anything of the device is touched
-        from .criterions import AlignLoss, ChamferLoss
+        # ab_chamfer_rigid / ab_procrustes_loss / ab_contact_loss are never captured (DESIGN.md sections 19, 26): refused before anything of
+        # the device is touched
+        from .criterions import AlignLoss, ChamferLoss, ContactLoss
+        if any(isinstance(l, ContactLoss) for l in self.crit.loss_list):
+            raise NotImplementedError("ContactLoss runs on the eager route only: a step that holds it is not captured in a hipGraph "
+                                      "(DESIGN.md section 26); build the TrainStep with use_graph=False")
         if any(isinstance(l, (ChamferLoss, AlignLoss)) for l in self.crit.loss_list):
             raise NotImplementedError("ChamferLoss / AlignLoss run on the eager route only: a step that holds either is not captured in a "
                                       "hipGraph (DESIGN.md section 19); build the TrainStep with use_graph=False")

@@ -850,6 +850,47 @@ int ab_interaction(const float* hand_verts, const int32_t* hand_faces, int Nh, i
                    const int64_t* obj_row, const float* rot, const float* tsl, int B, float contact_thr, float voxel, int max_voxels, int flags,
                    float* rows, int32_t* counts, float* sdf, float* wind, void* workspace, void* stream);
 
+/* ---- Contact loss: hand-object repulsion and attraction with their gradient, eager only (csrc/contact_loss.hip) ------
+ * The contact loss of Hasson et al. (CVPR 2019) on the quantities of ab_interaction, for training: hand vertices inside the posed object
+ * are pushed out, contact zones that do not touch it are pulled in.  The object of sample b is rot[b] can + tsl[b] from the packed table
+ * of ab_interaction (same arguments); a hand vertex q is taken into the canonical frame once, q' = rot[b]^T (q - tsl[b]).
+ *   distance     d(q) and the closest point cp'(q) by the triangle region form of ab_interaction, the first minimum in face order winning;
+ *                the residual r' = q' - cp' is the sum of differences that form leaves, d = |r'|.
+ *   box          obj_box [n_obj,6] (lo xyz | hi xyz): the closed axis-aligned box of each object's canonical vertices, exact in fp32,
+ *                formed once per object by the host.
+ *   inside(q)    q' in box AND o w(q) > 0.5 (w the generalised winding number, o the table's orientation).  A vertex outside the box is
+ *                outside by definition and its winding number is not computed.
+ *   candidates   q' in box, or zone_id >= 0: the vertices that can contribute; only they are scanned.
+ *   repulsion    rep[b] = (1 / Nh) sum over inside vertices of rho tanh(d / rho)
+ *   attraction   zone_id int32 [Nh] (shared by the batch; NULL allowed when Z == 0): -1, or any value outside 0 .. Z-1, = no zone.  For zone
+ *                z, among its vertices that are NOT inside, d_z is the smallest d, the lowest vertex index winning ties; a zone without
+ *                such a vertex contributes 0.  The box does not limit attraction.  att[b] = (1 / max(Z, 1)) sum_z alpha tanh(d_z / alpha)
+ *   loss         loss[0] = (lambda_r sum_b m_b rep[b] + lambda_a sum_b m_b att[b]) / B;  m_b = 0 for a sample whose obj_row is outside
+ *                [0, n_obj) or whose mask (fp32 [B], optional) is 0: it still counts in B, nothing of it is scanned, rep[b] = att[b] = 0,
+ *                its counts are 0, its sdf NaN and its gradients 0.
+ *   gradient     analytic, cp' held fixed (it minimises the distance): d = |q - (rot[b] cp' + tsl[b])|.  With n = rot[b] r' / d and
+ *                s = sech^2(d / scale), a contributing vertex gets g_q = weight s n, 0 when d == 0: weight lambda_r m_b / (B Nh) and scale
+ *                rho for an inside vertex, weight lambda_a m_b / (B max(Z, 1)) and scale alpha for a zone's winner.  The two sets are
+ *                disjoint; every other vertex gets exactly 0.  g_tsl[b] = -sum g_q;  g_rot[b] = -sum g_q cp'^T, the nine rotation entries
+ *                free variables (the convention of ab_chamfer_rigid).  g_hand [B,Nh,3], g_rot [B,9], g_tsl [B,3]: all three or none.
+ * counts int32 [B,2]: n_inside, n_candidates.  sdf [B,Nh] (optional): NaN for a vertex that is no candidate, -d for an inside vertex, +d
+ * for any other candidate.  AB_CL_SCAN_ALL scans every vertex of an unmasked sample instead of its candidates; what it scans beyond them
+ * is dropped, so every output has the same bits with and without it (the A/B of tools/bench_contact_loss.py).
+ * workspace: ab_contact_loss_workspace(B, Nh) bytes.  Launches: classify and compact (one workgroup per sample; the candidates as an
+ * ascending index list by ballots and prefix counts), scan (a FIXED grid of ceil(Nh / 256) chunks of 256 candidates per sample; a
+ * workgroup past the list leaves at once, the host reads nothing back; triangles through LDS in tiles of 512), finalize (one workgroup per
+ * sample: zone winners, terms, gradients, the 12 pose sums), one workgroup for the batch.  No atomics: two calls give the same bits, and a
+ * sample's rep, att, sdf, counts and B x its gradients do not depend on the batch around it for B a power of two.
+ * 1 <= B <= 65535, 1 <= Nh <= 2^24, 0 <= Z <= 16, rho > 0, alpha > 0: AB_EINVAL otherwise (the tables' contents are trusted).
+ * Like the mesh losses above, this entry point is not captured in a hipGraph anywhere in this project (DESIGN.md sections 19, 26).       */
+#define AB_CL_SCAN_ALL 1
+long ab_contact_loss_workspace(int B, int Nh);
+int ab_contact_loss(const float* hand_verts, const int32_t* zone_id, int Nh, int Z, const float* obj_verts, const int32_t* obj_faces,
+                    const int32_t* vert_off, const int32_t* face_off, const float* obj_orient, const float* obj_box, int n_obj,
+                    const int64_t* obj_row, const float* rot, const float* tsl, const float* mask, int B, float rho, float alpha,
+                    float lambda_r, float lambda_a, int flags, float* loss, float* rep, float* att, int32_t* counts, float* sdf,
+                    float* g_hand, float* g_rot, float* g_tsl, void* workspace, void* stream);
+
 /* ---- BOP pose errors of the evaluator, eager only (ab_mspd: csrc/mssd.hip, ab_vsd: csrc/bop_recall.hip) ---------------
  * The two errors of bop_toolkit's pose_error.py that, with ab_mssd, make the BOP average recall: MSPD and VSD.
  *
@@ -985,6 +1026,7 @@ int ab_vsd(const float* obj_verts, const int32_t* obj_faces, const int32_t* vert
  * @check ab_procrustes_loss: pred targ aligned g_pred >= B*n*3; root >= B*3; sample_loss >= B; loss >= 1
  * @check ab_mesh_metrics: pred >= B*N*3; targ >= B*M*3; root >= B*3; thresholds_host >= T; rows >= B*AB_MM_ROW; counts >= B*T*4; d_pg pa_d_pg >= B*N; d_gp pa_d_gp >= B*M; bytes workspace >= ab_mesh_metrics_workspace(B,N,M)
  * @check ab_interaction: hand_verts >= B*Nh*3; hand_faces >= Fh*3; vert_off face_off >= n_obj+1; obj_verts >= 3; obj_faces >= 3; obj_orient >= n_obj; obj_row >= B; rot >= B*9; tsl >= B*3; rows >= B*AB_IA_ROW; counts >= B*4; sdf wind >= B*Nh; bytes workspace >= ab_interaction_workspace(B,Nh,max_voxels)
+ * @check ab_contact_loss: hand_verts g_hand >= B*Nh*3; zone_id >= Nh; vert_off face_off >= n_obj+1; obj_verts >= 3; obj_faces >= 3; obj_orient >= n_obj; obj_box >= n_obj*6; obj_row mask rep att >= B; rot g_rot >= B*9; tsl g_tsl >= B*3; loss >= 1; counts >= B*2; sdf >= B*Nh; bytes workspace >= ab_contact_loss_workspace(B,Nh)
  * @check ab_mspd: can pred_pts >= B*V*3; obj_transf >= B*16; obj_idx mspd >= B; sym_R >= n_obj*Kmax*9; sym_t >= n_obj*Kmax*3; sym_count >= n_obj; pred_R cam_intr >= B*9; pred_t >= B*3; bytes workspace >= ab_mspd_workspace(B,Kmax,V)
  * @check ab_vsd: obj_verts >= 3; obj_faces >= 3; vert_off face_off >= n_obj+1; rows >= B; rot_est rot_gt cam_intr >= B*9; tsl_est tsl_gt >= B*3; depth_test >= B*H*W; occ_verts >= B*Nv*3; occ_faces >= Nf*3; taus_host >= T; diameter >= n_obj; counts >= B*(2+T); err >= B*T; depth_out >= B*3*H*W; bytes workspace >= ab_vsd_workspace(B,max_obj_verts,Nv,W,H,T)
  */
