@@ -21,9 +21,6 @@ struct hl_weights {
     float lam_shape, lam_pose, lam_joints, lam_hand_verts, lam_obj_verts, w_mano, w_obj;
 };
 
-__device__ __forceinline__ void hl_ld3(const float* p, size_t i, float v[3]) { v[0] = p[i * 3]; v[1] = p[i * 3 + 1]; v[2] = p[i * 3 + 2]; }
-__device__ __forceinline__ void hl_st3(float* p, size_t i, float a, float b, float c) { p[i * 3] = a; p[i * 3 + 1] = b; p[i * 3 + 2] = c; }
-
 // one point of an MSE term: d = pred - (targ + root); -> |d|^2, and scale * d into the gradient (scale = 2 lambda / count; targ NULL: zeros)
 __device__ __forceinline__ float hl_point(const float* __restrict__ pred, const float* __restrict__ targ, const float root[3], size_t i,
                                           float* __restrict__ grad, float scale, float d[3]) {
@@ -31,12 +28,12 @@ __device__ __forceinline__ float hl_point(const float* __restrict__ pred, const 
     d[0] = d[1] = d[2] = 0.f;
     if (targ) {
         float p[3], t[3];
-        hl_ld3(pred, i, p);
-        hl_ld3(targ, i, t);
+        ld3(pred, i, p);
+        ld3(targ, i, t);
         for (int k = 0; k < 3; ++k) d[k] = p[k] - (t[k] + root[k]);
         sq = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
     }
-    if (grad) hl_st3(grad, i, scale * d[0], scale * d[1], scale * d[2]);
+    if (grad) st3(grad, i, scale * d[0], scale * d[1], scale * d[2]);
     return sq;
 }
 
@@ -48,7 +45,7 @@ __global__ __launch_bounds__(256) void honet_loss_kernel(
         float* __restrict__ partial, float* __restrict__ g_joints_3d_abs, float* __restrict__ g_hand_verts_3d_abs,
         float* __restrict__ g_obj_verts_3d_abs, float* __restrict__ g_mano_pca_pose, float* __restrict__ g_mano_shape) {
     __shared__ float red[4][HL_NSUM];
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y, tid = threadIdx.x;
     const float root[3] = {root_joint[(size_t)b * 3], root_joint[(size_t)b * 3 + 1], root_joint[(size_t)b * 3 + 2]};
     const float Bf = (float)B;
     float* out = partial + ((size_t)b * (nco + 1) + blockIdx.x) * HL_NSUM;
@@ -87,13 +84,8 @@ __global__ __launch_bounds__(256) void honet_loss_kernel(
             if (g_mano_pca_pose) g_mano_pca_pose[(size_t)b * P + tid] = (w.w_mano * w.lam_pose * 2.f / (Bf * (float)ncomps)) * x;
         }
     }
-#pragma unroll
-    for (int k = 0; k < HL_NSUM; ++k) acc[k] = wave_sum(acc[k]);
-    if (lane == 0)
-        for (int k = 0; k < HL_NSUM; ++k) red[wave][k] = acc[k];
-    __syncthreads();
+    float s = block_sum4<HL_NSUM>(acc, red);
     if (tid < HL_NSUM) {
-        float s = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
         if (tid == 5) s /= 21.f;
         if (tid == 6) s /= 8.f;
         out[tid] = s;
@@ -108,17 +100,11 @@ __global__ __launch_bounds__(64) void honet_loss_finalize(const float* __restric
     for (int c = 0; c < HL_NSUM; ++c) col[c] = 0.0;
     for (int b = lane; b < B; b += 64) {
         float s[HL_NSUM];
-        for (int c = 0; c < HL_NSUM; ++c) s[c] = 0.f;
-        for (int x = 0; x <= nco; ++x) {                   // the sample's rows in chunk order
-            const float* row = partial + ((size_t)b * (nco + 1) + x) * HL_NSUM;
-            for (int c = 0; c < HL_NSUM; ++c) s[c] += row[c];
-        }
+        sum_rows<HL_NSUM>(partial + (size_t)b * (nco + 1) * HL_NSUM, nco + 1, s);
         for (int c = 0; c < HL_NSUM; ++c) { sample_part[(size_t)b * HL_NSUM + c] = s[c]; col[c] += (double)s[c]; }
     }
 #pragma unroll
-    for (int c = 0; c < HL_NSUM; ++c)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) col[c] += __shfl_xor(col[c], o, 64);
+    for (int c = 0; c < HL_NSUM; ++c) col[c] = wave_sum(col[c]);
     if (lane != 0) return;
     const double Bd = (double)B;
     const float ms = (float)(col[0] / (Bd * 10.0)), mp = (float)(col[1] / (Bd * (double)ncomps));
@@ -200,16 +186,16 @@ __global__ __launch_bounds__(256) void mesh_queries_kernel(
     float c[3];
     if (p < n) {
         const size_t i = (size_t)b * n + p;
-        hl_ld3(table, (size_t)P.row * n + p, c);
-        hl_st3(obj_verts_can, i, c[0], c[1], c[2]);
-        hl_st3(obj_verts_3d, i,
+        ld3(table, (size_t)P.row * n + p, c);
+        st3(obj_verts_can, i, c[0], c[1], c[2]);
+        st3(obj_verts_3d, i,
                ((((P.R[0] * c[0] + P.R[1] * c[1]) + P.R[2] * c[2]) + P.t[0]) - P.root[0]),
                ((((P.R[3] * c[0] + P.R[4] * c[1]) + P.R[5] * c[2]) + P.t[1]) - P.root[1]),
                ((((P.R[6] * c[0] + P.R[7] * c[1]) + P.R[8] * c[2]) + P.t[2]) - P.root[2]));
     } else {
         const size_t i = (size_t)b * NV + (p - n);
-        hl_ld3(hand_verts, i, c);
-        hl_st3(hand_verts_3d, i,
+        ld3(hand_verts, i, c);
+        st3(hand_verts_3d, i,
                (((P.rm[0] * c[0] + P.rm[1] * c[1]) + P.rm[2] * c[2]) - P.root[0]),
                (((P.rm[3] * c[0] + P.rm[4] * c[1]) + P.rm[5] * c[2]) - P.root[1]),
                (((P.rm[6] * c[0] + P.rm[7] * c[1]) + P.rm[8] * c[2]) - P.root[2]));
@@ -241,7 +227,7 @@ struct rmq_place {
 };
 
 __device__ __forceinline__ void rmq_apply(const float* __restrict__ m, const float c[3], float* __restrict__ dst, size_t i) {
-    hl_st3(dst, i,
+    st3(dst, i,
            (((m[0] * c[0] + m[1] * c[1]) + m[2] * c[2]) + m[3]),
            (((m[4] * c[0] + m[5] * c[1]) + m[6] * c[2]) + m[7]),
            (((m[8] * c[0] + m[9] * c[1]) + m[10] * c[2]) + m[11]));
@@ -267,12 +253,12 @@ __global__ __launch_bounds__(256) void real_mesh_queries_kernel(
     float c[3];
     if (p < n) {
         const size_t i = (size_t)b * n + p;
-        hl_ld3(table, (size_t)P.row * n + p, c);
-        hl_st3(obj_verts_can, i, c[0], c[1], c[2]);
+        ld3(table, (size_t)P.row * n + p, c);
+        st3(obj_verts_can, i, c[0], c[1], c[2]);
         rmq_apply(P.obj, c, obj_verts_3d, i);
     } else {
         const size_t i = (size_t)b * NV + (p - n);
-        hl_ld3(mano_verts, i, c);
+        ld3(mano_verts, i, c);
         rmq_apply(P.hand, c, hand_verts_3d, i);
     }
 }

@@ -85,8 +85,6 @@ __device__ __forceinline__ void hr_rotate(const float* R, const float c[3], floa
     r[2] = (R[6] * c[0] + R[7] * c[1]) + R[8] * c[2];
 }
 
-__device__ __forceinline__ void ld3(const float* p, size_t i, float v[3]) { v[0] = p[i * 3]; v[1] = p[i * 3 + 1]; v[2] = p[i * 3 + 2]; }
-__device__ __forceinline__ void st3(float* p, size_t i, const float v[3]) { p[i * 3] = v[0]; p[i * 3 + 1] = v[1]; p[i * 3 + 2] = v[2]; }
 __device__ __forceinline__ void add3(const float* p, size_t i, float v[3]) {
     if (p) { v[0] += p[i * 3]; v[1] += p[i * 3 + 1]; v[2] += p[i * 3 + 2]; }
 }
@@ -147,15 +145,10 @@ __global__ __launch_bounds__(256) void honet_recover_fwd_kernel(
     }
 }
 
-// block-wide sums of acc[HR_NSUM] in a fixed order -> out[HR_NSUM] (thread 0 writes)
-__device__ __forceinline__ void hr_block_sums(float acc[HR_NSUM], float (*red)[HR_NSUM], float* out) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < HR_NSUM; ++k) acc[k] = wave_sum(acc[k]);
-    if (lane == 0)
-        for (int k = 0; k < HR_NSUM; ++k) red[wave][k] = acc[k];
-    __syncthreads();
-    if (tid < HR_NSUM) out[tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+// block-wide sums of acc[HR_NSUM] in the fixed order -> the block's row out[HR_NSUM]
+__device__ __forceinline__ void hr_block_sums(float (&acc)[HR_NSUM], float (*red)[HR_NSUM], float* out) {
+    const float s = block_sum4<HR_NSUM>(acc, red);
+    if (threadIdx.x < HR_NSUM) out[threadIdx.x] = s;
 }
 
 // one rotated point of the object (vertex or corner): gp = dL/d(abs point) -> the sums
@@ -253,11 +246,7 @@ __global__ __launch_bounds__(64) void honet_recover_fin_kernel(
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
     float s[HR_NSUM];
-    for (int k = 0; k < HR_NSUM; ++k) s[k] = 0.f;
-    for (int c = 0; c <= nco; ++c) {
-        const float* row = partial + ((size_t)b * (nco + 1) + c) * HR_NSUM;
-        for (int k = 0; k < HR_NSUM; ++k) s[k] += row[k];
-    }
+    sum_rows<HR_NSUM>(partial + (size_t)b * (nco + 1) * HR_NSUM, nco + 1, s);
     float K[9];
     for (int i = 0; i < 9; ++i) K[i] = cam_intr[(size_t)b * 9 + i];
     const float* h = hand_st + (size_t)b * hand_pitch;

@@ -33,12 +33,6 @@ __device__ __forceinline__ void fit_quat_to_aa(const float* __restrict__ q, floa
     aa[0] = q1 * k; aa[1] = q2 * k; aa[2] = q3 * k;
 }
 
-__device__ __forceinline__ void cross3(const float* a, const float* b, float* c) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
 __global__ __launch_bounds__(256) void mano_fit_kernel(const float* __restrict__ quat, const float* __restrict__ pred_joints,
                                                        const float* __restrict__ v_template, const float* __restrict__ shapedirs,
                                                        const float* __restrict__ posedirs, const float* __restrict__ J_regressor,

@@ -36,7 +36,6 @@ __global__ __launch_bounds__(CH_THREADS) void chamfer_rigid_kernel(const float* 
     __shared__ __attribute__((aligned(16))) float vs[3 * CH_TILE];
     __shared__ float s_red[4][13];
     const int b = blockIdx.y, chunk = blockIdx.x, nchunks = gridDim.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool own_x = chunk < cx;                                               // block-uniform: this chunk's queries are points of x
     const int nq = own_x ? N : M, ns = own_x ? M : N;                            // queries / scanned points of this direction
     const int q0 = (own_x ? chunk : chunk - cx) * CH_THREADS;
@@ -107,15 +106,8 @@ __global__ __launch_bounds__(CH_THREADS) void chamfer_rigid_kernel(const float* 
             acc[10] = d2 * c0; acc[11] = d2 * c1; acc[12] = d2 * c2;
         }
     }
-#pragma unroll
-    for (int k = 0; k < 13; ++k) acc[k] = wave_sum(acc[k]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 13; ++k) s_red[wave][k] = acc[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < CH_PART)
-        pout[threadIdx.x] = threadIdx.x < 13 ? ((s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + s_red[2][threadIdx.x]) + s_red[3][threadIdx.x] : 0.f;
+    const float tot = block_sum4<13>(acc, s_red);
+    if (threadIdx.x < CH_PART) pout[threadIdx.x] = threadIdx.x < 13 ? tot : 0.f;
 }
 
 // One thread per sample adds its chunks in turn; the batch sum of the distances is a fixed tree (thread-serial, wave butterfly, waves in turn).
@@ -125,7 +117,7 @@ __global__ __launch_bounds__(256) void chamfer_rigid_finalize_kernel(const float
     __shared__ float s_red[4][2];
     const int nchunks = cx + cy;
     const float sxy = (2.f / (float)N) / (float)B, syx = (2.f / (float)M) / (float)B;   // 1/B last: exact when B is a power of two
-    float axy = 0.f, ayx = 0.f;
+    float a[2] = {0.f, 0.f};                                                     // distances x -> y | y -> x
     for (int b = threadIdx.x; b < B; b += 256) {
         float sx[13], sy[13];
 #pragma unroll
@@ -137,7 +129,7 @@ __global__ __launch_bounds__(256) void chamfer_rigid_finalize_kernel(const float
         for (int c = cx; c < nchunks; ++c)
 #pragma unroll
             for (int k = 0; k < 13; ++k) sy[k] += p[(size_t)c * CH_PART + k];
-        axy += sx[0]; ayx += sy[0];
+        a[0] += sx[0]; a[1] += sy[0];
         if (g_rot) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) g_tsl[(size_t)b * 3 + k] = sxy * sx[1 + k] + syx * sy[1 + k];
@@ -145,13 +137,8 @@ __global__ __launch_bounds__(256) void chamfer_rigid_finalize_kernel(const float
             for (int k = 0; k < 9; ++k) g_rot[(size_t)b * 9 + k] = sxy * sx[4 + k] + syx * sy[4 + k];
         }
     }
-    axy = wave_sum(axy); ayx = wave_sum(ayx);
-    if ((threadIdx.x & 63) == 0) { s_red[threadIdx.x >> 6][0] = axy; s_red[threadIdx.x >> 6][1] = ayx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float a = ((s_red[0][0] + s_red[1][0]) + s_red[2][0]) + s_red[3][0], c = ((s_red[0][1] + s_red[1][1]) + s_red[2][1]) + s_red[3][1];
-        loss[0] = a / ((float)B * (float)N) + c / ((float)B * (float)M);
-    }
+    const float txy = block_sum4<2>(a, s_red), tyx = __shfl(txy, 1, 64);          // thread 0 takes thread 1's column
+    if (threadIdx.x == 0) loss[0] = txy / ((float)B * (float)N) + tyx / ((float)B * (float)M);
 }
 
 extern "C" long ab_chamfer_rigid_workspace(int B, int N, int M) {
@@ -247,7 +234,8 @@ __global__ __launch_bounds__(PR_THREADS) void procrustes_kernel(const float* __r
     }
 }
 
-// the batch mean of the per-sample losses: thread-serial, wave butterfly, waves in turn
+// the batch mean of the per-sample losses: thread-serial, wave butterfly, waves in turn (block_sum4's order, spelled out: through the helper
+// this one-column kernel measured slower, profiles/criterion_bodies.md)
 __global__ __launch_bounds__(256) void procrustes_finalize_kernel(const float* __restrict__ sample_loss, int B, float* __restrict__ loss) {
     __shared__ float s_red[4];
     float a = 0.f;

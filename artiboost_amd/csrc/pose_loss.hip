@@ -12,8 +12,6 @@
 // inputs, drawn on the host in the reference's RNG order.  Deterministic: no atomics; fixed reduction order.
 #include "common.h"
 
-#define PL_NJ 21
-#define PL_NC 8
 #define PL_MAXPAIR 96
 #define PL_MAXVIEW 48
 
@@ -65,13 +63,119 @@ struct PoseLossArgs {
     float* g_shape;            // [B,10]
 };
 
-__device__ __forceinline__ void cross3(const float* a, const float* b, float* o) {
-    o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
-}
+// plain multiply-add, left to right (procrustes.h's dot3 is an fmaf chain: the same name, not the same arithmetic)
 __device__ __forceinline__ float dot3(const float* a, const float* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 __device__ __forceinline__ float sgn(float x) { return (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f); }
 
 __constant__ int c_parents[21] = {0, 0, 1, 2, 3, 0, 5, 6, 7, 0, 9, 10, 11, 0, 13, 14, 15, 0, 17, 18, 19};
+
+// ---- the pose assembly of hybridbaseline.py:49-96, once for pose_loss_kernel<0>, pose_loss_kernel<1> (its corners and outputs) and
+// pose_assemble_kernel.  The caller stages one sample's inputs in LDS and calls the steps on its first wave with a barrier between them:
+// a `lane` of 64 or more (the other waves of the sixteen-wave kernel) takes no part in any of them.
+struct PoseLds {                      // the caller's __shared__ arrays (separate arrays: each keeps the alignment the wide LDS reads want)
+    const float *kp, *Kc, (*CAN)[3], *RJ;   // staged inputs: uvd predictions [66], intrinsics [9], canonical corners [8], root
+    float (*P)[3], (*C)[3], (*R)[3];  // predicted abs positions (21 joints + boxroot), abs corners [8], rotation
+};
+
+// uvd -> xyz (transform.py:512-546)
+__device__ __forceinline__ void uvd2xyz(const PoseLds& s, int lane, float res_w, float res_h, float depth_range) {
+    const float fx = s.Kc[0], fy = s.Kc[4], cx = s.Kc[2], cy = s.Kc[5], rootz = s.RJ[2];
+    if (lane < 22) {
+        float u = s.kp[lane * 3], v = s.kp[lane * 3 + 1], d = s.kp[lane * 3 + 2];
+        float z = (d - 0.5f) * depth_range + rootz;
+        s.P[lane][0] = (u * res_w - cx) / fx * z;
+        s.P[lane][1] = (v * res_h - cy) / fy * z;
+        s.P[lane][2] = z;
+    }
+}
+
+// ortho6d -> R (transform.py:578-618) and its reverse, one thread.  The forward leaves what the reverse needs.
+struct Rot6d {
+    alignas(16) float xh[3], zh[3], b[3];   // x = a / |a|, z = (x x b) / |x x b|, the second input vector
+    float an, zn;                           // |a|, |x x b| (clamped)
+};
+__device__ __forceinline__ void rot6d_fwd(const float* a, const float* b, float (*R)[3], Rot6d& s) {
+    float yh[3], zraw[3];
+    float n = sqrtf(dot3(a, a)); n = fmaxf(n, 1e-8f); s.an = n;
+    for (int i = 0; i < 3; ++i) { s.xh[i] = a[i] / n; s.b[i] = b[i]; }
+    cross3(s.xh, b, zraw);
+    float m = sqrtf(dot3(zraw, zraw)); m = fmaxf(m, 1e-8f); s.zn = m;
+    for (int i = 0; i < 3; ++i) s.zh[i] = zraw[i] / m;
+    cross3(s.zh, s.xh, yh);
+    for (int i = 0; i < 3; ++i) { R[i][0] = s.xh[i]; R[i][1] = yh[i]; R[i][2] = s.zh[i]; }
+}
+// GR = dL/dR -> ga, gb = dL/d(a, b)
+__device__ __forceinline__ void rot6d_bwd(const Rot6d& s, const float (*GR)[3], float* ga, float* gb) {
+    float gx[3] = {GR[0][0], GR[1][0], GR[2][0]}, gy[3] = {GR[0][1], GR[1][1], GR[2][1]}, gz[3] = {GR[0][2], GR[1][2], GR[2][2]};
+    float t[3];
+    cross3(s.xh, gy, t); for (int i = 0; i < 3; ++i) gz[i] += t[i];        // y = z x x
+    cross3(gy, s.zh, t); for (int i = 0; i < 3; ++i) gx[i] += t[i];
+    float gzr[3]; float dz = dot3(s.zh, gz);
+    for (int i = 0; i < 3; ++i) gzr[i] = (gz[i] - s.zh[i] * dz) / s.zn;    // z = zraw / |zraw|
+    cross3(s.b, gzr, t); for (int i = 0; i < 3; ++i) gx[i] += t[i];        // zraw = x x b
+    cross3(gzr, s.xh, gb);
+    float dx = dot3(s.xh, gx);
+    for (int i = 0; i < 3; ++i) ga[i] = (gx[i] - s.xh[i] * dx) / s.an;     // x = a / |a|
+}
+
+// corners = R * can + boxroot
+__device__ __forceinline__ void box_corners(const PoseLds& s, int lane) {
+    if (lane < 24) {
+        int c = lane / 3, i = lane % 3;
+        const float* can = s.CAN[c];
+        s.C[c][i] = s.R[i][0] * can[0] + s.R[i][1] * can[1] + s.R[i][2] * can[2] + s.P[21][i];
+    }
+}
+
+// what both callers write: joints_3d_abs, corners_3d_abs, box_rot_rotmat and (uvd2d may be NULL) the 2d_uvd rows
+__device__ __forceinline__ void pose_write(const PoseLds& s, int lane, int b, float res_w, float res_h, float* joints_abs, float* corners_abs,
+                                           float* rotmat, float* uvd2d) {
+    if (lane < 63) joints_abs[(long)b * 63 + lane] = s.P[lane / 3][lane % 3];
+    if (lane < 24) corners_abs[(long)b * 24 + lane] = s.C[lane / 3][lane % 3];
+    if (lane < 9) rotmat[(long)b * 9 + lane] = s.R[lane / 3][lane % 3];
+    if (uvd2d) {
+        float* o = uvd2d + (long)b * 90;
+        const float* kp = s.kp;
+        if (lane < 21) { o[lane * 3] = kp[lane * 3]; o[lane * 3 + 1] = kp[lane * 3 + 1]; o[lane * 3 + 2] = kp[lane * 3 + 2]; }
+        if (lane < 8) {
+            const float* K = s.Kc;
+            float X = s.C[lane][0], Y = s.C[lane][1], Z = s.C[lane][2];
+            float hx = K[0] * X + K[1] * Y + K[2] * Z, hy = K[3] * X + K[4] * Y + K[5] * Z, hz = K[6] * X + K[7] * Y + K[8] * Z;
+            o[(21 + lane) * 3] = hx / hz / res_w; o[(21 + lane) * 3 + 1] = hy / hz / res_h; o[(21 + lane) * 3 + 2] = 0.f;
+        }
+        if (lane < 3) o[29 * 3 + lane] = kp[21 * 3 + lane];
+    }
+}
+
+// The joint-level and scene-level ordinal terms (ordinal.py:39-56 under log(1 + relu)): pair pi = (A[i0s[pi]], B[i1s[pi]]), its views spread
+// over LPP lanes.  Thread t0 of the loss's wave range starts at pair t0 / LPP and steps `stride` pairs; g_pair[pi] receives the gradient
+// wrt A_p - B_p (weight w included).  Returns the thread's sum of the terms.
+template <int LPP>
+__device__ __forceinline__ float ordinal_pairs(int t0, int stride, int npair, const uint8_t* i0s, const uint8_t* i1s, const float (*A_t)[3],
+                                               const float (*B_t)[3], const float (*A_p)[3], const float (*B_p)[3], const float (*views)[3],
+                                               int nv, float w, float (*g_pair)[3]) {
+    const int sub = t0 & (LPP - 1);
+    float sum = 0.f;
+    for (int pi = t0 / LPP; pi < npair; pi += stride) {
+        int i0 = (int)i0s[pi], i1 = (int)i1s[pi];
+        float dt[3], dp[3], g[3] = {0.f, 0.f, 0.f};
+        for (int i = 0; i < 3; ++i) { dt[i] = A_t[i0][i] - B_t[i1][i]; dp[i] = A_p[i0][i] - B_p[i1][i]; }
+        for (int v = sub; v < nv; v += LPP) {
+            float s = sgn(dot3(dt, views[v])), t = -s * dot3(dp, views[v]);
+            if (t > 0.f) {
+                sum += log1pf(t);
+                float c = w * (-s) / (1.f + t);
+                g[0] += c * views[v][0]; g[1] += c * views[v][1]; g[2] += c * views[v][2];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int o = 1; o < LPP; o <<= 1) g[i] += __shfl_xor(g[i], o, 64);      // the fixed butterfly over the pair's lanes
+        if (sub == 0) { g_pair[pi][0] = g[0]; g_pair[pi][1] = g[1]; g_pair[pi][2] = g[2]; }
+    }
+    return sum;
+}
 
 // One workgroup of sixteen waves per sample.  The short assembly phases run on wave 0 (`lane` is out of range on the other
 // waves, so every `lane < N` guard excludes them).  The three ordinal losses run side by side on disjoint wave ranges with
@@ -82,17 +186,25 @@ __constant__ int c_parents[21] = {0, 0, 1, 2, 3, 0, 5, 6, 7, 0, 9, 10, 11, 0, 13
 // joints + the TARGET's root, corners = R(transf[3:9]) * can + root + transf[0:3] -- plus ManoLoss (criterions/honetloss.py:12-73): the
 // unmasked joint MSE per sample in sample_part[:, 7] and the gradients of the two regularisers; their sums are pose_loss_finalize<1>'s.
 #define PL_WAVES 16
+// the waves' partials p[w * stride], added in wave order
+__device__ __forceinline__ float sum_waves(const float* p, int stride) {
+    float s = 0.f;
+#pragma unroll
+    for (int w = 0; w < PL_WAVES; ++w) s += p[w * stride];
+    return s;
+}
 template <int REG>
 __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a) {
     const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, l64 = tid & 63;
     const int lane = wave == 0 ? tid : 1 << 20;
     __shared__ float P[22][3];        // predicted abs positions (21 joints + boxroot)
     __shared__ float C[8][3];         // predicted abs corners
+    __shared__ float R[3][3], avec[3], bvec[3];
+    __shared__ Rot6d rot;             // thread 0's, kept for the backward
     __shared__ float mP[21][3], mT[21][3], mC[8][3], mTC[8][3];   // vis-masked pred / target
     __shared__ float T[21][3], TC[8][3];
     __shared__ float part_p[20][3], part_t[20][3];
     __shared__ float vj[21], vc[8];
-    __shared__ float R[3][3], xh[3], yh[3], zh[3], zraw[3], avec[3], bvec[3], an, zn;
     __shared__ float hv[PL_MAXVIEW][3], sv[PL_MAXVIEW][3];
     __shared__ float gjp[PL_MAXPAIR][3];                 // gradient wrt (mP_a - mP_b) per joint pair
     __shared__ float gpp[PL_MAXPAIR][3], gpq[PL_MAXPAIR][3];   // gradient wrt part_p, part_q per part pair
@@ -107,6 +219,7 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
     __shared__ uint8_t ij0[PL_MAXPAIR], ij1[PL_MAXPAIR], ip0[PL_MAXPAIR], ip1[PL_MAXPAIR], is0[PL_MAXPAIR], is1[PL_MAXPAIR];
     __shared__ float kp[66], Kc[9], CAN[8][3], J3[63], C3[24], RJ[3];
     __shared__ float tvec[3];         // REG: the object's translation (transf[0:3])
+    const PoseLds ps = {kp, Kc, CAN, RJ, P, C, R};
     float r_pose = 0.f, r_shape = 0.f;
     // unconditional loads (index clamped, absent tables redirected to a valid address), conditional LDS writes: branches
     // around the loads would put each one in its own basic block with its own s_waitcnt
@@ -171,34 +284,15 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
     if (lane < 8) vc[lane] = r_vc;
     }
     __syncthreads();
-    const float fx = Kc[0], fy = Kc[4], cx = Kc[2], cy = Kc[5], rootz = RJ[2];
-    // ---- uvd -> xyz (transform.py:512-546)
     if constexpr (REG) {      // hpregnet.py:112-147: joints + the target's root; P[21] = the object's centre
         if (lane < 63) P[lane / 3][lane % 3] = kp[lane] + RJ[lane % 3];
         if (lane < 3) P[21][lane] = RJ[lane] + tvec[lane];
-    } else if (lane < 22) {
-        float u = kp[lane * 3], v = kp[lane * 3 + 1], d = kp[lane * 3 + 2];
-        float z = (d - 0.5f) * a.depth_range + rootz;
-        P[lane][0] = (u * a.res_w - cx) / fx * z;
-        P[lane][1] = (v * a.res_h - cy) / fy * z;
-        P[lane][2] = z;
+    } else {
+        uvd2xyz(ps, lane, a.res_w, a.res_h, a.depth_range);
     }
-    // ---- ortho6d -> R (transform.py:578-618)
-    if (lane == 0) {
-        float n = sqrtf(dot3(avec, avec)); n = fmaxf(n, 1e-8f); an = n;
-        for (int i = 0; i < 3; ++i) xh[i] = avec[i] / n;
-        cross3(xh, bvec, zraw);
-        float m = sqrtf(dot3(zraw, zraw)); m = fmaxf(m, 1e-8f); zn = m;
-        for (int i = 0; i < 3; ++i) zh[i] = zraw[i] / m;
-        cross3(zh, xh, yh);
-        for (int i = 0; i < 3; ++i) { R[i][0] = xh[i]; R[i][1] = yh[i]; R[i][2] = zh[i]; }
-    }
+    if (lane == 0) rot6d_fwd(avec, bvec, R, rot);
     __syncthreads();
-    if (lane < 24) {
-        int c = lane / 3, i = lane % 3;
-        const float* can = CAN[c];
-        C[c][i] = R[i][0] * can[0] + R[i][1] * can[1] + R[i][2] * can[2] + P[21][i];
-    }
+    box_corners(ps, lane);
     if (lane < 63) {
         int k = lane / 3, i = lane % 3;
         float t = J3[k * 3 + i] + RJ[i];
@@ -216,21 +310,7 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
         part_t[k - 1][i] = mT[k][i] - mT[c_parents[k]][i];
     }
     __syncthreads();
-    // ---- outputs
-    if (lane < 63) a.joints_abs[(long)b * 63 + lane] = P[lane / 3][lane % 3];
-    if (lane < 24) a.corners_abs[(long)b * 24 + lane] = C[lane / 3][lane % 3];
-    if (lane < 9) a.rotmat[(long)b * 9 + lane] = R[lane / 3][lane % 3];
-    if (a.uvd2d) {
-        float* o = a.uvd2d + (long)b * 90;
-        if (lane < 21) { o[lane * 3] = kp[lane * 3]; o[lane * 3 + 1] = kp[lane * 3 + 1]; o[lane * 3 + 2] = kp[lane * 3 + 2]; }
-        if (lane < 8) {
-            const float* K = Kc;
-            float X = C[lane][0], Y = C[lane][1], Z = C[lane][2];
-            float hx = K[0] * X + K[1] * Y + K[2] * Z, hy = K[3] * X + K[4] * Y + K[5] * Z, hz = K[6] * X + K[7] * Y + K[8] * Z;
-            o[(21 + lane) * 3] = hx / hz / a.res_w; o[(21 + lane) * 3 + 1] = hy / hz / a.res_h; o[(21 + lane) * 3 + 2] = 0.f;
-        }
-        if (lane < 3) o[29 * 3 + lane] = kp[21 * 3 + lane];
-    }
+    pose_write(ps, lane, b, a.res_w, a.res_h, a.joints_abs, a.corners_abs, a.rotmat, a.uvd2d);
     // ---- losses: per-lane partial sums   [Lj, Lc, jo, po, so]
     float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     const float B_ = (float)a.B;
@@ -245,23 +325,7 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
     const float wpo = a.w_handord * a.lam_hand_part / nPO;
     const float wso = a.w_sceneord * a.lam_scene / nSO;
     if (wave < wj) {                                    // joint-level ordinal: 4 lanes per pair
-        const int sub = tid & 3;
-        for (int pi = tid >> 2; pi < a.njp; pi += wj * 16) {
-            int i0 = (int)ij0[pi], i1 = (int)ij1[pi];
-            float dt[3], dp[3], g[3] = {0.f, 0.f, 0.f};
-            for (int i = 0; i < 3; ++i) { dt[i] = mT[i0][i] - mT[i1][i]; dp[i] = mP[i0][i] - mP[i1][i]; }
-            for (int v = sub; v < a.nvh; v += 4) {
-                float s = sgn(dot3(dt, hv[v])), t = -s * dot3(dp, hv[v]);
-                if (t > 0.f) {
-                    acc[2] += log1pf(t);
-                    float c = wjo * (-s) / (1.f + t);
-                    g[0] += c * hv[v][0]; g[1] += c * hv[v][1]; g[2] += c * hv[v][2];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { g[i] += __shfl_xor(g[i], 1, 64); g[i] += __shfl_xor(g[i], 2, 64); }
-            if (sub == 0) { gjp[pi][0] = g[0]; gjp[pi][1] = g[1]; gjp[pi][2] = g[2]; }
-        }
+        acc[2] = ordinal_pairs<4>(tid, wj * 16, a.njp, ij0, ij1, mT, mT, mP, mP, hv, a.nvh, wjo, gjp);
     } else if (wave < wj + wp) {                        // part-level ordinal: 4 lanes per pair
         const int t0 = tid - wj * 64, sub = t0 & 3;
         for (int pi = t0 >> 2; pi < a.npp; pi += wp * 16) {
@@ -288,23 +352,7 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
             if (sub == 0) for (int i = 0; i < 3; ++i) { gpp[pi][i] = gp[i]; gpq[pi][i] = gq[i]; }
         }
     } else if (wave < wj + wp + ws) {                   // scene ordinal: 8 lanes per pair
-        const int t0 = tid - (wj + wp) * 64, sub = t0 & 7;
-        for (int pi = t0 >> 3; pi < a.nsp; pi += ws * 8) {
-            int i0 = (int)is0[pi], i1 = (int)is1[pi];
-            float dt[3], dp[3], g[3] = {0.f, 0.f, 0.f};
-            for (int i = 0; i < 3; ++i) { dt[i] = mT[i0][i] - mTC[i1][i]; dp[i] = mP[i0][i] - mC[i1][i]; }
-            for (int v = sub; v < a.nvs; v += 8) {
-                float s = sgn(dot3(dt, sv[v])), t = -s * dot3(dp, sv[v]);
-                if (t > 0.f) {
-                    acc[4] += log1pf(t);
-                    float c = wso * (-s) / (1.f + t);
-                    g[0] += c * sv[v][0]; g[1] += c * sv[v][1]; g[2] += c * sv[v][2];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { g[i] += __shfl_xor(g[i], 1, 64); g[i] += __shfl_xor(g[i], 2, 64); g[i] += __shfl_xor(g[i], 4, 64); }
-            if (sub == 0) { gsp[pi][0] = g[0]; gsp[pi][1] = g[1]; gsp[pi][2] = g[2]; }
-        }
+        acc[4] = ordinal_pairs<8>(tid - (wj + wp) * 64, ws * 8, a.nsp, is0, is1, mT, mTC, mP, mC, sv, a.nvs, wso, gsp);
     }
     // ---- SymCornerLoss: lanes scan the symmetry set, wave arg-min (ties -> lowest k), gradient from the winner only
     __shared__ float gsym[8][3];
@@ -347,30 +395,22 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
     }
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
-        float v = acc[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        const float v = wave_sum(acc[i]);
         if (l64 == 0) red[wave][i] = v;
     }
     __syncthreads();
-    if (lane < 5) {
+    if (lane < 5) a.sample_part[(long)b * 8 + lane] = sum_waves(&red[0][lane], 5);
+    auto epe_mm = [](const float (*A)[3], const float (*B)[3], int n) {      // per-sample EPE in mm (unmasked, absolute), val_metric.py:96-104
         float s = 0.f;
-#pragma unroll
-        for (int w = 0; w < PL_WAVES; ++w) s += red[w][lane];
-        a.sample_part[(long)b * 8 + lane] = s;
-    }
-    if (lane == 5 || lane == 6) {     // per-sample EPE in mm (unmasked, absolute), val_metric.py:96-104
-        float s = 0.f;
-        if (lane == 5) { for (int k = 0; k < 21; ++k) { float d[3] = {P[k][0] - T[k][0], P[k][1] - T[k][1], P[k][2] - T[k][2]}; s += sqrtf(dot3(d, d)); } s = s / 21.f * 1000.f; }
-        else { for (int k = 0; k < 8; ++k) { float d[3] = {C[k][0] - TC[k][0], C[k][1] - TC[k][1], C[k][2] - TC[k][2]}; s += sqrtf(dot3(d, d)); } s = s / 8.f * 1000.f; }
-        a.sample_part[(long)b * 8 + lane] = s;
-    }
+        for (int k = 0; k < n; ++k) { float d[3] = {A[k][0] - B[k][0], A[k][1] - B[k][1], A[k][2] - B[k][2]}; s += sqrtf(dot3(d, d)); }
+        return s / (float)n * 1000.f;
+    };
+    if (lane == 5) a.sample_part[(long)b * 8 + 5] = epe_mm(P, T, 21);
+    if (lane == 6) a.sample_part[(long)b * 8 + 6] = epe_mm(C, TC, 8);
     if constexpr (REG) {      // ManoLoss's joint term: unmasked squared error of the sample (honetloss.py:49-53)
         if (wave == 0) {
             const float d = l64 < 63 ? P[l64 / 3][l64 % 3] - T[l64 / 3][l64 % 3] : 0.f;
-            float v = d * d;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+            const float v = wave_sum(d * d);
             if (l64 == 0) a.sample_part[(long)b * 8 + 7] = v;
         }
     }
@@ -405,20 +445,12 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
         gC_w[wave][c][i] = s;
     }
     __syncthreads();
-    if (lane < 60) {
-        int k = lane / 3, i = lane % 3;
-        float s = 0.f;
-#pragma unroll
-        for (int w = 0; w < PL_WAVES; ++w) s += gpart_w[w][k][i];
-        gpart[k][i] = s;
-    }
+    if (lane < 60) (&gpart[0][0])[lane] = sum_waves(&gpart_w[0][0][0] + lane, 60);
     __syncthreads();
     const float wJ = a.w_jointsloss * a.lam_joints * 2.f / nJ, wC = a.w_jointsloss * a.lam_corners * 2.f / nC;
     if (lane < 63) {      // gradient wrt masked joint mP[k][i], then * vis
         int k = lane / 3, i = lane % 3;
-        float s = 0.f;
-#pragma unroll
-        for (int w = 0; w < PL_WAVES; ++w) s += gP_w[w][k][i];
+        float s = sum_waves(&gP_w[0][k][i], 63);
         s += wJ * (mP[k][i] - mT[k][i]);
         if (k >= 1) s += gpart[k - 1][i];
         for (int c = 1; c < 21; ++c) if (c_parents[c] == k) s -= gpart[c - 1][i];
@@ -427,9 +459,7 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
     }
     if (lane < 24) {
         int c = lane / 3, i = lane % 3;
-        float s = 0.f;
-#pragma unroll
-        for (int w = 0; w < PL_WAVES; ++w) s += gC_w[w][c][i];
+        float s = sum_waves(&gC_w[0][c][i], 24);
         s += wC * (mC[c][i] - mTC[c][i]) + gsym[c][i];
         gC[c][i] = s * vc[c];
     }
@@ -447,6 +477,7 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
         if (lane < P_) a.g_pose[(long)b * P_ + lane] = lane < 3 ? 0.f : a.w_mano * a.lam_pose_reg * 2.f / (B_ * (float)a.ncomps) * r_pose;
         if (lane < 10) a.g_shape[(long)b * 10 + lane] = a.w_mano * a.lam_shape_reg * 2.f / (B_ * 10.f) * r_shape;
     } else if (lane < 22) {     // xyz -> uvd
+        const float fx = Kc[0], fy = Kc[4], cx = Kc[2], cy = Kc[5];
         float u = kp[lane * 3], v = kp[lane * 3 + 1];
         float z = P[lane][2];
         float gx = gP[lane][0], gy = gP[lane][1], gz = gP[lane][2];
@@ -462,16 +493,8 @@ __global__ __launch_bounds__(PL_WAVES * 64) void pose_loss_kernel(PoseLossArgs a
             for (int c = 0; c < 8; ++c) s += gC[c][i] * CAN[c][j];
             GR[i][j] = s;
         }
-        float gx[3] = {GR[0][0], GR[1][0], GR[2][0]}, gy[3] = {GR[0][1], GR[1][1], GR[2][1]}, gz[3] = {GR[0][2], GR[1][2], GR[2][2]};
-        float t[3];
-        cross3(xh, gy, t); for (int i = 0; i < 3; ++i) gz[i] += t[i];        // y = z x x
-        cross3(gy, zh, t); for (int i = 0; i < 3; ++i) gx[i] += t[i];
-        float gzr[3]; float dz = dot3(zh, gz);
-        for (int i = 0; i < 3; ++i) gzr[i] = (gz[i] - zh[i] * dz) / zn;       // z = zraw / |zraw|
-        cross3(bvec, gzr, t); for (int i = 0; i < 3; ++i) gx[i] += t[i];      // zraw = x x b
-        float gb[3]; cross3(gzr, xh, gb);
-        float dx = dot3(xh, gx), ga[3];
-        for (int i = 0; i < 3; ++i) ga[i] = (gx[i] - xh[i] * dx) / an;        // x = a / |a|
+        float ga[3], gb[3];
+        rot6d_bwd(rot, GR, ga, gb);
         float* o = REG ? a.g_box6d + (long)b * a.box_stride + 3 : a.g_box6d + (long)b * 6;
         o[0] = ga[0]; o[1] = ga[1]; o[2] = ga[2]; o[3] = gb[0]; o[4] = gb[1]; o[5] = gb[2];
     }
@@ -488,17 +511,14 @@ __global__ __launch_bounds__(64) void pose_loss_finalize(const float* __restrict
     for (int c = 0; c < 8; ++c) {
         double s = 0.0;
         for (int b = lane; b < a.B; b += 64) s += (double)sample_part[(long)b * 8 + c];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        col[c] = s;
+        col[c] = wave_sum(s);
     }
     double reg_s = 0.0, reg_p = 0.0;
     if constexpr (REG) {      // the two regularisers: mean(shape^2), mean(pose[:, 3:]^2), same fixed order
         const int P_ = 3 + a.ncomps;
         for (int i = lane; i < a.B * 10; i += 64) { const double x = (double)a.mano_shape[i]; reg_s += x * x; }
         for (int i = lane; i < a.B * P_; i += 64) { const double x = (i % P_) >= 3 ? (double)a.mano_pose[i] : 0.0; reg_p += x * x; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { reg_s += __shfl_xor(reg_s, o, 64); reg_p += __shfl_xor(reg_p, o, 64); }
+        reg_s = wave_sum(reg_s); reg_p = wave_sum(reg_p);
     }
     if (lane != 0) return;
     const float B_ = (float)a.B;
@@ -531,52 +551,47 @@ __global__ __launch_bounds__(64) void pose_loss_finalize(const float* __restrict
     }
 }
 
-static int pose_loss_impl(const float* kp3d, const float* box6d, int box_stride, const float* root_joint,
-                            const float* cam_intr, const float* corners_can, const float* joints_3d,
-                            const float* corners_3d, const float* joints_vis, const float* corners_vis,
-                            const float* hand_views, int nvh, const int64_t* j0, const int64_t* j1, int njp,
-                            const int64_t* p0, const int64_t* p1, int npp, const float* scene_views, int nvs,
-                            const int64_t* s0, const int64_t* s1, int nsp, int B, int center_idx, float res_w,
-                            float res_h, const float* weights8_host, float* joints_abs, float* corners_abs, float* rotmat,
-                            float* uvd2d, float* sample_part, float* losses, float* g_kp3d, float* g_box6d,
-                            void* stream, const ab_symcorner* sym) {
-    if (!kp3d || !box6d || !root_joint || !cam_intr || !corners_can || !joints_3d || !corners_3d || !joints_vis ||
-        !corners_vis || !weights8_host || !joints_abs || !corners_abs || !rotmat || !sample_part || !losses)
-        return AB_EINVAL;
-    if (njp > PL_MAXPAIR || npp > PL_MAXPAIR || nsp > PL_MAXPAIR || nvh > PL_MAXVIEW || nvs > PL_MAXVIEW || B < 1) return AB_ESHAPE;
-    if ((weights8_host[5] != 0.f || weights8_host[6] != 0.f) && (!hand_views || !j0 || !j1 || !p0 || !p1)) return AB_EINVAL;
-    if (weights8_host[7] != 0.f && (!scene_views || !s0 || !s1)) return AB_EINVAL;
+// The fields both criteria set.  w: the first six entries of either weight table.  An ordinal loss the caller found absent (hand / scene
+// false) keeps NULL tables and zero counts, which is how the kernel knows it.
+static PoseLossArgs pl_args(const float* kp3d, const float* box6d, int box_stride, const float* root_joint, const float* cam_intr,
+                            const float* corners_can, const float* joints_3d, const float* corners_3d, const float* joints_vis,
+                            const float* corners_vis, bool hand, const float* hand_views, int nvh, const int64_t* j0, const int64_t* j1,
+                            int njp, const int64_t* p0, const int64_t* p1, int npp, bool scene, const float* scene_views, int nvs,
+                            const int64_t* s0, const int64_t* s1, int nsp, int B, const float* w, float* joints_abs, float* corners_abs,
+                            float* rotmat, float* sample_part, float* g_kp3d, float* g_box6d) {
     PoseLossArgs a = {};
     a.kp3d = kp3d; a.box6d = box6d; a.box_stride = box_stride; a.root_joint = root_joint; a.cam_intr = cam_intr;
-    a.corners_can = corners_can; a.joints_3d = joints_3d; a.corners_3d = corners_3d; a.joints_vis = joints_vis;
-    a.corners_vis = corners_vis; a.hand_views = hand_views; a.scene_views = scene_views;
-    a.j0 = j0; a.j1 = j1; a.p0 = p0; a.p1 = p1; a.s0 = s0; a.s1 = s1;
-    a.nvh = weights8_host[5] != 0.f || weights8_host[6] != 0.f ? nvh : 0; a.nvs = weights8_host[7] != 0.f ? nvs : 0;
-    a.njp = a.nvh ? njp : 0; a.npp = a.nvh ? npp : 0; a.nsp = a.nvs ? nsp : 0;
-    a.B = B; a.center_idx = center_idx; a.res_w = res_w; a.res_h = res_h; a.depth_range = 0.4f;
-    // weights8_host = {lam_joints, lam_corners, lam_hand_joint, lam_hand_part, lam_scene, w_JointsLoss, w_HandOrdLoss, w_SceneOrdLoss}
-    a.lam_joints = weights8_host[0]; a.lam_corners = weights8_host[1]; a.lam_hand_joint = weights8_host[2]; a.lam_hand_part = weights8_host[3];
-    a.lam_scene = weights8_host[4]; a.w_jointsloss = weights8_host[5]; a.w_handord = weights8_host[6]; a.w_sceneord = weights8_host[7];
-    a.joints_abs = joints_abs; a.corners_abs = corners_abs; a.rotmat = rotmat; a.uvd2d = uvd2d;
-    a.sample_part = sample_part; a.g_kp3d = g_kp3d; a.g_box6d = g_box6d;
-    if (sym && sym->K > 0 && sym->weight != 0.f && sym->lambda != 0.f) {
-        if (!sym->R || !sym->t || !sym->obj_idx || !sym->obj_transf) return AB_EINVAL;
-        a.sym_R = sym->R; a.sym_t = sym->t; a.obj_idx = sym->obj_idx; a.obj_transf = sym->obj_transf;
-        a.symK = sym->K; a.lam_sym = sym->lambda; a.w_sym = sym->weight; a.sym_loss = sym->loss_out;
-    }
-    pose_loss_kernel<0><<<B, PL_WAVES * 64, 0, as_stream(stream)>>>(a);
+    a.corners_can = corners_can; a.joints_3d = joints_3d; a.corners_3d = corners_3d; a.joints_vis = joints_vis; a.corners_vis = corners_vis;
+    if (hand) { a.hand_views = hand_views; a.j0 = j0; a.j1 = j1; a.p0 = p0; a.p1 = p1; a.nvh = nvh; a.njp = njp; a.npp = npp; }
+    if (scene) { a.scene_views = scene_views; a.s0 = s0; a.s1 = s1; a.nvs = nvs; a.nsp = nsp; }
+    a.B = B; a.depth_range = 0.4f;
+    a.lam_joints = w[0]; a.lam_corners = w[1]; a.lam_hand_joint = w[2]; a.lam_hand_part = w[3]; a.lam_scene = w[4]; a.w_jointsloss = w[5];
+    a.joints_abs = joints_abs; a.corners_abs = corners_abs; a.rotmat = rotmat; a.sample_part = sample_part;
+    a.g_kp3d = g_kp3d; a.g_box6d = g_box6d;
+    return a;
+}
+
+// The kernel, then the finalize pass on a copy whose normalisers of absent losses are guarded.  The two criteria's guards differ and both
+// are kept: the classification-based one replaces all of a loss's counts when its first pair list is empty (an empty part list beside a
+// non-empty joint list is left alone), the regression-based one every zero count on its own (a present loss may have no pairs).
+template <int REG>
+static int pl_run(const PoseLossArgs& a, float* losses, void* stream) {
+    pose_loss_kernel<REG><<<a.B, PL_WAVES * 64, 0, as_stream(stream)>>>(a);
     AB_LAUNCH_CHECK();
-    // guard the normalisers of disabled losses
     PoseLossArgs f = a;
-    if (f.njp == 0) { f.njp = 1; f.npp = 1; f.nvh = 1; }
-    if (f.nsp == 0) { f.nsp = 1; f.nvs = 1; }
-    pose_loss_finalize<0><<<1, 64, 0, as_stream(stream)>>>(sample_part, f, losses);
+    if (REG) {
+        for (int* n : {&f.njp, &f.npp, &f.nvh, &f.nsp, &f.nvs}) *n = *n ? *n : 1;
+    } else {
+        if (f.njp == 0) { f.njp = 1; f.npp = 1; f.nvh = 1; }
+        if (f.nsp == 0) { f.nsp = 1; f.nvs = 1; }
+    }
+    pose_loss_finalize<REG><<<1, 64, 0, as_stream(stream)>>>(a.sample_part, f, losses);
     AB_LAUNCH_CHECK();
     return 0;
 }
 
-// ---- M4 alone (eval-mode forwards: no targets, no criterion): hybridbaseline.py:49-96 for one sample per wave -- the same
-// arithmetic, in the same order, as the assembly phase of pose_loss_kernel above.
+// ---- M4 alone (eval-mode forwards: no targets, no criterion): hybridbaseline.py:49-96 for one sample per wave -- the assembly steps
+// pose_loss_kernel<0> calls, plus the root-relative outputs and the box root that only this kernel writes.
 __global__ __launch_bounds__(64) void pose_assemble_kernel(const float* __restrict__ kp3d, const float* __restrict__ box6d, int box_stride,
                                                            const float* __restrict__ root_joint, const float* __restrict__ cam_intr,
                                                            const float* __restrict__ corners_can, int center_idx, float res_w, float res_h,
@@ -585,6 +600,7 @@ __global__ __launch_bounds__(64) void pose_assemble_kernel(const float* __restri
                                                            float* __restrict__ corners_rel, float* __restrict__ boxroot) {
     const int b = blockIdx.x, lane = threadIdx.x;
     __shared__ float kp[66], Kc[9], CAN[8][3], RJ[3], avec[3], bvec[3], P[22][3], C[8][3], R[3][3];
+    const PoseLds s = {kp, Kc, CAN, RJ, P, C, R};
     kp[lane] = kp3d[(long)b * 66 + lane];
     if (lane < 2) kp[64 + lane] = kp3d[(long)b * 66 + 64 + lane];
     if (lane < 9) Kc[lane] = cam_intr[(long)b * 9 + lane];
@@ -592,54 +608,15 @@ __global__ __launch_bounds__(64) void pose_assemble_kernel(const float* __restri
     if (lane < 3) { RJ[lane] = root_joint[b * 3 + lane]; avec[lane] = box6d[(long)b * box_stride + lane]; }
     else if (lane < 6) bvec[lane - 3] = box6d[(long)b * box_stride + lane];
     __syncthreads();
-    const float fx = Kc[0], fy = Kc[4], cx = Kc[2], cy = Kc[5], rootz = RJ[2];
-    if (lane < 22) {
-        float u = kp[lane * 3], v = kp[lane * 3 + 1], d = kp[lane * 3 + 2];
-        float z = (d - 0.5f) * depth_range + rootz;
-        P[lane][0] = (u * res_w - cx) / fx * z;
-        P[lane][1] = (v * res_h - cy) / fy * z;
-        P[lane][2] = z;
-    }
-    if (lane == 0) {
-        float xh[3], yh[3], zh[3], zraw[3];
-        float n = sqrtf(dot3(avec, avec)); n = fmaxf(n, 1e-8f);
-        for (int i = 0; i < 3; ++i) xh[i] = avec[i] / n;
-        cross3(xh, bvec, zraw);
-        float m = sqrtf(dot3(zraw, zraw)); m = fmaxf(m, 1e-8f);
-        for (int i = 0; i < 3; ++i) zh[i] = zraw[i] / m;
-        cross3(zh, xh, yh);
-        for (int i = 0; i < 3; ++i) { R[i][0] = xh[i]; R[i][1] = yh[i]; R[i][2] = zh[i]; }
-    }
+    uvd2xyz(s, lane, res_w, res_h, depth_range);
+    if (lane == 0) { Rot6d rot; rot6d_fwd(avec, bvec, R, rot); }
     __syncthreads();
-    if (lane < 24) {
-        int c = lane / 3, i = lane % 3;
-        const float* can = CAN[c];
-        C[c][i] = R[i][0] * can[0] + R[i][1] * can[1] + R[i][2] * can[2] + P[21][i];
-    }
+    box_corners(s, lane);
     __syncthreads();
-    if (lane < 63) {
-        const float v = P[lane / 3][lane % 3];
-        joints_abs[(long)b * 63 + lane] = v;
-        if (joints_rel) joints_rel[(long)b * 63 + lane] = v - P[center_idx][lane % 3];
-    }
-    if (lane < 24) {
-        const float v = C[lane / 3][lane % 3];
-        corners_abs[(long)b * 24 + lane] = v;
-        if (corners_rel) corners_rel[(long)b * 24 + lane] = v - P[center_idx][lane % 3];
-    }
-    if (lane < 9) rotmat[(long)b * 9 + lane] = R[lane / 3][lane % 3];
+    pose_write(s, lane, b, res_w, res_h, joints_abs, corners_abs, rotmat, uvd2d);
+    if (lane < 63 && joints_rel) joints_rel[(long)b * 63 + lane] = P[lane / 3][lane % 3] - P[center_idx][lane % 3];
+    if (lane < 24 && corners_rel) corners_rel[(long)b * 24 + lane] = C[lane / 3][lane % 3] - P[center_idx][lane % 3];
     if (lane < 3 && boxroot) boxroot[b * 3 + lane] = P[21][lane];
-    if (uvd2d) {
-        float* o = uvd2d + (long)b * 90;
-        if (lane < 21) { o[lane * 3] = kp[lane * 3]; o[lane * 3 + 1] = kp[lane * 3 + 1]; o[lane * 3 + 2] = kp[lane * 3 + 2]; }
-        if (lane < 8) {
-            const float* K = Kc;
-            float X = C[lane][0], Y = C[lane][1], Z = C[lane][2];
-            float hx = K[0] * X + K[1] * Y + K[2] * Z, hy = K[3] * X + K[4] * Y + K[5] * Z, hz = K[6] * X + K[7] * Y + K[8] * Z;
-            o[(21 + lane) * 3] = hx / hz / res_w; o[(21 + lane) * 3 + 1] = hy / hz / res_h; o[(21 + lane) * 3 + 2] = 0.f;
-        }
-        if (lane < 3) o[29 * 3 + lane] = kp[21 * 3 + lane];
-    }
 }
 
 extern "C" int ab_pose_assemble(const float* kp3d, const float* box6d, int box_stride, const float* root_joint, const float* cam_intr,
@@ -662,13 +639,15 @@ extern "C" int ab_pose_loss(const float* kp3d, const float* box6d, int box_strid
                             float res_h, const float* weights8_host, float* joints_abs, float* corners_abs, float* rotmat,
                             float* uvd2d, float* sample_part, float* losses, float* g_kp3d, float* g_box6d,
                             void* stream) {
-    return pose_loss_impl(kp3d, box6d, box_stride, root_joint, cam_intr, corners_can, joints_3d, corners_3d, joints_vis,
-                          corners_vis, hand_views, nvh, j0, j1, njp, p0, p1, npp, scene_views, nvs, s0, s1, nsp, B, center_idx,
-                          res_w, res_h, weights8_host, joints_abs, corners_abs, rotmat, uvd2d, sample_part, losses, g_kp3d,
-                          g_box6d, stream, nullptr);
+    return ab_pose_loss_sym(kp3d, box6d, box_stride, root_joint, cam_intr, corners_can, joints_3d, corners_3d, joints_vis,
+                            corners_vis, hand_views, nvh, j0, j1, njp, p0, p1, npp, scene_views, nvs, s0, s1, nsp, B, center_idx,
+                            res_w, res_h, weights8_host, nullptr, joints_abs, corners_abs, rotmat, uvd2d, sample_part, losses,
+                            g_kp3d, g_box6d, stream);
 }
 
-// ab_pose_loss + SymCornerLoss (sym may be NULL): the final loss (losses[5]) and the corner gradients include it
+// the classification-based model's criterion: pose_loss_kernel<0>, with SymCornerLoss (sym may be NULL) in the final loss (losses[5]) and
+// the corner gradients.  weights8_host = {lam_joints, lam_corners, lam_hand_joint, lam_hand_part, lam_scene, w_JointsLoss, w_HandOrdLoss,
+// w_SceneOrdLoss}
 extern "C" int ab_pose_loss_sym(const float* kp3d, const float* box6d, int box_stride, const float* root_joint,
                                 const float* cam_intr, const float* corners_can, const float* joints_3d,
                                 const float* corners_3d, const float* joints_vis, const float* corners_vis,
@@ -678,10 +657,26 @@ extern "C" int ab_pose_loss_sym(const float* kp3d, const float* box6d, int box_s
                                 float res_h, const float* weights8_host, const ab_symcorner* sym, float* joints_abs,
                                 float* corners_abs, float* rotmat, float* uvd2d, float* sample_part, float* losses,
                                 float* g_kp3d, float* g_box6d, void* stream) {
-    return pose_loss_impl(kp3d, box6d, box_stride, root_joint, cam_intr, corners_can, joints_3d, corners_3d, joints_vis,
-                          corners_vis, hand_views, nvh, j0, j1, njp, p0, p1, npp, scene_views, nvs, s0, s1, nsp, B, center_idx,
-                          res_w, res_h, weights8_host, joints_abs, corners_abs, rotmat, uvd2d, sample_part, losses, g_kp3d,
-                          g_box6d, stream, sym);
+    if (!kp3d || !box6d || !root_joint || !cam_intr || !corners_can || !joints_3d || !corners_3d || !joints_vis ||
+        !corners_vis || !weights8_host || !joints_abs || !corners_abs || !rotmat || !sample_part || !losses)
+        return AB_EINVAL;
+    if (njp > PL_MAXPAIR || npp > PL_MAXPAIR || nsp > PL_MAXPAIR || nvh > PL_MAXVIEW || nvs > PL_MAXVIEW || B < 1) return AB_ESHAPE;
+    const float* w = weights8_host;
+    if ((w[5] != 0.f || w[6] != 0.f) && (!hand_views || !j0 || !j1 || !p0 || !p1)) return AB_EINVAL;
+    if (w[7] != 0.f && (!scene_views || !s0 || !s1)) return AB_EINVAL;
+    // an ordinal loss without views has no pairs either
+    const bool hand = (w[5] != 0.f || w[6] != 0.f) && nvh != 0, scene = w[7] != 0.f && nvs != 0;
+    PoseLossArgs a = pl_args(kp3d, box6d, box_stride, root_joint, cam_intr, corners_can, joints_3d, corners_3d, joints_vis, corners_vis, hand,
+                             hand_views, nvh, j0, j1, njp, p0, p1, npp, scene, scene_views, nvs, s0, s1, nsp, B, w, joints_abs, corners_abs,
+                             rotmat, sample_part, g_kp3d, g_box6d);
+    a.center_idx = center_idx; a.res_w = res_w; a.res_h = res_h; a.uvd2d = uvd2d;
+    a.w_handord = w[6]; a.w_sceneord = w[7];
+    if (sym && sym->K > 0 && sym->weight != 0.f && sym->lambda != 0.f) {
+        if (!sym->R || !sym->t || !sym->obj_idx || !sym->obj_transf) return AB_EINVAL;
+        a.sym_R = sym->R; a.sym_t = sym->t; a.obj_idx = sym->obj_idx; a.obj_transf = sym->obj_transf;
+        a.symK = sym->K; a.lam_sym = sym->lambda; a.w_sym = sym->weight; a.sym_loss = sym->loss_out;
+    }
+    return pl_run<0>(a, losses, stream);
 }
 
 // ---- the regression-based model's criterion (HOPRegNet + [ManoLoss, JointsLoss, HandOrdLoss, SceneOrdLoss]): pose_loss_kernel<1>
@@ -705,24 +700,13 @@ extern "C" int ab_reg_pose_loss(const float* joints_pred, const float* mano_pca_
     if (hand && (njp < 0 || npp < 0 || njp > PL_MAXPAIR || npp > PL_MAXPAIR || nvh > PL_MAXVIEW)) return AB_ESHAPE;
     if (scene && (nsp < 0 || nsp > PL_MAXPAIR || nvs > PL_MAXVIEW)) return AB_ESHAPE;
     const float* w = weights12_host;
-    PoseLossArgs a = {};
-    a.kp3d = joints_pred; a.box6d = transf; a.box_stride = transf_stride; a.root_joint = root_joint; a.cam_intr = cam_intr;
-    a.corners_can = corners_can; a.joints_3d = joints_3d; a.corners_3d = corners_3d; a.joints_vis = joints_vis; a.corners_vis = corners_vis;
-    if (hand) { a.hand_views = hand_views; a.j0 = j0; a.j1 = j1; a.p0 = p0; a.p1 = p1; a.nvh = nvh; a.njp = njp; a.npp = npp; }
-    if (scene) { a.scene_views = scene_views; a.s0 = s0; a.s1 = s1; a.nvs = nvs; a.nsp = nsp; }
-    a.B = B; a.res_w = a.res_h = 1.f; a.depth_range = 0.4f;
-    a.lam_joints = w[0]; a.lam_corners = w[1]; a.lam_hand_joint = w[2]; a.lam_hand_part = w[3]; a.lam_scene = w[4];
-    a.w_jointsloss = w[5]; a.w_handord = hand ? w[6] : 0.f; a.w_sceneord = scene ? w[7] : 0.f;
+    PoseLossArgs a = pl_args(joints_pred, transf, transf_stride, root_joint, cam_intr, corners_can, joints_3d, corners_3d, joints_vis,
+                             corners_vis, hand, hand_views, nvh, j0, j1, njp, p0, p1, npp, scene, scene_views, nvs, s0, s1, nsp, B, w,
+                             joints_abs, corners_abs, rotmat, sample_part, g_joints, g_transf);
+    a.res_w = a.res_h = 1.f;
+    a.w_handord = hand ? w[6] : 0.f; a.w_sceneord = scene ? w[7] : 0.f;
     a.lam_shape_reg = w[8]; a.lam_pose_reg = w[9]; a.lam_mano_joints = w[10]; a.w_mano = w[11];
     a.mano_pose = mano_pca_pose; a.mano_shape = mano_shape; a.ncomps = ncomps;
-    a.joints_abs = joints_abs; a.corners_abs = corners_abs; a.rotmat = rotmat; a.sample_part = sample_part;
-    a.g_kp3d = g_joints; a.g_box6d = g_transf; a.g_pose = g_pose; a.g_shape = g_shape;
-    pose_loss_kernel<1><<<B, PL_WAVES * 64, 0, as_stream(stream)>>>(a);
-    AB_LAUNCH_CHECK();
-    PoseLossArgs f = a;      // guard the normalisers of absent losses
-    if (!hand || f.njp == 0 || f.npp == 0) { f.njp = f.njp ? f.njp : 1; f.npp = f.npp ? f.npp : 1; f.nvh = f.nvh ? f.nvh : 1; }
-    if (!scene || f.nsp == 0) { f.nsp = 1; f.nvs = f.nvs ? f.nvs : 1; }
-    pose_loss_finalize<1><<<1, 64, 0, as_stream(stream)>>>(sample_part, f, losses);
-    AB_LAUNCH_CHECK();
-    return 0;
+    a.g_pose = g_pose; a.g_shape = g_shape;
+    return pl_run<1>(a, losses, stream);
 }

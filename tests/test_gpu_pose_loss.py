@@ -60,6 +60,88 @@ def test_fused_pose_loss_vs_oracle(B, size, seed):
     np.testing.assert_allclose(o["sample_part"][:, 5].cpu().numpy(), epe.numpy(), rtol=1e-4)
 
 
+@pytest.mark.parametrize("B,seed", [(1, 0), (5, 1)])
+def test_pose_assemble_equals_criterion_assembly(B, seed):
+    """ab_pose_assemble and the assembly phase of the fused criterion are one body: the four outputs both write are the same bits."""
+    from artiboost_amd import kernels
+    from artiboost_amd.criterions import FusedPoseCriterion
+    size = 256
+    batch = make_batch(B, size, seed + 10)
+    g = torch.Generator().manual_seed(seed)
+    kp3d = torch.rand(B, 22, 3, generator=g).cuda()
+    box_buf = torch.zeros(B, 64).cuda()
+    box_buf[:, :6] = torch.randn(B, 6, generator=g).cuda()
+    tb = {k: v.cuda() for k, v in batch.items()}
+    fused = FusedPoseCriterion(_crit(), [size, size], 0)
+    random.seed(seed + 3); torch.manual_seed(seed + 3)
+    fused.draw(torch.device("cuda"))
+    o = fused(kp3d, box_buf, 64, tb)
+    p = kernels.pose_assemble(kp3d, box_buf[:, :6], tb["root_joint"], tb["cam_intr"], tb["corners_can"], 0, [size, size])
+    for k in ("joints_3d_abs", "corners_3d_abs", "box_rot_rotmat", "uvd2d"):
+        assert torch.equal(p[k], o[k]), k
+
+
+@pytest.mark.parametrize("npair,nview", [(96, 48), (1, 1)], ids=["maxima", "minima"])
+def test_fused_pose_loss_pair_and_view_limits(npair, nview):
+    """PL_MAXPAIR joint, part and scene pairs with PL_MAXVIEW views of each kind (the only input that takes the kernel's fixed 5 / 4 / 7
+    wave split, with more than one pass per wave; the default draws fit the per-wave split exactly), and one pair and one view of each
+    kind (most lanes of every pair group idle): the selections are placed in the losses' draw buffers and the three oracle losses are
+    evaluated in float64 on the same selections.  Tolerances of test_fused_pose_loss_vs_oracle."""
+    from artiboost_amd.criterions import FusedPoseCriterion
+    B, size, seed = 2, 256, 6          # a seed at which the oracle's single pair of each kind has an active hinge
+    batch = make_batch(B, size, seed + 30)
+    g = torch.Generator().manual_seed(seed)
+    kp3d = torch.rand(B, 22, 3, generator=g)
+    box6d = torch.randn(B, 6, generator=g)
+    torch.manual_seed(seed + 3)
+    hviews, sviews = lo.draw_view_vectors(nview - 1), lo.draw_view_vectors(nview - 1)      # the fixed (0, 0, 1) + nview - 1 drawn
+    jsel = torch.randperm(len(lo.JOINT_PAIRS), generator=g)[:npair].tolist()
+    psel = torch.randperm(len(lo.PART_PAIRS), generator=g)[:npair].tolist()
+    ssel = torch.randperm(len(lo.HO_PAIRS), generator=g)[:npair].tolist()
+    # oracle, float64
+    b64 = {k: v.double() for k, v in batch.items() if k != "image"}
+    kp64, box64 = kp3d.double().requires_grad_(True), box6d.double().requires_grad_(True)
+    pose = lo.uvd2xyz(kp64, b64["root_joint"], b64["cam_intr"], [size, size])
+    R = lo.ortho6d_to_rotmat(box64)
+    corners = torch.matmul(R, b64["corners_can"].permute(0, 2, 1)).permute(0, 2, 1) + pose[:, 21:22]
+    preds = {"joints_3d_abs": pose[:, :21], "corners_3d_abs": corners}
+    l1, losses = lo.joints_loss(preds, b64)
+    l2, d2 = lo.hand_ord_loss(preds, b64, hviews.double(), jsel, psel)
+    l3, d3 = lo.scene_ord_loss(preds, b64, sviews.double(), ssel)
+    losses.update(d2); losses.update(d3)
+    losses["final_loss"] = 0.5 * l1 + 0.2 * l2 + 0.1 * l3
+    losses["final_loss"].backward()
+    # fused kernel on the same selections
+    crit = _crit()
+    fused = FusedPoseCriterion(crit, [size, size], 0)
+    dev = torch.device("cuda")
+    hd, sd = fused.hand.draws, fused.scene.draws
+    hd.put("views", hviews, dev)
+    hd.put("j0", torch.tensor([lo.JOINT_PAIRS[i][0] for i in jsel]), dev)
+    hd.put("j1", torch.tensor([lo.JOINT_PAIRS[i][1] for i in jsel]), dev)
+    hd.put("p0", torch.tensor([lo.PART_PAIRS[i][0] for i in psel]), dev)
+    hd.put("p1", torch.tensor([lo.PART_PAIRS[i][1] for i in psel]), dev)
+    sd.put("views", sviews, dev)
+    sd.put("i0", torch.tensor([lo.HO_PAIRS[i][0] for i in ssel]), dev)
+    sd.put("i1", torch.tensor([lo.HO_PAIRS[i][1] for i in ssel]), dev)
+    box_buf = torch.zeros(B, 64).cuda()
+    box_buf[:, :6] = box6d.cuda()
+    tb = {k: v.cuda() for k, v in batch.items()}
+    o = fused(kp3d.cuda(), box_buf, 64, tb)
+    np.testing.assert_allclose(o["joints_3d_abs"].cpu().numpy(), pose[:, :21].detach().numpy(), rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(o["corners_3d_abs"].cpu().numpy(), corners.detach().numpy(), rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(o["box_rot_rotmat"].cpu().numpy(), R.detach().numpy(), rtol=1e-5, atol=1e-6)
+    ld = fused.losses_dict()
+    for k in ("joints_3d_loss", "corners_3d_loss", "joint_ord_loss", "part_ord_loss", "scene_ord_loss", "final_loss"):
+        print(k, float(ld[k]), float(losses[k]))
+        assert float(losses[k]) > 0.0, k          # every term is exercised
+        np.testing.assert_allclose(float(ld[k]), float(losses[k]), rtol=2e-5, err_msg=k)
+    gk = kp64.grad.numpy()
+    np.testing.assert_allclose(o["g_kp3d"].cpu().numpy(), gk, rtol=2e-4, atol=2e-5 * np.abs(gk).max())
+    gb = box64.grad.numpy()
+    np.testing.assert_allclose(o["g_box6d"].cpu().numpy(), gb, rtol=2e-4, atol=2e-5 * np.abs(gb).max())
+
+
 @pytest.mark.parametrize("graph", [False, True])
 def test_fused_train_step_matches_reference_golden(golden_dir, graph):
     from test_gpu_learner import build
