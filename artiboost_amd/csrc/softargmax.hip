@@ -285,8 +285,15 @@ __global__ __launch_bounds__(256) void sam_bwd_scalar(const T* __restrict__ logi
         float m = stat[bc * 2], s = stat[bc * 2 + 1];
         float pr = __expf(x - m) / s;
         float u = uvd[bc * 3] * z, v = uvd[bc * 3 + 1] * z, dd = uvd[bc * 3 + 2] * z;  // sum p*coord
+        if (NORM == 1) { u = uvd[bc * 3]; v = uvd[bc * 3 + 1]; dd = uvd[bc * 3 + 2]; }   // sigmoid: the centre is uvd itself (see below)
         float g = g_uvd[bc * 3] * (cu - u) + g_uvd[bc * 3 + 1] * (cv - v) + g_uvd[bc * 3 + 2] * ((float)d / D - dd);
         float out = pr * g / z;
+        if (NORM == 1) {
+            // d uvd / dx = w (1 - w) (coord - uvd) / (S + 1e-7), S = sum w = s w_max: the 1e-7 is not relative to S here (the softmax
+            // sums to 1, a sigmoid volume of very negative logits to ~1e-7), so the factor is the forward's w_max / (s w_max + 1e-7)
+            const float wmax = __expf(m);
+            out = __expf(x - m) * (wmax / (s * wmax + 1e-7f)) * g;
+        }
         if (g_conf) {
             float cf = conf[bc];
             out += g_conf[bc] * cf * ((x == m ? 1.f : 0.f) - pr);
@@ -308,6 +315,7 @@ template <> __device__ __forceinline__ void st_pair<bf16_t>(bf16_t* p, float a, 
 // d logits = p * (g_u*(cu-u) + g_v*(cv-v) + g_d*(d/D-dd)) / z  [+ g_conf * conf * ([x == max] - p)],  p = exp(x-m)/s.
 // Everything that depends only on (b, channel) is folded into per-lane constants once per workgroup:
 //   out = exp(x - m) * (A*cu + Bv*cv + K),  A = g_u/(s z), Bv = g_v/(s z), K = (g_d*(d/D-dd) - g_u*u - g_v*v)/(s z)
+// (sigmoid head: 1/(s z) -> w_max / (s w_max + 1e-7) and u, v, dd are uvd itself, times d log sigmoid / dx at the end)
 // SPLIT (T = float): dlogits leaves as the split-bf16 planes the final layer's data / weight gradients consume
 // (dl_hi, dl_lo: bf16 [B, H, W, C*DP]) instead of fp32 -- no separate split pass over the largest activation of the net.
 // colpart != NULL (PIX pixels per workgroup): the workgroup also writes the column sums of its dlogits rows (fixed order: a
@@ -341,6 +349,11 @@ __global__ __launch_bounds__(256) void sam_bwd(const T* __restrict__ logits, int
             float u = uvd[bc * 3] * z, v = uvd[bc * 3 + 1] * z, dd = uvd[bc * 3 + 2] * z;  // sum p*coord
             float gu = g_uvd[bc * 3], gv = g_uvd[bc * 3 + 1], gd = g_uvd[bc * 3 + 2];
             float sc = 1.f / (s * z);
+            if (NORM == 1) {     // sigmoid: 1 / (S + 1e-7) in units of w_max (as stage 2), and the centre is uvd itself -- see sam_bwd_scalar
+                const float wmax = __expf(m);
+                sc = wmax / (s * wmax + 1e-7f);
+                u = uvd[bc * 3]; v = uvd[bc * 3 + 1]; dd = uvd[bc * 3 + 2];
+            }
             a = gu * sc; bb = gv * sc;
             k0 = (gd * ((float)d / D - dd) - gu * u - gv * v) * sc;
             is = 1.f / s;
@@ -433,26 +446,53 @@ __global__ __launch_bounds__(256) void sam_bias_finalize(const float* __restrict
 
 extern "C" int ab_softargmax3d_ntiles(int H, int W) { return (H * W + SAM_TILE_PIX - 1) / SAM_TILE_PIX; }
 
+#define SAM_BWD_PIX_BIAS 64   // pixels per workgroup of the split backward that also reduces the bias gradient
+
+// The dispatch of every launcher below, as one host function: the launch macros switch on its result, so what it reports is what runs.
+//   entry 0 (stage 1):   10 = sam_stage1_scalar;  100 + 10 KP + (D <= 32) = sam_stage1<T, KP, N>, last digit 1: the 32-lane class merge
+//   entry 1 (backward):  20 = sam_bwd_scalar;     PIX * 100 + V * 10 + KV = sam_bwd<T, false, PIX, N, V, KV>          (1628)
+//   entry 2, 3 (split):  10000 + PIX * 100 + V * 10 + KV = sam_bwd<float, true, PIX, N, V, KV>    (11628 / 11643 / 11644, 16428 / 16443 / 16444)
+static int sam_quad() {
+    static const int quad = getenv("AB_SAM_BWD_QUAD") ? atoi(getenv("AB_SAM_BWD_QUAD")) : 1;
+    return quad;
+}
+extern "C" int ab_softargmax3d_form(int entry, int dtype, int C, int D, int DP, int norm) {
+    if (entry < 0 || entry > 3) return AB_EINVAL;
+    if (C <= 0 || D <= 0 || DP < D || C > SAM_MAXCH || DP > SAM_MAXCH || C * DP > SAM_MAXCH || norm < 0 || norm > 1) return AB_ESHAPE;
+    const int CD = C * DP;
+    if (entry >= 2 && (CD & 1)) return AB_ESHAPE;
+    if (dtype != AB_DT_F32 && (dtype != AB_DT_BF16 || entry >= 2)) return AB_EINVAL;
+    if (entry == 0) {
+        if (CD & 1) return 10;
+        const int kp = (CD + 127) / 128;
+        return 100 + 10 * (kp <= 2 ? 2 : kp <= 4 ? 4 : kp <= 6 ? 6 : 8) + (D <= 32 ? 1 : 0);
+    }
+    if (entry == 1) return (CD & 1) ? 20 : SAM_BWD_PIX * 100 + 28;
+    const int pix = entry == 2 ? SAM_BWD_PIX : SAM_BWD_PIX_BIAS;
+    const int vk = (sam_quad() && CD % 4 == 0) ? (CD <= 768 ? 43 : 44) : 28;
+    return 10000 + pix * 100 + vk;
+}
+
 static int sam_fwd_impl(const void* logits, int dtype, int B, int C, int D, int DP, int H, int W, float* part,
                         float* uvd, float* conf, float* stat, int norm, void* stream) {
     if (!logits || !part || !uvd || !conf || !stat) return AB_EINVAL;
-    if (B <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || DP < D || C * DP > SAM_MAXCH || norm < 0 || norm > 1) return AB_ESHAPE;
+    if (B <= 0 || H <= 0 || W <= 0) return AB_ESHAPE;
+    const int form = ab_softargmax3d_form(0, dtype, C, D, DP, norm);
+    if (form < 0) return form;
     int ntile = ab_softargmax3d_ntiles(H, W);
     dim3 grid(ntile, B);
-    const bool pair = ((C * DP) & 1) == 0;
     hipStream_t st = as_stream(stream);
-    const int kp = (C * DP + 127) / 128;
 #define SAM_S1(TT, NN) \
-    do { \
-        if (!pair) sam_stage1_scalar<TT, NN><<<grid, SAM_THREADS, 0, st>>>((const TT*)logits, C, D, DP, H, W, ntile, part); \
-        else if (kp <= 2) sam_stage1<TT, 2, NN><<<grid, SAM_THREADS, 0, st>>>((const TT*)logits, C, D, DP, H, W, ntile, part); \
-        else if (kp <= 4) sam_stage1<TT, 4, NN><<<grid, SAM_THREADS, 0, st>>>((const TT*)logits, C, D, DP, H, W, ntile, part); \
-        else if (kp <= 6) sam_stage1<TT, 6, NN><<<grid, SAM_THREADS, 0, st>>>((const TT*)logits, C, D, DP, H, W, ntile, part); \
-        else sam_stage1<TT, 8, NN><<<grid, SAM_THREADS, 0, st>>>((const TT*)logits, C, D, DP, H, W, ntile, part); \
-    } while (0)
-    if (dtype == AB_DT_F32) { if (norm) SAM_S1(float, 1); else SAM_S1(float, 0); }
-    else if (dtype == AB_DT_BF16) { if (norm) SAM_S1(bf16_t, 1); else SAM_S1(bf16_t, 0); }
-    else return AB_EINVAL;
+    switch (form) { \
+    case 10: sam_stage1_scalar<TT, NN><<<grid, SAM_THREADS, 0, st>>>((const TT*)logits, C, D, DP, H, W, ntile, part); break; \
+    case 120: case 121: sam_stage1<TT, 2, NN><<<grid, SAM_THREADS, 0, st>>>((const TT*)logits, C, D, DP, H, W, ntile, part); break; \
+    case 140: case 141: sam_stage1<TT, 4, NN><<<grid, SAM_THREADS, 0, st>>>((const TT*)logits, C, D, DP, H, W, ntile, part); break; \
+    case 160: case 161: sam_stage1<TT, 6, NN><<<grid, SAM_THREADS, 0, st>>>((const TT*)logits, C, D, DP, H, W, ntile, part); break; \
+    case 180: case 181: sam_stage1<TT, 8, NN><<<grid, SAM_THREADS, 0, st>>>((const TT*)logits, C, D, DP, H, W, ntile, part); break; \
+    default: return AB_EINVAL; \
+    }
+    if (dtype == AB_DT_F32) { if (norm) SAM_S1(float, 1) else SAM_S1(float, 0) }
+    else { if (norm) SAM_S1(bf16_t, 1) else SAM_S1(bf16_t, 0) }
 #undef SAM_S1
     AB_LAUNCH_CHECK();
     sam_stage2<<<B * C, 64, 0, st>>>(part, C, ntile, uvd, conf, stat, norm);
@@ -482,20 +522,21 @@ extern "C" int ab_softargmax3d_stage2(const float* part, int B, int C, int ntile
 static int sam_bwd_impl(const void* logits, int dtype, int B, int C, int D, int DP, int H, int W, const float* uvd,
                         const float* conf, const float* stat, const float* g_uvd, const float* g_conf, void* dlogits, int norm, void* stream) {
     if (!logits || !uvd || !conf || !stat || !g_uvd || !dlogits) return AB_EINVAL;
-    if (B <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || DP < D || C * DP > SAM_MAXCH || norm < 0 || norm > 1) return AB_ESHAPE;
+    if (B <= 0 || H <= 0 || W <= 0) return AB_ESHAPE;
+    const int form = ab_softargmax3d_form(1, dtype, C, D, DP, norm);
+    if (form < 0) return form;
     if (norm && g_conf) return AB_EINVAL;          // the sigmoid head's confidence (max w) is not differentiated here
-    const bool pair = ((C * DP) & 1) == 0;
     hipStream_t st = as_stream(stream);
-    dim3 grid(pair ? (H * W + SAM_BWD_PIX - 1) / SAM_BWD_PIX : (H * W + 3) / 4, B);
+    dim3 grid(form == 20 ? (H * W + 3) / 4 : (H * W + SAM_BWD_PIX - 1) / SAM_BWD_PIX, B);
 #define SAM_BWD_ARGS(TT) (const TT*)logits, C, D, DP, H, W, uvd, conf, stat, g_uvd, g_conf, (TT*)dlogits
 #define SAM_BW(TT, NN) \
-    do { \
-        if (pair) sam_bwd<TT, false, SAM_BWD_PIX, NN><<<grid, 256, 0, st>>>(SAM_BWD_ARGS(TT)); \
-        else sam_bwd_scalar<TT, NN><<<grid, 256, 0, st>>>(SAM_BWD_ARGS(TT)); \
-    } while (0)
-    if (dtype == AB_DT_F32) { if (norm) SAM_BW(float, 1); else SAM_BW(float, 0); }
-    else if (dtype == AB_DT_BF16) { if (norm) SAM_BW(bf16_t, 1); else SAM_BW(bf16_t, 0); }
-    else return AB_EINVAL;
+    switch (form) { \
+    case 1628: sam_bwd<TT, false, SAM_BWD_PIX, NN, 2, 8><<<grid, 256, 0, st>>>(SAM_BWD_ARGS(TT)); break; \
+    case 20: sam_bwd_scalar<TT, NN><<<grid, 256, 0, st>>>(SAM_BWD_ARGS(TT)); break; \
+    default: return AB_EINVAL; \
+    }
+    if (dtype == AB_DT_F32) { if (norm) SAM_BW(float, 1) else SAM_BW(float, 0) }
+    else { if (norm) SAM_BW(bf16_t, 1) else SAM_BW(bf16_t, 0) }
 #undef SAM_BW
 #undef SAM_BWD_ARGS
     AB_LAUNCH_CHECK();
@@ -516,20 +557,22 @@ extern "C" int ab_softargmax3d_bwd_norm(const void* logits, int dtype, int B, in
 // the split-plane launches: 4 channels per lane and group where C*DP allows (3 groups up to 768 channels, else 4), otherwise pairs
 #define SAM_BWX_ARGS logits, C, D, DP, H, W, uvd, conf, stat, g_uvd, g_conf, nullptr, (bf16_t*)dl_hi, (bf16_t*)dl_lo, colpart
 #define SAM_BWX_N(PIXV, NN) \
-    do { \
-        static const int quad = getenv("AB_SAM_BWD_QUAD") ? atoi(getenv("AB_SAM_BWD_QUAD")) : 1; \
-        if (quad && (C * DP) % 4 == 0 && C * DP <= 768) sam_bwd<float, true, PIXV, NN, 4, 3><<<grid, 256, 0, st>>>(SAM_BWX_ARGS); \
-        else if (quad && (C * DP) % 4 == 0) sam_bwd<float, true, PIXV, NN, 4, 4><<<grid, 256, 0, st>>>(SAM_BWX_ARGS); \
-        else sam_bwd<float, true, PIXV, NN><<<grid, 256, 0, st>>>(SAM_BWX_ARGS); \
-    } while (0)
-#define SAM_BWX(PIXV) do { if (norm) SAM_BWX_N(PIXV, 1); else SAM_BWX_N(PIXV, 0); } while (0)
+    switch (form) { \
+    case 10000 + PIXV * 100 + 43: sam_bwd<float, true, PIXV, NN, 4, 3><<<grid, 256, 0, st>>>(SAM_BWX_ARGS); break; \
+    case 10000 + PIXV * 100 + 44: sam_bwd<float, true, PIXV, NN, 4, 4><<<grid, 256, 0, st>>>(SAM_BWX_ARGS); break; \
+    case 10000 + PIXV * 100 + 28: sam_bwd<float, true, PIXV, NN, 2, 8><<<grid, 256, 0, st>>>(SAM_BWX_ARGS); break; \
+    default: return AB_EINVAL; \
+    }
+#define SAM_BWX(PIXV) do { if (norm) SAM_BWX_N(PIXV, 1) else SAM_BWX_N(PIXV, 0) } while (0)
 
 // fp32 logits in, dlogits out as split-bf16 planes (C * DP even)
 static int sam_bwd_x3_impl(const float* logits, int B, int C, int D, int DP, int H, int W, const float* uvd,
                            const float* conf, const float* stat, const float* g_uvd, const float* g_conf,
                            void* dl_hi, void* dl_lo, int norm, void* stream) {
     if (!logits || !uvd || !conf || !stat || !g_uvd || !dl_hi || !dl_lo) return AB_EINVAL;
-    if (B <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || DP < D || C * DP > SAM_MAXCH || ((C * DP) & 1) || norm < 0 || norm > 1) return AB_ESHAPE;
+    if (B <= 0 || H <= 0 || W <= 0) return AB_ESHAPE;
+    const int form = ab_softargmax3d_form(2, AB_DT_F32, C, D, DP, norm);
+    if (form < 0) return form;
     if (norm && g_conf) return AB_EINVAL;
     dim3 grid((H * W + SAM_BWD_PIX - 1) / SAM_BWD_PIX, B);
     hipStream_t st = as_stream(stream);
@@ -546,13 +589,14 @@ extern "C" int ab_softargmax3d_bwd_x3(const float* logits, int B, int C, int D, 
 
 // ... and the column sums of dlogits over all B*H*W rows (the bias gradient of the layer that produced the logits) -> dbias [C*DP]
 // fp32.  colpart: scratch of ab_softargmax3d_bwd_x3_bias_rows(B, H, W) x C*DP floats.
-#define SAM_BWD_PIX_BIAS 64
 extern "C" int ab_softargmax3d_bwd_x3_bias_rows(int B, int H, int W) { return B * ((H * W + SAM_BWD_PIX_BIAS - 1) / SAM_BWD_PIX_BIAS); }
 static int sam_bwd_x3_bias_impl(const float* logits, int B, int C, int D, int DP, int H, int W, const float* uvd,
                                 const float* conf, const float* stat, const float* g_uvd, const float* g_conf,
                                 void* dl_hi, void* dl_lo, float* colpart, float* dbias, int norm, void* stream) {
     if (!logits || !uvd || !conf || !stat || !g_uvd || !dl_hi || !dl_lo || !colpart || !dbias) return AB_EINVAL;
-    if (B <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || DP < D || C * DP > SAM_MAXCH || ((C * DP) & 1) || norm < 0 || norm > 1) return AB_ESHAPE;
+    if (B <= 0 || H <= 0 || W <= 0) return AB_ESHAPE;
+    const int form = ab_softargmax3d_form(3, AB_DT_F32, C, D, DP, norm);
+    if (form < 0) return form;
     if (norm && g_conf) return AB_EINVAL;
     dim3 grid((H * W + SAM_BWD_PIX_BIAS - 1) / SAM_BWD_PIX_BIAS, B);
     hipStream_t st = as_stream(stream);

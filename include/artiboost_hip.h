@@ -47,6 +47,15 @@ int ab_wall_clock_khz(void);
  * conf   : float [B, C]     (max softmax probability)
  * stat   : float [B, C, 2]  (global max, sum exp(x - max)) kept for backward                                  */
 int ab_softargmax3d_ntiles(int H, int W);
+/* Host only, launches nothing: which kernel instantiation an entry point runs for (dtype, C, D, DP, norm = norm_type) -- the launchers switch
+ * on this very function.  entry: 0 = forward stage 1, 1 = ab_softargmax3d_bwd[_norm], 2 = ab_softargmax3d_bwd_x3 (split planes),
+ * 3 = ab_softargmax3d_bwd_x3_bias (split planes + bias gradient).  Returns
+ *   entry 0:    10 = scalar kernel (C*DP odd);  100 + 10*KP + m = pair kernel walking KP in {2, 4, 6, 8} groups of 128 channels,
+ *               m = 1: depth bins merged by 32 lanes per class (D <= 32), m = 0: by one thread per class (D > 32)
+ *   entry 1:    20 = scalar kernel (C*DP odd);  PIX*100 + V*10 + KV = pair kernel, PIX pixels per workgroup, KV groups of V channels (1628)
+ *   entry 2, 3: 10000 + PIX*100 + V*10 + KV  (PIX = 16 | 64;  V, KV = 4, 3 for C*DP % 4 == 0 up to 768;  4, 4 above;  2, 8 otherwise)
+ * or the AB_E* code with which the entry point refuses these arguments (AB_ESHAPE: DP < D, C*DP > 1024, odd C*DP on entries 2 and 3).  */
+int ab_softargmax3d_form(int entry, int dtype, int C, int D, int DP, int norm);
 int ab_softargmax3d_fwd(const void* logits, int dtype, int B, int C, int D, int DP, int H, int W,
                         float* part, float* uvd, float* conf, float* stat, void* stream);
 /* dlogits[b,h,w,c*D+d] = p * ( g_uvd . (coord - uvd) ) / (1+1e-7) + g_conf * conf * (argmax? 1 : 0 - p)
@@ -68,6 +77,7 @@ int ab_softargmax3d_bwd_x3_bias(const float* logits, int B, int C, int D, int DP
 /* NORM_TYPE of IntegralDeconvHead (anakin/models/simplebaseline.py:16-40): norm_type 0 = "softmax" (the entry points above),
  * 1 = "sigmoid": w = sigmoid(x), conf = max w, uvd = sum(w * coord) / (sum(w) + 1e-7) -- evaluated in the log domain with the same
  * kernels (x' = log sigmoid(x); `stat` holds (log w_max, sum w / w_max)).  g_conf must be NULL for the sigmoid head.
+ * Its backward is dlogits = w (1 - w) ( g_uvd . (coord - uvd) ) / (sum w + 1e-7): the 1e-7 is absolute, as in the forward.
  * ("divide_sum" is not implemented: raw weights can be negative, and the reference's own docstring advises against it.)
  * _bwd_x3_norm: dlogits as split planes; colpart + dbias non-NULL: also the bias gradient (scratch as for _bwd_x3_bias). */
 int ab_softargmax3d_fwd_norm(const void* logits, int dtype, int B, int C, int D, int DP, int H, int W, int norm_type, float* part,
