@@ -1194,7 +1194,36 @@ def interaction(hand_verts, hand_faces, hand_orient, obj_verts, obj_faces, vert_
     return o
 
 
-CL_SCAN_ALL = 1                                 # AB_CL_SCAN_ALL: scan every vertex, not only the candidates (same bits; the A/B of the benchmark)
+IAS_ROW = {"obj_pen_max": 0, "obj_pen_mean": 1, "obj_min_dist": 2, "obj_inside_frac": 3, "obj_contact": 4}      # slots 5..7 reserved (NaN)
+IAS_COUNTS = {"n_obj_inside": 0, "n_obj_verts": 1}
+
+
+def interaction_sym(hand_verts, hand_faces, hand_orient, obj_verts, vert_off, obj_row, rot, tsl, no_max, contact_thr=0.005, want_sdf=False):
+    """ab_interaction_sym (eager only, never under graph capture): the reverse direction of `interaction`, the vertices of the object
+    rot[b] can + tsl[b] of the packed table (obj_verts [*,3] fp32, vert_off int32 [n_obj+1], obj_row int64 [B]) against the hand mesh
+    (hand_verts [B,Nh,3], hand_faces int32 [Fh,3], hand_orient +-1), scanned in the object's canonical frame.  no_max: the largest vertex
+    count of the table's objects (ObjectMeshTable.no_max).  Distances in metres.  -> dict: rows [B,8] (columns IAS_ROW, the others NaN),
+    counts int32 [B,2] (IAS_COUNTS); with want_sdf sdf_obj [B,no_max] (-d inside the hand, +d outside) and wind_obj [B,no_max]
+    (orientation x winding number), NaN past the sample's object."""
+    B, Nh, Fh, n_obj, no_max = hand_verts.shape[0], hand_verts.shape[1], hand_faces.shape[0], vert_off.numel() - 1, int(no_max)
+    for what, t, dt, numel in (("hand_faces", hand_faces, torch.int32, Fh * 3), ("vert_off", vert_off, torch.int32, None),
+                               ("obj_row", obj_row, torch.int64, B), ("obj_verts", obj_verts, torch.float32, None)):
+        if t.dtype != dt or (t.numel() != numel if numel is not None else t.numel() < (3 if what == "obj_verts" else 2)):
+            raise ValueError(f"interaction_sym: {what} must be {dt} with {numel if numel is not None else 'enough'} elements, got {t.dtype} {tuple(t.shape)}")
+    ins = {"hand_verts": _f32_of("interaction_sym", "hand_verts", hand_verts, B * Nh * 3), "rot": _f32_of("interaction_sym", "rot", rot, B * 9),
+           "tsl": _f32_of("interaction_sym", "tsl", tsl, B * 3)}
+    dev = hand_verts.device
+    o = {"rows": torch.empty((B, 8), dtype=torch.float32, device=dev), "counts": torch.empty((B, 2), dtype=torch.int32, device=dev)}
+    if want_sdf:
+        o["sdf_obj"], o["wind_obj"] = torch.empty((B, no_max), dtype=torch.float32, device=dev), torch.empty((B, no_max), dtype=torch.float32, device=dev)
+    ws = _workspace(L.lib().ab_interaction_sym_workspace(L.i(B), L.i(Nh), L.i(no_max)), dev)
+    L.check(L.lib().ab_interaction_sym(ins["hand_verts"], L.ptr(hand_faces), L.i(Nh), L.i(Fh), L.f(hand_orient), L.ptr(obj_verts), L.ptr(vert_off),
+                                       L.i(n_obj), L.ptr(obj_row), ins["rot"], ins["tsl"], L.i(B), L.i(no_max), L.f(contact_thr), o["rows"], o["counts"],
+                                       o.get("sdf_obj"), o.get("wind_obj"), L.ptr(ws), L.stream()), "ab_interaction_sym")
+    return o
+
+
+CL_SCAN_ALL = 1                               # AB_CL_SCAN_ALL: scan every vertex, not only the candidates (same bits; the A/B of the benchmark)
 CL_MAX_ZONES = 16
 CL_COUNTS = {"n_inside": 0, "n_candidates": 1}
 

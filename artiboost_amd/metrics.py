@@ -999,6 +999,46 @@ def interaction_values_torch(hand_verts, hand_faces, hand_orient, obj_verts, obj
     return out
 
 
+def interaction_sym_values_torch(hand_verts, hand_faces, hand_orient, obj_verts, vert_off, obj_row, rot, tsl, no_max, contact_thr=0.005, want_sdf=False):
+    """The definitions of ab_interaction_sym (include/artiboost_hip.h) as torch ops in hand_verts' dtype: the route of CPU tensors and, in
+    float64, the reference of the tests.  Same arguments and the same dict as kernels.interaction_sym: rows [B,8] (columns
+    kernels.IAS_ROW, the others NaN), counts int32 [B,2] and, with want_sdf, sdf_obj and wind_obj [B,no_max], NaN past the sample's object.
+    Like the kernel it takes the hand into the object's canonical frame, triangles ((hv[b] - t) @ R)[hand_faces], and scans them for the
+    canonical object vertices, one [No_r, Fh] block per sample."""
+    from .kernels import IAS_ROW as C
+    hv = hand_verts.detach()
+    dt, dev = hv.dtype, hv.device
+    B, Nh, no_max = hv.shape[0], hv.shape[1], int(no_max)
+    n_obj = int(vert_off.numel()) - 1
+    nan = float("nan")
+    rows = torch.full((B, 8), nan, dtype=dt, device=dev)
+    counts = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+    out = {"rows": rows, "counts": counts}
+    if want_sdf:
+        out["sdf_obj"], out["wind_obj"] = torch.full((B, no_max), nan, dtype=dt, device=dev), torch.full((B, no_max), nan, dtype=dt, device=dev)
+    vo = [int(x) for x in vert_off.cpu()]
+    orow = [min(max(int(r), 0), n_obj - 1) for r in obj_row.cpu()]
+    hf = hand_faces.to(dev).long().reshape(-1, 3).clamp(0, Nh - 1)
+    R_all, t_all = rot.detach().to(device=dev, dtype=dt).reshape(B, 3, 3), tsl.detach().to(device=dev, dtype=dt).reshape(B, 3)
+    for b in range(B):
+        r = orow[b]
+        n = min(max(vo[r + 1] - vo[r], 1), no_max)
+        can = obj_verts[vo[r]:vo[r] + n].to(device=dev, dtype=dt)
+        tri = ((hv[b] - t_all[b]) @ R_all[b])[hf]
+        w, d2 = _triangle_scan(can, tri, True)
+        w, d = hand_orient * w, d2.sqrt()
+        inside = w > 0.5
+        n_in = inside.sum()
+        din = torch.where(inside, d, torch.zeros_like(d))
+        rows[b, C["obj_pen_max"]], rows[b, C["obj_pen_mean"]] = din.max(), din.sum() / n_in.clamp_min(1).to(dt)
+        rows[b, C["obj_min_dist"]], rows[b, C["obj_inside_frac"]] = d.min(), n_in.to(dt) / n
+        rows[b, C["obj_contact"]] = ((n_in > 0) | (d.min() <= contact_thr)).to(dt)
+        counts[b, 0], counts[b, 1] = n_in.to(torch.int32), n
+        if want_sdf:
+            out["sdf_obj"][b, :n], out["wind_obj"][b, :n] = torch.where(inside, -d, d), w
+    return out
+
+
 class ObjectMeshTable:
     """The object meshes of the interaction measures as one packed table (the layout of assets.SceneAssets: verts [*,3] fp32, faces int32
     [*,3] with indices local to the object, vert_off / face_off int32 [n_obj + 1]), each mesh's orientation (the sign of its signed volume,
@@ -1016,6 +1056,7 @@ class ObjectMeshTable:
         self.verts, self.faces = np.concatenate(vs), np.concatenate(fs)
         self.vert_off, self.face_off = np.asarray(vo, np.int32), np.asarray(fo, np.int32)
         self.orient = np.asarray(orient, np.float32)
+        self.no_max = max(len(v) for v in vs)      # the largest vertex count of the objects (the No_max of ab_interaction_sym): a host integer
         # the closed axis-aligned box of each object's canonical vertices, lo xyz | hi xyz: minima and maxima of fp32 values, so exact in fp32
         self.box = np.stack([np.concatenate([v.min(0), v.max(0)]) for v in vs]).astype(np.float32)
         self.obj_ids = [int(i) for i in obj_ids]
@@ -1076,6 +1117,7 @@ class ObjectMeshTable:
 
 
 IA_MEASURES = ("pen_depth_mm", "pen_mean_mm", "min_dist_mm", "inside_frac", "contact_ratio", "inter_vol_cm3", "capped")
+IA_SYM_MEASURES = ("obj_pen_depth_mm", "obj_pen_mean_mm", "obj_min_dist_mm", "obj_inside_frac", "sym_pen_depth_mm", "sym_contact_ratio")      # with SYMMETRIC
 
 
 @METRIC.register_module
@@ -1089,13 +1131,20 @@ class InteractionMetric(Metric):
     the annotation with a `gt_` prefix (targs: hand_verts_3d + root_joint, obj_transf).  OBJ_MESHES {SOURCE: assets, DATASET: HO3D} builds
     the stand-in table as synth.py builds its assets; `set_obj_meshes(table)` is for callers that hold the real meshes.  HIP tensors: one
     ab_interaction call per batch and group (through the evaluator's memo), nothing read back in feed_device; CPU tensors:
-    interaction_values_torch in their dtype.  A batch that lacks a key is skipped and logged once."""
+    interaction_values_torch in their dtype.  A batch that lacks a key is skipped and logged once.
+    SYMMETRIC (default false) adds the reverse direction, the object's vertices against the hand mesh: means over
+    samples of their maximum and mean depth inside the hand (`obj_pen_depth_mm`, `obj_pen_mean_mm`), their smallest distance to it
+    (`obj_min_dist_mm`), the fraction of them inside (`obj_inside_frac`), the larger of the two directions' maximum depths
+    (`sym_pen_depth_mm`, what the hand-object literature reports) and the fraction of samples in contact in either direction
+    (`sym_contact_ratio`).  One ab_interaction_sym call per batch and group under a memo key of its own (CPU tensors:
+    interaction_sym_values_torch); the one-sided call keeps its key, so a plain and a symmetric metric of one evaluator share it."""
 
     def __init__(self, **cfg):
         self.hand_key = cfg.get("HAND_KEY", "hand_verts_3d_abs")
         self.rot_key, self.tsl_key = cfg.get("ROT_KEY", "box_rot_rotmat"), cfg.get("TSL_KEY", "boxroot_3d_abs")
         self.contact_thr, self.voxel = float(cfg.get("CONTACT_MM", 5.0)) / 1000.0, float(cfg.get("VOXEL_MM", 5.0)) / 1000.0
         self.max_voxels, self.volume, self.report_gt = int(cfg.get("MAX_VOXELS", 262144)), bool(cfg.get("VOLUME", True)), bool(cfg.get("REPORT_GT", False))
+        self.symmetric = bool(cfg.get("SYMMETRIC", False))
         if self.voxel <= 0 or self.contact_thr < 0 or not 1 <= self.max_voxels <= 1 << 24:
             raise ValueError("InteractionMetric: VOXEL_MM > 0, CONTACT_MM >= 0 and 1 <= MAX_VOXELS <= 2^24")
         self.table = None
@@ -1116,7 +1165,9 @@ class InteractionMetric(Metric):
         return self
 
     def reset(self):
-        self.sums = {}       # prefix -> float64 [9]: sums of the six row slots | samples not capped | capped | samples
+        # prefix -> float64 [9]: sums of the six row slots | samples not capped | capped | samples; with SYMMETRIC six more: sums of the four
+        # obj_* slots | of max(pen_max, obj_pen_max) | of max(contact, obj_contact)
+        self.sums = {}
 
     def _inputs(self, preds, targs, prefix):
         """(hand [B,Nh,3], rot [B,3,3], tsl [B,3], obj_idx [B]) of a group, or the name of the key the batch lacks."""
@@ -1151,6 +1202,19 @@ class InteractionMetric(Metric):
                   self.table.rows(obj_idx.to(dev)), f(rot), f(tsl), contact_thr=self.contact_thr, voxel=self.voxel, max_voxels=self.max_voxels,
                   flags=flags)
 
+    def values_sym(self, hand, rot, tsl, obj_idx):
+        """The dict of kernels.interaction_sym for one batch: HIP tensors through ab_interaction_sym (fp32), CPU tensors through the torch route."""
+        if self.table is None:
+            raise RuntimeError("InteractionMetric: no object meshes (OBJ_MESHES in the config, or set_obj_meshes)")
+        from . import kernels as K
+        dev = hand.device
+        tb = self.table.on(dev)
+        dt = torch.float32 if hand.is_cuda else hand.dtype
+        f = lambda t: t.to(device=dev, dtype=dt).contiguous()      # noqa: E731
+        fn = K.interaction_sym if hand.is_cuda else interaction_sym_values_torch
+        return fn(f(hand), tb["hand_faces"], self.table.hand_orient, tb["obj_verts"], tb["vert_off"], self.table.rows(obj_idx.to(dev)), f(rot), f(tsl),
+                  self.table.no_max, contact_thr=self.contact_thr)
+
     def feed_device(self, preds, targs, memo=None, **kwargs):
         names, out = [], []
         for prefix in ("", "gt_") if self.report_gt else ("",):
@@ -1172,13 +1236,24 @@ class InteractionMetric(Metric):
             vol = torch.where(capped | rows[:, 5].isnan(), torch.zeros_like(rows[:, 5]), rows[:, 5])
             n = torch.full((), float(rows.shape[0]), dtype=torch.float64, device=rows.device)
             names.append(prefix)
-            out.append(torch.stack([rows[:, 0].sum(), rows[:, 1].sum(), rows[:, 2].sum(), rows[:, 3].sum(), rows[:, 4].sum(), vol.sum(),
-                                    (~capped).sum().double(), capped.sum().double(), n]))
+            cols = [rows[:, 0].sum(), rows[:, 1].sum(), rows[:, 2].sum(), rows[:, 3].sum(), rows[:, 4].sum(), vol.sum(),
+                    (~capped).sum().double(), capped.sum().double(), n]
+            if self.symmetric:
+                sk = ("interaction_sym", prefix, self.hand_key, self.rot_key, self.tsl_key, self.contact_thr, id(self.table))
+                sval = memo.get(sk) if memo is not None else None
+                if sval is None:
+                    sval = self.values_sym(*got)
+                    if memo is not None:
+                        memo[sk] = sval
+                srows = sval["rows"].double()
+                cols += [srows[:, 0].sum(), srows[:, 1].sum(), srows[:, 2].sum(), srows[:, 3].sum(),
+                         torch.maximum(rows[:, 0], srows[:, 0]).sum(), torch.maximum(rows[:, 4], srows[:, 4]).sum()]
+            out.append(torch.stack(cols))
         return out, names
 
     def feed_host(self, arrays, extra=None, **kwargs):
         for prefix, a in zip(extra or [], arrays):
-            self.sums[prefix] = self.sums.get(prefix, np.zeros(9)) + np.asarray(a, np.float64)
+            self.sums[prefix] = self.sums.get(prefix, np.zeros(15 if self.symmetric else 9)) + np.asarray(a, np.float64)
 
     def feed(self, preds, targs, **kwargs):
         out, names = self.feed_device(preds, targs)
@@ -1195,6 +1270,10 @@ class InteractionMetric(Metric):
             if self.volume:
                 out[prefix + "inter_vol_cm3"] = 1.0e6 * s[5] / s[6] if s[6] > 0 else float("nan")
                 out[prefix + "capped"] = int(s[7])
+            if self.symmetric:
+                out.update({prefix + "obj_pen_depth_mm": 1000.0 * s[9] / n, prefix + "obj_pen_mean_mm": 1000.0 * s[10] / n,
+                            prefix + "obj_min_dist_mm": 1000.0 * s[11] / n, prefix + "obj_inside_frac": s[12] / n,
+                            prefix + "sym_pen_depth_mm": 1000.0 * s[13] / n, prefix + "sym_contact_ratio": s[14] / n})
         return out
 
     def __str__(self):

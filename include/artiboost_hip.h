@@ -901,6 +901,47 @@ int ab_contact_loss(const float* hand_verts, const int32_t* zone_id, int Nh, int
                     float lambda_r, float lambda_a, int flags, float* loss, float* rep, float* att, int32_t* counts, float* sdf,
                     float* g_hand, float* g_rot, float* g_tsl, void* workspace, void* stream);
 
+/* ---- Symmetric interaction measures: object vertices inside the hand mesh, eager only (csrc/interact_sym.hip) --------
+ * The reverse direction of ab_interaction: the vertices of the sample's object are the queries, the posed hand's triangles the mesh.  A
+ * small or pointed object pressed into the palm has no hand vertex inside it while dozens of its vertices are inside the hand.  Solid
+ * angle, winding number w, orientation o, "inside <=> o w > 0.5", the closest point by the region form and the first minimum in face order
+ * are those of the comment block of ab_interaction above, computed by the same functions (csrc/ia_tile.h): a distance has the same bits.
+ * hand_verts [B,Nh,3] fp32, hand_faces int32 [Fh,3] (indices clamped into [0, Nh) while staging), hand_orient +-1 from the host.  The
+ * objects are the packed table of ab_interaction, of which only obj_verts [*,3] and vert_off int32 [n_obj + 1] are read (the object's
+ * faces and orientation play no part in this direction); r = obj_row[b] clamped into [0, n_obj), No_r = min(vert_off[r+1] - vert_off[r],
+ * No_max) canonical vertices c_i.
+ *   frame          each hand vertex is taken into the object's canonical frame once, v' = rot[b]^T (v - tsl[b]) (the arithmetic of
+ *                  ab_interaction's queries); the queries are the canonical vertices c_i straight from the table.  No posed object vertex
+ *                  is formed, and coordinates stay within the object's extent.
+ *   per vertex     inside_i <=> hand_orient w_hand'(c_i) > 0.5;  d_i = the distance of c_i to the hand's triangles
+ *   per sample     obj_pen_max = max over inside vertices of d_i (0 when none), obj_pen_mean their mean (0 when none),
+ *                  obj_min_dist = min_i d_i, obj_inside_frac = n_obj_inside / No_r, obj_contact = 1 when n_obj_inside > 0 or
+ *                  obj_min_dist <= contact_thr, else 0
+ *   optional       sdf_obj [B,No_max]: -d_i inside, +d_i outside; wind_obj [B,No_max]: o w; entries at i >= No_r are NaN (each may be NULL)
+ * No query is culled by the hand's box: on a mesh that is not watertight (the stand-in hand's kept face list has boundary loops and
+ * non-manifold edges) a vertex outside the box can still have o w > 0.5, and the definition does not depend on a shortcut.
+ * rows [B, AB_IAS_ROW] fp32, written in full, metres: the slots below, the reserved ones NaN.  counts int32 [B,2]: n_obj_inside, No_r.
+ * workspace: ab_interaction_sym_workspace(B, Nh, No_max) bytes (the canonical hand vertices [B,Nh,3] and four words per chunk).
+ * Launches: (1) one thread per (sample, hand vertex) writes the canonical hand; (2) a FIXED grid of ceil(No_max / 256) chunks x B samples,
+ * 256 threads, one object vertex per thread, the hand's triangles through LDS in SoA tiles of 512: a workgroup whose chunk starts at or
+ * past No_r fills its slots of sdf_obj / wind_obj with NaN and leaves before any barrier, lanes past No_r of the last live chunk compute
+ * on a clamped vertex and are masked out of every reduction; a chunk leaves n_inside, the sum and maximum of the inside depths and the
+ * smallest distance in the workspace (ballot and popcount, wave butterflies, the four waves in turn); (3) one thread per sample adds its
+ * live chunks in turn and writes the row and the counts.  The host reads nothing back between the launches.  No atomics:
+ * two calls give the same bits, and a sample's row, counts, sdf_obj and wind_obj do not depend on the batch around it.  1 <= B <= 65535, 1 <= Nh, Fh, No_max <= 2^24, n_obj >= 1, contact_thr >= 0, hand_orient +-1, rows and counts
+ * non-NULL: AB_EINVAL otherwise (the tables' contents are trusted).
+ * Like ab_interaction, this entry point is not captured in a hipGraph anywhere in this project (DESIGN.md sections 19, 24, 27).          */
+#define AB_IAS_ROW 8           /* floats per sample row: */
+#define AB_IAS_OBJ_PEN_MAX 0
+#define AB_IAS_OBJ_PEN_MEAN 1
+#define AB_IAS_OBJ_MIN_DIST 2
+#define AB_IAS_OBJ_INSIDE_FRAC 3
+#define AB_IAS_OBJ_CONTACT 4   /* slots 5..7 reserved (NaN) */
+long ab_interaction_sym_workspace(int B, int Nh, int No_max);
+int ab_interaction_sym(const float* hand_verts, const int32_t* hand_faces, int Nh, int Fh, float hand_orient, const float* obj_verts,
+                       const int32_t* vert_off, int n_obj, const int64_t* obj_row, const float* rot, const float* tsl, int B, int No_max,
+                       float contact_thr, float* rows, int32_t* counts, float* sdf_obj, float* wind_obj, void* workspace, void* stream);
+
 /* ---- BOP pose errors of the evaluator, eager only (ab_mspd: csrc/mssd.hip, ab_vsd: csrc/bop_recall.hip) ---------------
  * The two errors of bop_toolkit's pose_error.py that, with ab_mssd, make the BOP average recall: MSPD and VSD.
  *
@@ -1037,6 +1078,7 @@ int ab_vsd(const float* obj_verts, const int32_t* obj_faces, const int32_t* vert
  * @check ab_mesh_metrics: pred >= B*N*3; targ >= B*M*3; root >= B*3; thresholds_host >= T; rows >= B*AB_MM_ROW; counts >= B*T*4; d_pg pa_d_pg >= B*N; d_gp pa_d_gp >= B*M; bytes workspace >= ab_mesh_metrics_workspace(B,N,M)
  * @check ab_interaction: hand_verts >= B*Nh*3; hand_faces >= Fh*3; vert_off face_off >= n_obj+1; obj_verts >= 3; obj_faces >= 3; obj_orient >= n_obj; obj_row >= B; rot >= B*9; tsl >= B*3; rows >= B*AB_IA_ROW; counts >= B*4; sdf wind >= B*Nh; bytes workspace >= ab_interaction_workspace(B,Nh,max_voxels)
  * @check ab_contact_loss: hand_verts g_hand >= B*Nh*3; zone_id >= Nh; vert_off face_off >= n_obj+1; obj_verts >= 3; obj_faces >= 3; obj_orient >= n_obj; obj_box >= n_obj*6; obj_row mask rep att >= B; rot g_rot >= B*9; tsl g_tsl >= B*3; loss >= 1; counts >= B*2; sdf >= B*Nh; bytes workspace >= ab_contact_loss_workspace(B,Nh)
+ * @check ab_interaction_sym: hand_verts >= B*Nh*3; hand_faces >= Fh*3; vert_off >= n_obj+1; obj_verts >= 3; obj_row >= B; rot >= B*9; tsl >= B*3; rows >= B*AB_IAS_ROW; counts >= B*2; sdf_obj wind_obj >= B*No_max; bytes workspace >= ab_interaction_sym_workspace(B,Nh,No_max)
  * @check ab_mspd: can pred_pts >= B*V*3; obj_transf >= B*16; obj_idx mspd >= B; sym_R >= n_obj*Kmax*9; sym_t >= n_obj*Kmax*3; sym_count >= n_obj; pred_R cam_intr >= B*9; pred_t >= B*3; bytes workspace >= ab_mspd_workspace(B,Kmax,V)
  * @check ab_vsd: obj_verts >= 3; obj_faces >= 3; vert_off face_off >= n_obj+1; rows >= B; rot_est rot_gt cam_intr >= B*9; tsl_est tsl_gt >= B*3; depth_test >= B*H*W; occ_verts >= B*Nv*3; occ_faces >= Nf*3; taus_host >= T; diameter >= n_obj; counts >= B*(2+T); err >= B*T; depth_out >= B*3*H*W; bytes workspace >= ab_vsd_workspace(B,max_obj_verts,Nv,W,H,T)
  */
